@@ -15,14 +15,21 @@ host-side normalization into pinned staging) happens before it, as the reference
 figure excludes addTransaction (SkipList.cpp:1069-1078, 1087-1090).  `total_txns_per_s` is the
 reference's "total" figure: addTransaction (and the H2D) inside the timed loop as well.
 
-Passes, in order, each on its own batches: warmup; a per-kernel profile (events around every
-kernel, timing level 3) that names the dominant kernel (largest device time); the timed region
-(events around that kernel only, on 1 batch in 4: `roofline`); PCIe-inclusive, add+detect
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the
+line: `value`, `ms_per_step` and what the timed region's own counters give; every figure of another
+pass is null.  `--dump-outputs DIR` writes the last timed step's verdicts (and combined conflict
+bytes under a process group) as DIR/<name>.npy; the inputs depend only on the arguments.  Everything
+below that is not the warmup or the timed region runs only with `--full`.
+
+Passes, in order, each on its own batches: warmup; the timed region (no event inside it); a
+per-kernel profile (events around every kernel, timing level 3) that names the dominant kernel
+(largest device time); the roofline pass (events around that kernel only, on 1 batch in 4:
+`roofline`); PCIe-inclusive, add+detect
 ("total"), synchronous (one batch at a time through detect_conflicts, as Resolver.actor.cpp:179-194
 calls it: `sync_*` and per-batch latency), device-bound (batches queued behind a hold kernel, then
 released: the device's own rate) and per-phase breakdown passes.
 
-After timing, the whole batch sequence is replayed on the CPU restatement of the reference
+After timing (`--full`), the whole batch sequence is replayed on the CPU restatement of the reference
 algorithm (oracle/skiplist_baseline.cpp, with the reference's bounded removeBefore,
 SkipList.cpp:880-889) and every GPU verdict is compared: `parity` in the JSON line.  That replay's
 time over the timed batches is `cpu_baseline`: one thread pinned to one core like skipListTest's
@@ -107,7 +114,35 @@ def parse():
     ap.add_argument("--too-old-frac", type=float, default=0.0,
                     help="share of transactions whose snapshot sits at the MVCC window's edge (about half of "
                     "them TooOld, SkipList.cpp:770)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run every other pass (per-kernel profile, roofline, "
+                    "PCIe-inclusive, total, synchronous, device-bound, per-phase breakdown) and the CPU replay "
+                    "(parity, cpu_baseline); without it a run warms up, times --steps batches and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (its verdicts; with a process group also the "
+                    "combined conflict bytes) as DIR/<name>.npy, float32")
+    args = ap.parse_args()
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.profile_steps = args.roof_steps = args.h2d_steps = args.total_steps = 0
+        args.sync_steps = args.hold_steps = args.breakdown_steps = 0
+        args.no_cpu_baseline = True
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20  # bound on what --dump-outputs writes in all
+
+
+def dump_outputs(path, arrays, seed, files):
+    """arrays: name -> 1-d array, written as path/<name>.npy in float32; `files`: how many files all
+    ranks write together.  An array past its share of DUMP_MAX_BYTES is cut to a fixed sample (sorted
+    indices drawn from `seed`)."""
+    os.makedirs(path, exist_ok=True)
+    cap = (DUMP_MAX_BYTES - 4096 * files) // 4 // files
+    for name, a in arrays.items():
+        a = np.asarray(a).reshape(-1)
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(seed).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float32))
 
 
 def log(*a):
@@ -629,6 +664,14 @@ def main():
     host_timed = {k: v / args.steps * 1e3 for k, v in host.items()}
     for k in ("host_ms_prepare", "host_ms_record", "host_ms_submit"):  # inside detect_async (engine's clock)
         host_timed["engine_" + k[8:]] = st[k] / max(1, st["batches"])
+    if args.dump_outputs and args.steps > 0:
+        # what the last timed step handed its caller: this resolver's verdict per transaction (0 conflict,
+        # 1 too old, 2 committed) and, under a process group, the conflict bytes combined over the resolvers
+        last = timed_hi - 1
+        dump = {"verdicts" if world == 1 else f"verdicts_rank{rank}": verdicts[last]}
+        if dist is not None and rank == 0:
+            dump["conflict_bytes"] = combined[last].cpu().numpy()
+        dump_outputs(args.dump_outputs, dump, args.seed, files=world + (dist is not None))
 
     # per-kernel profile, after the timed region so that it sees the history the roofline pass runs
     # on (the kernels can change with it: a base tier past kSplitCheckMinBase splits the read check):
@@ -648,7 +691,8 @@ def main():
     # this configuration and build is committed: the profile pass's events also count the time a
     # kernel waits for its stream's turn behind the other streams' kernels.
     build = roofline.build_id(ROOT)
-    rp_kernels, rp_note = roofline.rocprof_kernels(ROOT, args.workload, p.txns, p.history, build)
+    rp_kernels, rp_note = (roofline.rocprof_kernels(ROOT, args.workload, p.txns, p.history, build) if args.full
+                           else (None, None))
     dominant_source = "profile pass (events around every kernel)"
     if rp_kernels:
         ranked = [k for k in rp_kernels if k in kprof]  # (kernels this history state launches)
@@ -805,10 +849,12 @@ def main():
     # the dominant kernel's line from the timed region's own events (fdbcs_set_timed_kernel).
     # Algorithmic bytes per launch: roofline.py (SURVEY §8(d) model per kernel, batch shapes of
     # this run).
-    sample = [mine_at(i) for i in range(timed_lo, min(timed_hi, timed_lo + 8))]
-    shape = roofline.shape_of(sample, st_prof if args.profile_steps > 0 else st, len(vers),
-                              dir_share=directory_share(kb, ko, sample))
-    table = roofline.kernel_table(kprof, shape, st_prof if args.profile_steps > 0 else None)
+    table = {}
+    if args.full:
+        sample = [mine_at(i) for i in range(timed_lo, min(timed_hi, timed_lo + 8))]
+        shape = roofline.shape_of(sample, st_prof if args.profile_steps > 0 else st, len(vers),
+                                  dir_share=directory_share(kb, ko, sample))
+        table = roofline.kernel_table(kprof, shape, st_prof if args.profile_steps > 0 else None)
     roof = None
     if dominant and args.roof_steps > 0 and dominant not in kprof_timed:
         print(f"[rank {rank}] roofline pass timed no launch of {dominant!r} (timed: {sorted(kprof_timed)}, "
@@ -844,7 +890,7 @@ def main():
         }
 
     combine_check = None
-    if dist is not None:
+    if dist is not None and args.full:
         # the device-side combine against host-built conflict bytes of the same verdicts
         bad = 0
         # (the same batches on every rank: the first 24 of the timed region and after)
@@ -911,6 +957,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": elapsed / args.steps * 1e3,
         "higher_is_better": True,
         "scaling": "weak",

@@ -6,7 +6,7 @@
 set -u
 cd "$(dirname "$0")/.." || exit 1
 TAG=${TAG:-r04e}
-O=gpurun_out/$TAG
+O=bench_out/$TAG
 mkdir -p $O
 step() {  # name, timeout, command...
   local name=$1 t=$2; shift 2

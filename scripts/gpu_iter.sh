@@ -3,7 +3,7 @@
 # bench.  TESTS=0 skips the tests; SWEEP="variant ..." (kernel_sweep.py specs); WORKLOADS for sweeps.
 set -u
 cd "$(dirname "$0")/.." || exit 1
-O=gpurun_out/${TAG:-iter}
+O=bench_out/${TAG:-iter}
 mkdir -p $O
 if [ "${TESTS:-1}" = "1" ]; then
   timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread -p no:cacheprovider \
@@ -19,6 +19,6 @@ for w in ${WORKLOADS:-c2}; do
   fi
 done
 for w in ${BENCH:-}; do
-  timeout -k 10 400 python bench.py --workload $w ${BENCH_ARGS:---steps 40 --cpu-seconds 20} > $O/bench_$w.json 2> $O/bench_$w.err || { tail -20 $O/bench_$w.err; exit 1; }
+  timeout -k 10 400 python bench.py --full --workload $w ${BENCH_ARGS:---steps 40 --cpu-seconds 20} > $O/bench_$w.json 2> $O/bench_$w.err || { tail -20 $O/bench_$w.err; exit 1; }
   python scripts/bench_summary.py $O/bench_$w.json 2>/dev/null || head -c 600 $O/bench_$w.json
 done

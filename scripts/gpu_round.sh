@@ -1,11 +1,11 @@
 #!/bin/bash
 # Round evidence in one GPU call: parity tests, smoke, then per workload a bench line (with the
-# CPU baseline and parity replay) and a rocprofv3 kernel-trace profile.  Output: gpurun_out/$TAG/.
+# CPU baseline and parity replay) and a rocprofv3 kernel-trace profile.  Output: bench_out/$TAG/.
 # Stops at the first step that faults, aborts or times out.
 set -u
 cd "$(dirname "$0")/.." || exit 1
 TAG=${TAG:-r02}
-O=gpurun_out/$TAG
+O=bench_out/$TAG
 mkdir -p $O
 step() {  # name, timeout, command...
   local name=$1 t=$2; shift 2
@@ -23,7 +23,7 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
 fi
 for w in ${WORKLOADS:-c2 c3 c4}; do
-  step bench_$w 600 python bench.py --workload $w ${BENCH_ARGS:-} > $O/bench_$w.json 2> $O/bench_$w.err
+  step bench_$w 600 python bench.py --full --workload $w ${BENCH_ARGS:-} > $O/bench_$w.json 2> $O/bench_$w.err
   cat $O/bench_$w.json >&2
   if [ "${PROFILE:-1}" = "1" ]; then
     WORKLOAD=$w OUT=$O/prof_$w step prof_$w 660 bash scripts/gpu_profile.sh

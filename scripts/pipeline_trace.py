@@ -6,7 +6,7 @@ For the last N batches: the epilogue-to-epilogue interval, each queue's busy sha
 mean duration, and per batch the span of stage A (k_sample start .. k_edge_fill end), of stage B
 (delta check start .. epilogue end) and the idle time inside each stage's chain.
 
-    python3 scripts/pipeline_trace.py gpurun_out/tl/.../run_kernel_trace.csv [--last 80]
+    python3 scripts/pipeline_trace.py bench_out/tl/.../run_kernel_trace.csv [--last 80]
 """
 import argparse
 import csv

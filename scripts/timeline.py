@@ -5,7 +5,7 @@ Splits the trace into batches at each k_epilogue, then reports, over the steady-
 the epilogue-to-epilogue interval, each queue's busy time, the union busy time, the idle gaps
 between consecutive kernels on each queue, and the kernel sequence of one median batch.
 
-    python3 scripts/timeline.py gpurun_out/prof/run_kernel_trace.csv [--skip 10] [--show 1]
+    python3 scripts/timeline.py bench_out/prof/run_kernel_trace.csv [--skip 10] [--show 1]
 """
 import argparse
 import csv

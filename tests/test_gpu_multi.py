@@ -32,7 +32,7 @@ def test_multi_rank_bench_parity(engine, world, workload, extra):
     txns, history = ("1000", "200000") if world == 2 else ("500", "50000")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", str(world), "--workload", workload, "--steps", "8", "--warmup", "2", "--txns", txns,
+           "--gpus", str(world), "--full", "--workload", workload, "--steps", "8", "--warmup", "2", "--txns", txns,
            "--history", history, "--h2d-steps", "0", "--total-steps", "0", "--breakdown-steps", "0",
            "--profile-steps", "4", "--sync-steps", "4", "--roof-steps", "0", "--backend", "gloo",
            "--cpu-seconds", "20"] + extra
@@ -279,7 +279,8 @@ def test_rccl_leg_one_rank(engine, workload):
     the restatement fed the same routing, the device combine against host-built bytes."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "1", "--dist", "--backend", "nccl", "--workload", workload, "--steps", "12", "--warmup", "2",
+           "--gpus", "1", "--full", "--dist", "--backend", "nccl", "--workload", workload, "--steps", "12",
+           "--warmup", "2",
            "--txns", "2000", "--history", "300000", "--h2d-steps", "0", "--total-steps", "4",
            "--breakdown-steps", "2", "--profile-steps", "4", "--sync-steps", "4", "--hold-steps", "2",
            "--roof-steps", "8", "--too-old-frac", "0.05", "--cpu-seconds", "30"]
