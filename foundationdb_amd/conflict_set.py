@@ -34,6 +34,9 @@ FDBCS_E_STATE = -5
 FDBCS_E_NODEVICE = -6
 FDBCS_E_TIMEOUT = -7
 
+# dump_history(floor=NO_FLOOR): versions as stored, no clamp below the oldest version
+NO_FLOOR = -(1 << 63)
+
 TransactionConflict = 0
 TransactionTooOld = 1
 TransactionCommitted = 2
@@ -113,6 +116,11 @@ SIGNATURES = {
     "fdbcs_get_oldest_version": (ctypes.c_int, [_VP, ctypes.POINTER(_I64)]),
     "fdbcs_history_size": (ctypes.c_int, [_VP, ctypes.POINTER(_I64)]),
     "fdbcs_load_history": (ctypes.c_int, [_VP, _I64, _VP, _VP, _VP, _I64]),
+    "fdbcs_history_export": (ctypes.c_int, [_VP, _VP, _I32, _VP, _I32, _I64, ctypes.POINTER(_I64),
+                                            ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+    "fdbcs_history_export_read": (ctypes.c_int, [_VP, _VP, _I64, _VP, _VP, _I64]),
+    "fdbcs_history_export_timing": (ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_double),
+                                                   ctypes.POINTER(ctypes.c_double)]),
     "fdbcs_get_stats": (ctypes.c_int, [_VP, ctypes.POINTER(Stats)]),
     "fdbcs_reset_stats": (ctypes.c_int, [_VP]),
     "fdbcs_set_gc_interval": (ctypes.c_int, [_VP, _I32]),
@@ -310,6 +318,45 @@ class ConflictSet:
             load_library().fdbcs_load_history(self._h, len(vv), _p(kb), _p(ko), _p(vv), header_version),
             "loadHistory",
         )
+
+    def export_history(self, lo: Optional[bytes] = None, hi: Optional[bytes] = None,
+                       floor: Optional[int] = None) -> Tuple[int, int, int]:
+        """fdbcs_history_export: run the export on the device and leave the result there; returns
+        (boundaries, key bytes, header version).  read_export() fetches it."""
+        L = load_library()
+        if floor is None:
+            floor = self.oldest_version
+        kl = np.frombuffer(lo if lo is not None else b"", np.uint8)
+        kh = np.frombuffer(hi if hi is not None else b"", np.uint8)
+        n, nb, hdr = _I64(), _I64(), _I64()
+        _check(L.fdbcs_history_export(self._h, _p(kl), len(kl) if lo is not None else -1, _p(kh),
+                                      len(kh) if hi is not None else -1, floor, ctypes.byref(n), ctypes.byref(nb),
+                                      ctypes.byref(hdr)), "historyExport")
+        return n.value, nb.value, hdr.value
+
+    def read_export(self, n: int, key_bytes: int):
+        """fdbcs_history_export_read into fresh arrays of the sizes export_history returned."""
+        kb = np.empty(key_bytes, np.uint8)
+        ko = np.empty(n + 1, np.int64)
+        vv = np.empty(n, np.int64)
+        _check(load_library().fdbcs_history_export_read(self._h, _p(kb), key_bytes, _p(ko), _p(vv), n),
+               "historyExportRead")
+        return kb, ko, vv
+
+    def export_timing(self) -> Tuple[float, float]:
+        """Milliseconds of the last export's kernels (device) and of the last read's copies (host)."""
+        a, b = ctypes.c_double(), ctypes.c_double()
+        _check(load_library().fdbcs_history_export_timing(self._h, ctypes.byref(a), ctypes.byref(b)), "exportTiming")
+        return a.value, b.value
+
+    def dump_history(self, lo: Optional[bytes] = None, hi: Optional[bytes] = None, floor: Optional[int] = None):
+        """The canonical history over [lo, hi): (key_bytes uint8[], key_offsets int64[n+1], versions
+        int64[n], header_version), the keys where the version a read sees changes, with versions
+        below `floor` (default: the oldest version; NO_FLOOR: none) read as floor - 1.  The tuple
+        unpacks into load_history(*...)."""
+        n, nb, hdr = self.export_history(lo, hi, floor)
+        kb, ko, vv = self.read_export(n, nb)
+        return kb, ko, vv, hdr
 
     def stats(self) -> dict:
         s = Stats()

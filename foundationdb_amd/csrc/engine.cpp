@@ -404,6 +404,14 @@ struct fdbcs_conflict_set {
     hipStream_t pending_ys = nullptr;  // the stream of pending_y
     fdbcs_batch* pending_batch = nullptr;
     std::unordered_set<fdbcs_batch*> live;  // batches not yet destroyed (detached if the set goes first)
+    // fdbcs_history_export: scratch (per delta boundary), the bounds' tails, scan granules + export
+    // words, and the result arrays; all allocated by the first export.  x_valid: a result is pending
+    // and the set has not changed since (detect, load, clear and another export end it).
+    DBuf x_pos, x_val, x_btail, x_state, x_ver, x_off, x_bytes;
+    bool x_valid = false;
+    int64_t x_n = 0, x_nbytes = 0;
+    hipEvent_t x_ev0 = nullptr, x_ev1 = nullptr;  // around the export's kernels
+    double x_ms_kernels = 0, x_ms_d2h = 0;        // of the last export / read (fdbcs_history_export_timing)
 };
 
 // Host/device staging of one batch.  Batches are short-lived (one per commit batch, as the
@@ -1382,6 +1390,10 @@ void fdbcs_destroy_conflict_set(fdbcs_conflict_set* cs) {
     cs->trace_buf.release();
     cs->hold.release();
     cs->hedge.release();
+    for (DBuf* x : {&cs->x_pos, &cs->x_val, &cs->x_btail, &cs->x_state, &cs->x_ver, &cs->x_off, &cs->x_bytes})
+        x->release();
+    if (cs->x_ev0) (void)hipEventDestroy(cs->x_ev0);
+    if (cs->x_ev1) (void)hipEventDestroy(cs->x_ev1);
     for (BatchSlot* sl : cs->pool) release_slot(sl);
     cs->pool.clear();
     // batches that outlive their set (e.g. garbage-collection order in a binding) keep their own
@@ -1409,6 +1421,7 @@ int fdbcs_clear_conflict_set(fdbcs_conflict_set* cs, int64_t version) {
     HIPOK(hipSetDevice(cs->device));
     if (int rc = flush_pending(cs)) return rc;
     if (int rc = sync_all(cs)) return rc;
+    cs->x_valid = false;
     HIPOK(hipMemsetAsync(cs->scal.p, 0, sizeof(Scalars), cs->stream));
     HIPOK(hipStreamSynchronize(cs->stream));
     cs->header_version = version;
@@ -1479,6 +1492,7 @@ int fdbcs_load_history(fdbcs_conflict_set* cs, int64_t n, const uint8_t* key_byt
     if (!cs || n < 0 || (n > 0 && (!key_bytes || !key_offsets || !versions))) return FDBCS_E_INVALID;
     HIPOK(hipSetDevice(cs->device));
     if (int rc = sync_all(cs)) return rc;
+    cs->x_valid = false;
     std::vector<ulonglong2> k(n);
     std::vector<uint2> lt(n);
     std::vector<uint8_t> tail;
@@ -1531,6 +1545,106 @@ int fdbcs_load_history(fdbcs_conflict_set* cs, int64_t n, const uint8_t* key_byt
     cs->n_ub = n;
     cs->nd_ub = 0;
     cs->tail_ub = (int64_t)tail.size();
+    return FDBCS_OK;
+}
+
+int fdbcs_history_export(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key,
+                         int32_t hi_len, int64_t floor_version, int64_t* n_out, int64_t* key_bytes_out,
+                         int64_t* header_version_out) {
+    if (!cs || !n_out || !key_bytes_out || !header_version_out) return FDBCS_E_INVALID;
+    if ((lo_len > 0 && !lo_key) || (hi_len > 0 && !hi_key)) return FDBCS_E_INVALID;
+    if (lo_len >= 0 && hi_len >= 0 && cmp_bytes(lo_key, lo_len, hi_key, hi_len) > 0) return FDBCS_E_INVALID;
+    if (cs->inflight) return FDBCS_E_STATE;
+    HIPOK(hipSetDevice(cs->device));
+    if (int rc = sync_all(cs)) return rc;
+    cs->x_valid = false;
+    Scalars sc;
+    HIPOK(hipMemcpy(&sc, cs->scal.p, sizeof(sc), hipMemcpyDeviceToHost));
+    ExportArgs a{};
+    a.nb = sc.n;
+    a.nd = sc.ndb[cs->dcur];
+    const int64_t total = a.nb + a.nd;
+    // the byte scan's exact range (kernels.hip, history export): refuse rather than wrap
+    if (total >= ((int64_t)1 << 29) || 16 * total + sc.tail_used >= ((int64_t)1 << 35)) return FDBCS_E_NOMEM;
+    a.base = hist_of(cs, cs->cur);
+    a.delta = delta_of(cs, cs->dcur);
+    a.htail = (const uint8_t*)cs->htail[cs->tcur].p;
+    a.hdr = cs->header_version;
+    a.floor = floor_version;
+    // lo / hi as RouteArgs::lo / hi: DKey + tail bytes in a small device buffer
+    std::vector<uint8_t> bt;
+    auto norm = [&](const uint8_t* p, int32_t len, DKey& k) {
+        dkey_prefix(p, (uint32_t)len, &k.hi, &k.lo);
+        k.len = (uint32_t)len;
+        k.tail = (uint32_t)bt.size();
+        if (len > 16) bt.insert(bt.end(), p + 16, p + len);
+    };
+    a.has_lo = lo_len >= 0;
+    a.has_hi = hi_len >= 0;
+    if (a.has_lo) norm(lo_key, lo_len, a.lo);
+    if (a.has_hi) norm(hi_key, hi_len, a.hi);
+    const int64_t tiles = export_tiles(total);
+    int rc;
+    if ((rc = cs->x_btail.ensure(bt.size() + kTailSlack))) return rc;
+    if ((rc = cs->x_pos.ensure(8 * (size_t)(a.nd + 1)))) return rc;
+    if ((rc = cs->x_val.ensure(8 * (size_t)(a.nd + 1)))) return rc;
+    if ((rc = cs->x_state.ensure(8 * (size_t)(kXwWords + 4 * tiles)))) return rc;
+    if ((rc = cs->x_ver.ensure(8 * (size_t)(total + 1)))) return rc;
+    if ((rc = cs->x_off.ensure(8 * (size_t)(total + 1)))) return rc;
+    if ((rc = cs->x_bytes.ensure((size_t)(16 * total + sc.tail_used + 64)))) return rc;
+    if (!cs->x_ev0) HIPOK(hipEventCreate(&cs->x_ev0));
+    if (!cs->x_ev1) HIPOK(hipEventCreate(&cs->x_ev1));
+    a.btail = (const uint8_t*)cs->x_btail.p;
+    a.d_pos = (int64_t*)cs->x_pos.p;
+    a.d_val = (int64_t*)cs->x_val.p;
+    a.words = (int64_t*)cs->x_state.p;
+    a.tile_tb = a.words + kXwWords + 3 * tiles;  // after the scan's granules
+    a.versions = (int64_t*)cs->x_ver.p;
+    a.offsets = (int64_t*)cs->x_off.p;
+    a.bytes = (uint8_t*)cs->x_bytes.p;
+    a.bytes_cap = (int64_t)cs->x_bytes.cap;
+    hipStream_t s = cs->stream;
+    if (!bt.empty()) HIPOK(hipMemcpyAsync(cs->x_btail.p, bt.data(), bt.size(), hipMemcpyHostToDevice, s));
+    HIPOK(hipMemsetAsync(cs->x_state.p, 0, 8 * (size_t)(kXwWords + 3 * tiles), s));
+    HIPOK(hipEventRecord(cs->x_ev0, s));
+    launch_export(s, a, levels_of(cs, cs->cur), (uint64_t*)cs->x_state.p + kXwWords, sc.tail_used > 0 ? 2 : 1);
+    HIPOK(take_launch_error());
+    HIPOK(hipEventRecord(cs->x_ev1, s));
+    int64_t words[kXwWords];
+    HIPOK(hipMemcpyAsync(words, cs->x_state.p, sizeof(words), hipMemcpyDeviceToHost, s));
+    HIPOK(hipStreamSynchronize(s));
+    cs->x_ms_kernels = ev_ms(cs->x_ev0, cs->x_ev1);
+    cs->x_ms_d2h = 0;
+    if (((const int32_t*)&words[kXwScan])[1]) return FDBCS_E_DEVICE;  // look-back bound, positions out of order, key buffer
+    cs->x_n = words[kXwN];
+    cs->x_nbytes = words[kXwBytes];
+    cs->x_valid = true;
+    *n_out = cs->x_n;
+    *key_bytes_out = cs->x_nbytes;
+    *header_version_out = words[kXwHeader];
+    return FDBCS_OK;
+}
+
+int fdbcs_history_export_read(fdbcs_conflict_set* cs, uint8_t* key_bytes, int64_t key_bytes_cap, int64_t* key_offsets,
+                              int64_t* versions, int64_t cap) {
+    if (!cs || key_bytes_cap < 0 || cap < 0 || !key_offsets) return FDBCS_E_INVALID;
+    if (!cs->x_valid) return FDBCS_E_STATE;
+    if (cap < cs->x_n || key_bytes_cap < cs->x_nbytes) return FDBCS_E_NOMEM;
+    if ((cs->x_n && !versions) || (cs->x_nbytes && !key_bytes)) return FDBCS_E_INVALID;
+    HIPOK(hipSetDevice(cs->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    if (cs->x_n) HIPOK(hipMemcpy(versions, cs->x_ver.p, 8 * (size_t)cs->x_n, hipMemcpyDeviceToHost));
+    HIPOK(hipMemcpy(key_offsets, cs->x_off.p, 8 * (size_t)(cs->x_n + 1), hipMemcpyDeviceToHost));
+    if (cs->x_nbytes) HIPOK(hipMemcpy(key_bytes, cs->x_bytes.p, (size_t)cs->x_nbytes, hipMemcpyDeviceToHost));
+    cs->x_ms_d2h = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    cs->x_valid = false;
+    return FDBCS_OK;
+}
+
+int fdbcs_history_export_timing(fdbcs_conflict_set* cs, double* ms_kernels, double* ms_d2h) {
+    if (!cs || !ms_kernels || !ms_d2h) return FDBCS_E_INVALID;
+    *ms_kernels = cs->x_ms_kernels;
+    *ms_d2h = cs->x_ms_d2h;
     return FDBCS_OK;
 }
 
@@ -2706,6 +2820,7 @@ int fdbcs_batch_detect_async(fdbcs_batch* b, int64_t now, int64_t new_oldest_ver
     }
     cs->tail_ub += tail_add;
     cs->inflight++;
+    cs->x_valid = false;
     b->state = 2;
     if (cs->htrace)
         cs->htr[0].push_back({b->seq, 'D',

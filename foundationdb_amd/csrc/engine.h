@@ -464,4 +464,33 @@ void launch_epilogue(hipStream_t s, const BatchDev& b, const Work& w, const MaxL
 // Cold-start samples of a sort over E endpoints in nb buckets (k_sample; ranks re-zeroed by the epilogue).
 int sort_cold_samples(int64_t E, int nb);
 
+// ---- canonical history export (fdbcs_history_export): reads both tiers, writes only the arrays below.
+// Device words of one export (zeroed before its launches).
+enum ExportWord { kXwLo, kXwHi, kXwHeader, kXwN, kXwBytes, kXwScan /* int counter, int error */, kXwWords = 8 };
+struct ExportArgs {
+    Hist base, delta;
+    const uint8_t* htail;
+    int64_t nb, nd;        // exact tier sizes (the set is idle)
+    int64_t hdr;           // the set's header version
+    int64_t floor;         // versions below it read floor - 1 (kHole: no clamp)
+    int32_t has_lo, has_hi;  // export (lo, hi) of the merged stream, header H(lo)
+    DKey lo, hi;
+    const uint8_t* btail;  // their tails
+    // scratch, one entry per delta boundary j: its position in the merged stream of both tiers' boundaries
+    // (j + base boundaries below it: on equal keys the delta's comes first) and the version at its key
+    int64_t* d_pos;
+    int64_t* d_val;
+    int64_t* words;        // [kXwWords] ExportWord
+    int64_t* tile_tb;      // [export_tiles] delta boundaries below each scan tile's first element
+    // result: the layout fdbcs_load_history takes
+    int64_t* versions;     // [n]
+    int64_t* offsets;      // [n + 1]
+    uint8_t* bytes;
+    int64_t bytes_cap;     // bytes the key buffer holds
+};
+// Tiles (scan granule triples) of an export over nb + nd boundaries.
+int64_t export_tiles(int64_t n);
+// mode: the compaction search's (1: lane_lower_bound, 2: the long-key form).
+void launch_export(hipStream_t s, const ExportArgs& a, const MaxLevels& basem, uint64_t* granules, int mode);
+
 }  // namespace fdbcs

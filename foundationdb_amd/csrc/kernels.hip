@@ -4323,4 +4323,276 @@ void launch_epilogue(hipStream_t s, const BatchDev& b, const Work& w, const MaxL
                    (const int64_t*)nullptr, ep);
 }
 
+// ------------------------------------------------------------------ history export
+//
+// The canonical description of H_f(k) = the version a read of k sees (delta entry unless kHole, else
+// base entry, else the header), clamped to floor - 1 below the floor, over (lo, hi): the keys where
+// it changes, with their new values, in the layout fdbcs_load_history takes.  Read-only: nothing of
+// the set, its levels, index, directories, Scalars or batch workspaces is written.
+//
+// Both tiers' boundaries in key order form one merged stream (on equal keys the delta's first).  H at
+// every stream element is known from the element and the delta boundary covering it, and an element
+// is kept when its clamped value differs from its predecessor's: base boundaries hidden under a
+// written delta segment, the second of two equal keys and runs the floor made equal all repeat their
+// predecessor's value, so no case is special.
+//   k_export_search  one lane per delta boundary j: lower bound lb in the base (the compaction's
+//                    search, without its side effects) -> stream position j + lb, and H(d_j)
+//   k_export_bounds  stream positions of lo and hi by plain binary searches, and the header H_f(lo)
+//   k_export_tile_starts  per scan tile, the delta boundaries below its first element (one thread each)
+//   k_export_scan    per 1024-element tile of the stream: the delta positions the tile can meet are
+//                    staged in LDS (consecutive elements meet consecutive delta boundaries), every
+//                    element is resolved to its source and clamped value there, then flagged and
+//                    scanned (scan.h look-back) and the kept ones written.
+// Key bytes are scanned as three 32-bit components, kept count c, bytes mod 2^32 a, and sum of
+// (len >> 3) b: a prefix P lies in [8 b, 8 b + 7 c] and is congruent to a, which determines it while
+// 7 c < 2^32 and b < 2^32: exact 64-bit offsets below 2^29 boundaries and 32 GiB of key bytes (the
+// host refuses an export that could pass either).
+
+__device__ __forceinline__ int64_t export_prefix64(uint32_t a, uint32_t b) {
+    const uint64_t lower = 8ull * b;
+    return (int64_t)(lower + (uint32_t)(a - (uint32_t)lower));
+}
+
+__device__ __forceinline__ int64_t export_clamp(int64_t v, int64_t floor) {
+    return (floor == kHole || v >= floor) ? v : floor - 1;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(kBlock) void k_export_search(Hist base, MaxLevels basem, Hist delta,
+                                                          const uint8_t* htail, int64_t nb, int64_t nd, int64_t hdr,
+                                                          int64_t* d_pos, int64_t* d_val) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= nd) return;
+    const ulonglong2 k = delta.key[j];
+    const uint2 lt = delta.lt[j];
+    DKey q;
+    q.hi = k.x;
+    q.lo = k.y;
+    q.len = lt.x;
+    q.tail = 0;  // the query's tail arena below starts at its own tail
+    bool exact = false;
+    const uint8_t* qtail = hist_tail(htail, lt.y);
+    int64_t lb;
+    if constexpr (MODE == 1) {
+        lb = lane_lower_bound(base, basem, nb, q, htail, qtail, exact);
+    } else {
+        QTail qt;
+        load_qtail(qt, q, qtail);
+        lb = lane_lower_bound_long(base, basem, nb, q, qt, htail, qtail, exact);
+    }
+    const int64_t dv = delta.ver[j];
+    d_pos[j] = j + lb;
+    // a hole takes the base value at its key: the base boundary there, or the one covering it
+    d_val[j] = dv != kHole ? dv : exact ? base.ver[lb] : lb > 0 ? base.ver[lb - 1] : hdr;
+}
+
+// Boundaries of a tier below q (upper: or equal to it).
+__device__ __forceinline__ int64_t export_bound(const Hist& h, int64_t n, const uint8_t* htail, const DKey& q,
+                                                const uint8_t* qtail, bool upper) {
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        const int c = hist_cmp(h, mid, htail, q, qtail);
+        if (c < 0 || (upper && c == 0))
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(64) void k_export_bounds(ExportArgs a) {
+    __shared__ int64_t r[4];  // boundaries <= lo in base, delta; boundaries < hi in base, delta
+    const int t = threadIdx.x;
+    if (t < 4) {
+        const bool is_hi = t >= 2, is_delta = t & 1;
+        const int64_t n = is_delta ? a.nd : a.nb;
+        if (is_hi ? a.has_hi : a.has_lo)
+            r[t] = export_bound(is_delta ? a.delta : a.base, n, a.htail, is_hi ? a.hi : a.lo, a.btail, !is_hi);
+        else
+            r[t] = is_hi ? n : 0;
+    }
+    __syncthreads();
+    if (t != 0) return;
+    int64_t h = a.hdr;
+    if (r[0] > 0) h = a.base.ver[r[0] - 1];
+    if (r[1] > 0) {
+        const int64_t dv = a.delta.ver[r[1] - 1];
+        if (dv != kHole) h = dv;
+    }
+    const int64_t m_lo = r[0] + r[1], m_hi = r[2] + r[3];
+    a.words[kXwLo] = m_lo;
+    a.words[kXwHi] = m_hi > m_lo ? m_hi : m_lo;
+    a.words[kXwHeader] = export_clamp(h, a.floor);
+}
+
+// Write the n bytes of a key, given as little-endian 8-byte words get(0 .. nw - 1) in key order, to
+// d (any alignment): bytes up to d's next 8-byte line, whole words, then the rest.
+template <class G>
+__device__ __forceinline__ void export_put_key(uint8_t* d, uint32_t n, uint32_t nw, const G& get) {
+    uint32_t head = (uint32_t)((8u - ((uintptr_t)d & 7u)) & 7u);
+    if (head > n) head = n;
+    uint64_t cur = nw ? get(0u) : 0ull;
+    for (uint32_t b = 0; b < head; b++) d[b] = (uint8_t)(cur >> (8u * b));
+    const uint32_t sh = 8u * head, nfull = (n - head) >> 3;
+    uint64_t* dw = (uint64_t*)(d + head);
+    for (uint32_t q = 0; q < nfull; q++) {
+        const uint64_t next = q + 1u < nw ? get(q + 1u) : 0ull;
+        dw[q] = sh ? (cur >> sh) | (next << (64u - sh)) : cur;
+        cur = next;
+    }
+    for (uint32_t b = head + 8u * nfull; b < n; b++) d[b] = (uint8_t)(get(b >> 3) >> (8u * (b & 7u)));
+}
+
+// Per scan tile: the delta boundaries below the first stream element the tile resolves (its
+// predecessor; tile 0: its first element).  One thread per tile, so the binary searches of all tiles
+// run side by side instead of one per workgroup at the head of its tile.
+__global__ __launch_bounds__(kBlock) void k_export_tile_starts(ExportArgs a) {
+    const int64_t tile = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t m_lo = a.words[kXwLo], n = a.words[kXwHi] - m_lo;
+    const int64_t ntiles = n > 0 ? (n + kScanTile - 1) / kScanTile : 1;
+    if (tile >= ntiles) return;
+    const int64_t mfirst = m_lo + tile * kScanTile - (tile > 0 ? 1 : 0);
+    int64_t tb = 0, th = a.nd;
+    while (tb < th) {
+        const int64_t mid = tb + (th - tb) / 2;
+        if (a.d_pos[mid] < mfirst)
+            tb = mid + 1;
+        else
+            th = mid;
+    }
+    a.tile_tb[tile] = tb;
+}
+
+constexpr int kExpWin = kScanTile + 2;  // delta boundaries a tile and its predecessor can meet, and one past
+
+struct ExportScan {
+    ExportArgs a;
+    const int64_t* s_val;  // LDS: clamped value of the tile's predecessor, then of its elements
+    const int64_t* s_src;  // LDS: source of each element: base boundary i, or ~j for delta boundary j
+    int64_t tile0;         // the tile's first element
+    int* err;              // the export's error word
+    __device__ bool keep(int e) const { return s_val[e + 1] != s_val[e]; }
+    __device__ void load(int64_t i, uint32_t (&v)[3]) const {
+        const int e = (int)(i - tile0);
+        uint32_t len = 0;
+        const bool kp = keep(e);
+        if (kp) {
+            const int64_t src = s_src[e];
+            len = src >= 0 ? a.base.lt[src].x : a.delta.lt[~src].x;
+        }
+        v[0] = kp ? 1u : 0u;
+        v[1] = len;
+        v[2] = len >> 3;
+    }
+    __device__ void store(int64_t i, const uint32_t (&ex)[3]) const {
+        const int e = (int)(i - tile0);
+        if (!keep(e)) return;
+        const int64_t o = ex[0], P = export_prefix64(ex[1], ex[2]);
+        const int64_t src = s_src[e];
+        const Hist& h = src >= 0 ? a.base : a.delta;
+        const int64_t p = src >= 0 ? src : ~src;
+        const ulonglong2 k = h.key[p];
+        const uint2 lt = h.lt[p];
+        a.versions[o] = s_val[e + 1];
+        a.offsets[o] = P;
+        if (P + (int64_t)lt.x > a.bytes_cap) {  // never past the result buffer (the host sized it for every key)
+            atomicOr(err, 8);
+            return;
+        }
+        // the prefix words are big-endian: swapped back, the key's first byte is the lowest
+        const uint64_t w0 = __builtin_bswap64(k.x), w1 = __builtin_bswap64(k.y);
+        const uint64_t* tw = (const uint64_t*)hist_tail(a.htail, lt.x > 16u ? lt.y : 0u);
+        export_put_key(a.bytes + P, lt.x, (lt.x + 7u) >> 3,
+                       [&](uint32_t q) { return q == 0u ? w0 : q == 1u ? w1 : tw[q - 2u]; });
+    }
+    __device__ void finish(const uint32_t (&tot)[3]) const {
+        const int64_t P = export_prefix64(tot[1], tot[2]);
+        a.words[kXwN] = tot[0];
+        a.words[kXwBytes] = P;
+        a.offsets[tot[0]] = P;
+    }
+};
+
+__global__ __launch_bounds__(kScanThreads) void k_export_scan(ExportArgs a, ScanState st) {
+    __shared__ uint32_t sv[3][kScanPad];
+    __shared__ uint32_t swave[3][kScanThreads / 64];
+    __shared__ uint32_t sbase[3];
+    __shared__ int s_tile;
+    __shared__ int64_t s_pos[kExpWin];
+    __shared__ int64_t s_val[kScanTile + 1];
+    __shared__ int64_t s_src[kScanTile];
+    const int64_t m_lo = a.words[kXwLo], n = a.words[kXwHi] - m_lo;
+    if (threadIdx.x == 0) s_tile = atomicAdd(st.counter, 1);
+    __syncthreads();
+    const int tile = s_tile;
+    const int64_t ntiles = n > 0 ? (n + kScanTile - 1) / kScanTile : 1;
+    if (tile >= ntiles) return;
+    const int64_t tile0 = (int64_t)tile * kScanTile;
+    // stream elements resolved here: the tile's, and before them its predecessor (tile 0: the header)
+    const int pre = tile > 0 ? 1 : 0;
+    const int64_t mfirst = m_lo + tile0 - pre;
+    int64_t rest = n - tile0;
+    const int cnt = (int)(rest < kScanTile ? rest : kScanTile) + pre;
+    // delta boundaries below the first element (k_export_tile_starts); the next kExpWin positions cover
+    // every element's search: positions ascend strictly, so window entry q lies at mfirst + q or later
+    const int64_t tb = a.tile_tb[tile];
+    for (int q = threadIdx.x; q < kExpWin; q += kScanThreads) s_pos[q] = tb + q < a.nd ? a.d_pos[tb + q] : LLONG_MAX;
+    __syncthreads();
+    for (int k = threadIdx.x; k < cnt; k += kScanThreads) {
+        const int64_t m = mfirst + k;
+        int l = 0, h = kExpWin;  // window entries at or below m
+        while (l < h) {
+            const int mid = (l + h) >> 1;
+            if (s_pos[mid] <= m)
+                l = mid + 1;
+            else
+                h = mid;
+        }
+        const int64_t t = tb + l;  // delta boundaries at or below element m: t - 1 covers it
+        int64_t v, src;
+        if (l > 0 && s_pos[l - 1] == m) {
+            src = ~(t - 1);
+            v = a.d_val[t - 1];
+        } else {
+            src = m - t;
+            if (src < 0 || src >= a.nb) {  // positions out of order: never index past the tier
+                atomicOr(st.error, 4);
+                src = a.nb > 0 ? 0 : ~(int64_t)0;
+            }
+            const int64_t dv = t > 0 ? a.delta.ver[t - 1] : kHole;
+            v = dv != kHole ? dv : src >= 0 ? a.base.ver[src] : a.hdr;
+        }
+        const int slot = k + 1 - pre;
+        s_val[slot] = export_clamp(v, a.floor);
+        if (slot > 0) s_src[slot - 1] = src;
+    }
+    if (tile == 0 && threadIdx.x == 0) s_val[0] = a.words[kXwHeader];
+    __syncthreads();
+    const ExportScan f{a, s_val, s_src, tile0, st.error};
+    scan_tile<3>(f, n, tile, ntiles, st, sv, swave, sbase);
+}
+
+int64_t export_tiles(int64_t n) { return n > 0 ? (n + kScanTile - 1) / kScanTile : 1; }
+
+void launch_export(hipStream_t s, const ExportArgs& a, const MaxLevels& basem, uint64_t* granules, int mode) {
+    if (a.nd > 0) {
+        const dim3 grid((unsigned)((a.nd + kBlock - 1) / kBlock));
+        if (mode == 1)
+            fdb_launch(k_export_search<1>, grid, dim3(kBlock), 0, s, a.base, basem, a.delta, a.htail, a.nb, a.nd, a.hdr,
+                       a.d_pos, a.d_val);
+        else
+            fdb_launch(k_export_search<2>, grid, dim3(kBlock), 0, s, a.base, basem, a.delta, a.htail, a.nb, a.nd, a.hdr,
+                       a.d_pos, a.d_val);
+    }
+    fdb_launch(k_export_bounds, dim3(1), dim3(64), 0, s, a);
+    const int64_t tiles = export_tiles(a.nb + a.nd);
+    fdb_launch(k_export_tile_starts, dim3((unsigned)((tiles + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, a);
+    ScanState st;
+    st.granules = granules;
+    st.counter = (int*)&a.words[kXwScan];
+    st.error = st.counter + 1;
+    fdb_launch(k_export_scan, dim3((unsigned)tiles), dim3(kScanThreads), 0, s, a, st);
+}
+
 }  // namespace fdbcs

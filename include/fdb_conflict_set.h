@@ -158,6 +158,30 @@ int fdbcs_history_size(fdbcs_conflict_set* cs, int64_t* out);
  * boundary read `header_version`.  Used by benchmarks to prefill an MVCC window. */
 int fdbcs_load_history(fdbcs_conflict_set* cs, int64_t n, const uint8_t* key_bytes,
                        const int64_t* key_offsets, const int64_t* versions, int64_t header_version);
+/* Canonical export of the history over [lo, hi), computed on the device; the set is not modified.
+ * No reference counterpart (the reference never serialises its skip list).
+ * With H(k) the version a read of key k sees and H_f(k) = H(k) if H(k) >= floor_version, else
+ * floor_version - 1 (INT64_MIN: no clamp; with the oldest version as floor the result does not
+ * depend on whether or when GC ran): *header_version_out = H_f(lo) (no lower bound: the clamped
+ * header of the set), and the boundaries are the keys lo < k < hi where H_f changes, ascending,
+ * each with its new value, adjacent equal values coalesced; keys are the original bytes.  The
+ * result stays in device buffers owned by the set (allocated by the first export) until it is read;
+ * *n_out and *key_bytes_out are the capacities fdbcs_history_export_read needs.  lo > hi is
+ * FDBCS_E_INVALID; with batches in flight FDBCS_E_STATE, and nothing is touched.
+ * Key-byte offsets are exact 64-bit values (the byte scan cannot wrap); a set of 2^29 boundaries or
+ * one whose keys could pass 32 GiB is refused with FDBCS_E_NOMEM. */
+int fdbcs_history_export(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, /* lo_len < 0: no lower bound */
+                         const uint8_t* hi_key, int32_t hi_len,                       /* hi_len < 0: no upper bound */
+                         int64_t floor_version, int64_t* n_out, int64_t* key_bytes_out,
+                         int64_t* header_version_out);
+/* Copy the pending export out, in the layout fdbcs_load_history takes (key_offsets [n+1], versions
+ * [n]), and release it.  FDBCS_E_NOMEM when a capacity is too small (the result stays available);
+ * FDBCS_E_STATE when no result is pending or the set changed since the export (a detect, a load,
+ * a clear; another export replaces the result). */
+int fdbcs_history_export_read(fdbcs_conflict_set* cs, uint8_t* key_bytes, int64_t key_bytes_cap,
+                              int64_t* key_offsets, int64_t* versions, int64_t cap);
+/* Diagnostics: device time of the last export's kernels and host time of the last read's copies (ms). */
+int fdbcs_history_export_timing(fdbcs_conflict_set* cs, double* ms_kernels, double* ms_d2h);
 int fdbcs_get_stats(fdbcs_conflict_set* cs, fdbcs_stats* out);
 int fdbcs_reset_stats(fdbcs_conflict_set* cs);
 /* Pre-size device capacity (history boundaries, history tail bytes, and the largest batch

@@ -6,7 +6,12 @@ read at set creation (directory slot budget, split check, stream layout, submitt
 compaction and GC cadence, and a sequence of batches whose snapshots straddle the oldest version; verdicts and
 conflicting-read reports must match oracle/skiplist_baseline.cpp batch by batch.
 
-    python3 scripts/stress_parity.py [seconds] [first_seed]
+    python3 scripts/stress_parity.py [seconds] [first_seed] [--state-every K]
+
+--state-every K (default off) also feeds the semantic oracle and compares the engine's exported
+history (ConflictSet.dump_history at floor = oldest version) with the canonical form of the oracle's
+step function every K batches: a wrong version or a lost boundary shows in the batch that made it,
+not when a later read happens to meet it.
 
 Exit status 1 and the failing seed on the first mismatch."""
 import os
@@ -21,6 +26,7 @@ sys.path.insert(0, ROOT)
 from foundationdb_amd import conflict_set as C  # noqa: E402
 from foundationdb_amd.packing import CommitTransaction, KeyRange, PackedBatch  # noqa: E402
 from oracle import oracle  # noqa: E402
+from tests.export_helpers import canon, split_dump  # noqa: E402
 from tests.helpers import EngineDriver  # noqa: E402
 
 KNOBS = {
@@ -32,7 +38,7 @@ KNOBS = {
 }
 
 
-def one(seed):
+def one(seed, state_every=0):
     rng = np.random.default_rng(seed)
     for k, vals in KNOBS.items():
         os.environ[k] = vals[int(rng.integers(0, len(vals)))]
@@ -68,6 +74,10 @@ def one(seed):
     o = oracle.SkipListBaseline()
     e.load_history(kb, ko, vers)
     o.load_history(kb, ko, vers)
+    so = None
+    if state_every:  # the skip-list restatement has no dump: the semantic oracle holds the state
+        so = oracle.OracleConflictSet()
+        so.load_history(kb, ko, vers)
     now, oldest = 1000, 0
     for i in range(int(rng.integers(3, 10))):
         now += int(rng.integers(1, 200))
@@ -91,18 +101,32 @@ def one(seed):
         co = {t: sorted(v) for t, v in co.items() if v}
         if ce != co:
             return f"conflicting reads batch {i}"
+        if so is not None:
+            so.detect(pb, now, oldest)
+            if (i + 1) % state_every == 0:
+                keys, hv = so.dump_history()
+                want = canon(keys, hv, 0, so.oldest_version)
+                got = split_dump(e.cs.dump_history())
+                if got != want:
+                    return f"exported state batch {i}: {len(got[1])} boundaries, oracle {len(want[1])}"
     e.cs.close()
     return None
 
 
 def main():
-    budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
-    seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+    args = sys.argv[1:]
+    state_every = 0
+    if "--state-every" in args:
+        k = args.index("--state-every")
+        state_every = int(args[k + 1])
+        del args[k:k + 2]
+    budget = float(args[0]) if len(args) > 0 else 120.0
+    seed = int(args[1]) if len(args) > 1 else 1
     oracle.build()
     t0 = time.time()
     n = 0
     while time.time() - t0 < budget:
-        err = one(seed)
+        err = one(seed, state_every)
         knobs = {k: os.environ[k] for k in KNOBS}
         if err:
             print(f"MISMATCH seed {seed} knobs {knobs}: {err}", flush=True)
