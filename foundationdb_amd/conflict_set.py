@@ -121,6 +121,11 @@ SIGNATURES = {
     "fdbcs_history_export_read": (ctypes.c_int, [_VP, _VP, _I64, _VP, _VP, _I64]),
     "fdbcs_history_export_timing": (ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_double),
                                                    ctypes.POINTER(ctypes.c_double)]),
+    "fdbcs_history_import": (ctypes.c_int, [_VP, _VP, _I32, _VP, _I32, _I64, _VP, _VP, _VP, _I64,
+                                            ctypes.POINTER(_I64)]),
+    "fdbcs_history_import_pending": (ctypes.c_int, [_VP, _VP, _VP, _I32, _VP, _I32, ctypes.POINTER(_I64)]),
+    "fdbcs_history_import_timing": (ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_double),
+                                                   ctypes.POINTER(ctypes.c_double)]),
     "fdbcs_get_stats": (ctypes.c_int, [_VP, ctypes.POINTER(Stats)]),
     "fdbcs_reset_stats": (ctypes.c_int, [_VP]),
     "fdbcs_set_gc_interval": (ctypes.c_int, [_VP, _I32]),
@@ -357,6 +362,42 @@ class ConflictSet:
         n, nb, hdr = self.export_history(lo, hi, floor)
         kb, ko, vv = self.read_export(n, nb)
         return kb, ko, vv, hdr
+
+    @staticmethod
+    def _bounds(lo: Optional[bytes], hi: Optional[bytes]):
+        kl = np.frombuffer(lo if lo is not None else b"", np.uint8)
+        kh = np.frombuffer(hi if hi is not None else b"", np.uint8)
+        return kl, (len(kl) if lo is not None else -1), kh, (len(kh) if hi is not None else -1)
+
+    def merge_history(self, key_bytes, key_offsets, versions, header_version: int = 0,
+                      lo: Optional[bytes] = None, hi: Optional[bytes] = None) -> int:
+        """fdbcs_history_import: fold an exported history (the arrays dump_history returns) into
+        this set over [lo, hi): every key there afterwards reads the greater of the version it read
+        before and the imported one.  Returns the history size afterwards.
+        dst.merge_history(*src.dump_history(lo, hi), lo=lo, hi=hi) hands [lo, hi) over."""
+        kb = np.ascontiguousarray(key_bytes, np.uint8)
+        ko = np.ascontiguousarray(key_offsets, np.int64)
+        vv = np.ascontiguousarray(versions, np.int64)
+        kl, ll, kh, hl = self._bounds(lo, hi)
+        out = _I64()
+        _check(load_library().fdbcs_history_import(self._h, _p(kl), ll, _p(kh), hl, len(vv), _p(kb), _p(ko), _p(vv),
+                                                   header_version, ctypes.byref(out)), "historyImport")
+        return out.value
+
+    def merge_pending_export(self, src: "ConflictSet", lo: Optional[bytes] = None, hi: Optional[bytes] = None) -> int:
+        """fdbcs_history_import_pending: the same import, reading the result of src.export_history()
+        from src's device buffers (same device; no host copy).  src's result stays readable."""
+        kl, ll, kh, hl = self._bounds(lo, hi)
+        out = _I64()
+        _check(load_library().fdbcs_history_import_pending(self._h, src._h, _p(kl), ll, _p(kh), hl, ctypes.byref(out)),
+               "historyImportPending")
+        return out.value
+
+    def import_timing(self) -> Tuple[float, float]:
+        """Milliseconds of the last import's kernels (device) and of the whole call (host)."""
+        a, b = ctypes.c_double(), ctypes.c_double()
+        _check(load_library().fdbcs_history_import_timing(self._h, ctypes.byref(a), ctypes.byref(b)), "importTiming")
+        return a.value, b.value
 
     def stats(self) -> dict:
         s = Stats()

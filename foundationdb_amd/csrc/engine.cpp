@@ -412,6 +412,13 @@ struct fdbcs_conflict_set {
     int64_t x_n = 0, x_nbytes = 0;
     hipEvent_t x_ev0 = nullptr, x_ev1 = nullptr;  // around the export's kernels
     double x_ms_kernels = 0, x_ms_d2h = 0;        // of the last export / read (fdbcs_history_export_timing)
+    int64_t x_hdr = 0;                            // the pending result's header version
+    // fdbcs_history_import: device copies of the imported arrays (host-array form), the bounds' bytes,
+    // the overlay stream (keys, lt, versions, tails), the merged stream (value, key, lt) and the import
+    // words + scan granules; all allocated by the first import and freed with the set.
+    DBuf i_bytes, i_off, i_ver, i_bnd, i_okey, i_olt, i_over, i_otail, i_mval, i_mkey, i_mlt, i_dblt, i_vblt, i_state;
+    hipEvent_t i_ev[6] = {};                      // around the import's three groups of kernels
+    double i_ms_kernels = 0, i_ms_host = 0;       // of the last import (fdbcs_history_import_timing)
 };
 
 // Host/device staging of one batch.  Batches are short-lived (one per commit batch, as the
@@ -1394,6 +1401,11 @@ void fdbcs_destroy_conflict_set(fdbcs_conflict_set* cs) {
         x->release();
     if (cs->x_ev0) (void)hipEventDestroy(cs->x_ev0);
     if (cs->x_ev1) (void)hipEventDestroy(cs->x_ev1);
+    for (DBuf* x : {&cs->i_bytes, &cs->i_off, &cs->i_ver, &cs->i_bnd, &cs->i_okey, &cs->i_olt, &cs->i_over, &cs->i_otail,
+                    &cs->i_mval, &cs->i_mkey, &cs->i_mlt, &cs->i_dblt, &cs->i_vblt, &cs->i_state})
+        x->release();
+    for (hipEvent_t e : cs->i_ev)
+        if (e) (void)hipEventDestroy(e);
     for (BatchSlot* sl : cs->pool) release_slot(sl);
     cs->pool.clear();
     // batches that outlive their set (e.g. garbage-collection order in a binding) keep their own
@@ -1618,6 +1630,7 @@ int fdbcs_history_export(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t 
     if (((const int32_t*)&words[kXwScan])[1]) return FDBCS_E_DEVICE;  // look-back bound, positions out of order, key buffer
     cs->x_n = words[kXwN];
     cs->x_nbytes = words[kXwBytes];
+    cs->x_hdr = words[kXwHeader];
     cs->x_valid = true;
     *n_out = cs->x_n;
     *key_bytes_out = cs->x_nbytes;
@@ -1645,6 +1658,200 @@ int fdbcs_history_export_timing(fdbcs_conflict_set* cs, double* ms_kernels, doub
     if (!cs || !ms_kernels || !ms_d2h) return FDBCS_E_INVALID;
     *ms_kernels = cs->x_ms_kernels;
     *ms_d2h = cs->x_ms_d2h;
+    return FDBCS_OK;
+}
+
+// The import proper, on device arrays (both entry points end here).  The set is idle, its streams
+// drained; d_bytes is 8-byte aligned with >= 16 readable bytes past nbytes.  The host does no
+// per-boundary work: it sizes buffers from n and nbytes, reads the import words back after the
+// validation and after the fold and, on success, switches to the base buffer and tail arena the
+// kernels filled.
+static int import_device(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key,
+                         int32_t hi_len, int64_t n, const uint8_t* d_bytes, int64_t nbytes, const int64_t* d_off,
+                         const int64_t* d_ver, int64_t ihdr, int64_t* boundaries_out) {
+    Scalars sc;
+    HIPOK(hipMemcpy(&sc, cs->scal.p, sizeof(sc), hipMemcpyDeviceToHost));
+    const int64_t nb = sc.n, nd = sc.ndb[cs->dcur];
+    const int64_t total_ub = nb + nd + n + 2;
+    if (total_ub >= ((int64_t)1 << 31)) return FDBCS_E_NOMEM;  // the fold's 32-bit scan components
+    const bool has_lo = lo_len >= 0, has_hi = hi_len >= 0;
+    const int64_t ll = has_lo ? lo_len : 0, hl = has_hi ? hi_len : 0;
+    // overlay tails, in 8-byte units: imported boundary j at (offset_j >> 3) + j, then lo's and hi's
+    const int64_t u_lo = ((nbytes + 7) >> 3) + n + 1, u_hi = u_lo + ((ll + 7) >> 3) + 1, u_end = u_hi + ((hl + 7) >> 3) + 1;
+    const int64_t tail_need = sc.tail_used + 8 * u_end;
+    if (tail_need + 1 >= kTailLimit) return FDBCS_E_NOMEM;
+    int rc;
+    if ((rc = ensure_history(cs, total_ub + 1, tail_need + 1))) return rc;
+    const int64_t bnd_hi = (ll + 7) / 8 * 8 + 16;
+    const int64_t gran = scan_granules(total_ub, 2);
+    if ((rc = cs->i_bnd.ensure((size_t)(bnd_hi + hl + 64)))) return rc;
+    if ((rc = cs->i_okey.ensure(16 * (size_t)(n + 2)))) return rc;
+    if ((rc = cs->i_olt.ensure(8 * (size_t)(n + 2)))) return rc;
+    if ((rc = cs->i_over.ensure(8 * (size_t)(n + 2)))) return rc;
+    if ((rc = cs->i_otail.ensure(8 * (size_t)u_end + kTailSlack))) return rc;
+    if ((rc = cs->i_mval.ensure(8 * (size_t)total_ub))) return rc;
+    if ((rc = cs->i_mkey.ensure(16 * (size_t)total_ub))) return rc;
+    if ((rc = cs->i_mlt.ensure(8 * (size_t)total_ub))) return rc;
+    if ((rc = cs->i_dblt.ensure(8 * (size_t)(nd + 1)))) return rc;
+    if ((rc = cs->i_vblt.ensure(8 * (size_t)(n + 2)))) return rc;
+    if ((rc = cs->i_state.ensure(8 * (size_t)(kIwWords + gran)))) return rc;
+    for (hipEvent_t& e : cs->i_ev)
+        if (!e) HIPOK(hipEventCreate(&e));
+    ImportArgs a{};
+    a.base = hist_of(cs, cs->cur);
+    a.delta = delta_of(cs, cs->dcur);
+    a.htail = (const uint8_t*)cs->htail[cs->tcur].p;
+    a.nb = nb;
+    a.nd = nd;
+    a.hdr = cs->header_version;
+    a.n = n;
+    a.bytes = d_bytes;
+    a.nbytes = nbytes;
+    a.offsets = d_off;
+    a.versions = d_ver;
+    a.ihdr = ihdr;
+    a.has_lo = has_lo;
+    a.has_hi = has_hi;
+    a.lo_len = (int32_t)ll;
+    a.hi_len = (int32_t)hl;
+    a.bnd = (const uint8_t*)cs->i_bnd.p;
+    a.bnd_hi = bnd_hi;
+    a.ov.key = (ulonglong2*)cs->i_okey.p;
+    a.ov.lt = (uint2*)cs->i_olt.p;
+    a.ov.ver = (int64_t*)cs->i_over.p;
+    a.otail = (uint8_t*)cs->i_otail.p;
+    a.otail_lo = u_lo;
+    a.otail_hi = u_hi;
+    a.ovhdr = has_lo ? kHole : ihdr;
+    a.words = (int64_t*)cs->i_state.p;
+    a.m_val = (int64_t*)cs->i_mval.p;
+    a.m_key = (ulonglong2*)cs->i_mkey.p;
+    a.m_lt = (uint2*)cs->i_mlt.p;
+    a.d_blt = (int64_t*)cs->i_dblt.p;
+    a.v_blt = (int64_t*)cs->i_vblt.p;
+    a.dst = hist_of(cs, cs->cur ^ 1);
+    a.tdst = (uint8_t*)cs->htail[cs->tcur ^ 1].p;
+    a.dst_cap = cs->hist_cap;
+    a.tdst_units = cs->tail_cap / 8;
+    a.new_hdr = has_lo ? cs->header_version : std::max(cs->header_version, ihdr);
+    hipStream_t s = cs->stream;
+    if (ll) HIPOK(hipMemcpyAsync(cs->i_bnd.p, lo_key, (size_t)ll, hipMemcpyHostToDevice, s));
+    if (hl) HIPOK(hipMemcpyAsync((uint8_t*)cs->i_bnd.p + bnd_hi, hi_key, (size_t)hl, hipMemcpyHostToDevice, s));
+    HIPOK(hipMemsetAsync(cs->i_state.p, 0, 8 * (size_t)(kIwWords + gran), s));
+    const int64_t none = kHole;
+    HIPOK(hipMemcpyAsync(&a.words[kIwMaxVer], &none, 8, hipMemcpyHostToDevice, s));
+    int64_t words[kIwWords];
+    HIPOK(hipEventRecord(cs->i_ev[0], s));
+    launch_import_overlay(s, a);
+    HIPOK(take_launch_error());
+    HIPOK(hipEventRecord(cs->i_ev[1], s));
+    HIPOK(hipMemcpyAsync(words, cs->i_state.p, sizeof(words), hipMemcpyDeviceToHost, s));
+    HIPOK(hipStreamSynchronize(s));
+    cs->i_ms_kernels = ev_ms(cs->i_ev[0], cs->i_ev[1]);
+    if ((int32_t)words[kIwError] & 1) return FDBCS_E_INVALID;
+    if (words[kIwError]) return FDBCS_E_DEVICE;
+    if (has_lo && has_hi && cmp_bytes(lo_key, lo_len, hi_key, hi_len) == 0) {  // an empty range: validated, nothing to do
+        *boundaries_out = nb + nd;
+        return FDBCS_OK;
+    }
+    const int64_t m = words[kIwM];
+    if (m < 0 || m > n + 2) return FDBCS_E_DEVICE;
+    HIPOK(hipEventRecord(cs->i_ev[2], s));
+    HIPOK(hipMemsetAsync(cs->i_mlt.p, 0, 8 * (size_t)(nb + nd + m), s));
+    launch_import_fold(s, a, m, (uint64_t*)cs->i_state.p + kIwWords);
+    HIPOK(take_launch_error());
+    HIPOK(hipEventRecord(cs->i_ev[3], s));
+    HIPOK(hipMemcpyAsync(words, cs->i_state.p, sizeof(words), hipMemcpyDeviceToHost, s));
+    HIPOK(hipStreamSynchronize(s));
+    cs->i_ms_kernels += ev_ms(cs->i_ev[2], cs->i_ev[3]);
+    if ((int32_t)words[kIwError] & 8) return FDBCS_E_NOMEM;
+    if (words[kIwError] || ((const int32_t*)&words[kIwScan])[1]) return FDBCS_E_DEVICE;
+    // success: the buffers the fold filled become current, the delta is empty
+    const int64_t kept = words[kIwKept], tail_used = 8 * words[kIwTailUnits];
+    cs->cur ^= 1;
+    cs->tcur ^= 1;
+    Scalars ns{};
+    ns.n = kept;
+    ns.tail_used = tail_used;
+    HIPOK(hipMemcpyAsync(cs->scal.p, &ns, sizeof(ns), hipMemcpyHostToDevice, s));
+    HIPOK(hipEventRecord(cs->i_ev[4], s));
+    launch_rangemax(s, levels_of(cs, cs->cur), (Scalars*)cs->scal.p, &((Scalars*)cs->scal.p)->n, cs->lvl3_n, cs->lvl2_n,
+                    std::max<int64_t>(kept, 1));
+    // the greatest version the import left in the history: the top of the rebuilt range-max levels
+    launch_import_max(s, levels_of(cs, cs->cur), cs->lvl3_n, &a.words[kIwMaxVer]);
+    HIPOK(take_launch_error());
+    HIPOK(hipEventRecord(cs->i_ev[5], s));
+    HIPOK(hipMemcpyAsync(&words[kIwMaxVer], &a.words[kIwMaxVer], 8, hipMemcpyDeviceToHost, s));
+    HIPOK(hipStreamSynchronize(s));
+    cs->i_ms_kernels += ev_ms(cs->i_ev[4], cs->i_ev[5]);
+    cs->header_version = a.new_hdr;
+    cs->max_written = std::max({cs->max_written, a.new_hdr, words[kIwMaxVer]});
+    cs->ddir_epoch[0] = cs->ddir_epoch[1] = 0;  // the delta is empty: no directory entry of it is trusted
+    cs->prev_segs = false;
+    cs->n_ub = kept;
+    cs->nd_ub = 0;
+    cs->tail_ub = tail_used;
+    *boundaries_out = kept;
+    return FDBCS_OK;
+}
+
+static int import_bounds_ok(const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key, int32_t hi_len) {
+    if ((lo_len > 0 && !lo_key) || (hi_len > 0 && !hi_key)) return FDBCS_E_INVALID;
+    if (lo_len >= 0 && hi_len >= 0 && cmp_bytes(lo_key, lo_len, hi_key, hi_len) > 0) return FDBCS_E_INVALID;
+    return FDBCS_OK;
+}
+
+int fdbcs_history_import(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key,
+                         int32_t hi_len, int64_t n, const uint8_t* key_bytes, const int64_t* key_offsets,
+                         const int64_t* versions, int64_t header_version, int64_t* boundaries_out) {
+    if (!cs || !boundaries_out || n < 0 || (n > 0 && (!key_offsets || !versions))) return FDBCS_E_INVALID;
+    if (int rc = import_bounds_ok(lo_key, lo_len, hi_key, hi_len)) return rc;
+    const int64_t nbytes = n ? key_offsets[n] : 0;
+    if (nbytes < 0 || (nbytes > 0 && !key_bytes)) return FDBCS_E_INVALID;
+    if (cs->inflight) return FDBCS_E_STATE;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPOK(hipSetDevice(cs->device));
+    if (int rc = sync_all(cs)) return rc;
+    cs->x_valid = false;
+    // the three arrays go up as they are
+    int rc;
+    if ((rc = cs->i_bytes.ensure((size_t)nbytes + 64))) return rc;
+    if ((rc = cs->i_off.ensure(8 * (size_t)(n + 1)))) return rc;
+    if ((rc = cs->i_ver.ensure(8 * (size_t)(n + 1)))) return rc;
+    hipStream_t s = cs->stream;
+    if (nbytes) HIPOK(hipMemcpyAsync(cs->i_bytes.p, key_bytes, (size_t)nbytes, hipMemcpyHostToDevice, s));
+    if (n) {
+        HIPOK(hipMemcpyAsync(cs->i_off.p, key_offsets, 8 * (size_t)(n + 1), hipMemcpyHostToDevice, s));
+        HIPOK(hipMemcpyAsync(cs->i_ver.p, versions, 8 * (size_t)n, hipMemcpyHostToDevice, s));
+    }
+    rc = import_device(cs, lo_key, lo_len, hi_key, hi_len, n, (const uint8_t*)cs->i_bytes.p, nbytes,
+                       (const int64_t*)cs->i_off.p, (const int64_t*)cs->i_ver.p, header_version, boundaries_out);
+    cs->i_ms_host = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return rc;
+}
+
+int fdbcs_history_import_pending(fdbcs_conflict_set* dst, fdbcs_conflict_set* src, const uint8_t* lo_key, int32_t lo_len,
+                                 const uint8_t* hi_key, int32_t hi_len, int64_t* boundaries_out) {
+    if (!dst || !src || src == dst || !boundaries_out || src->device != dst->device) return FDBCS_E_INVALID;
+    if (int rc = import_bounds_ok(lo_key, lo_len, hi_key, hi_len)) return rc;
+    if (dst->inflight || src->inflight || !src->x_valid) return FDBCS_E_STATE;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPOK(hipSetDevice(dst->device));
+    if (int rc = sync_all(dst)) return rc;
+    dst->x_valid = false;
+    // src's export finished on its own stream before fdbcs_history_export returned: its result
+    // arrays are read in place, and stay pending
+    const int rc = import_device(dst, lo_key, lo_len, hi_key, hi_len, src->x_n, (const uint8_t*)src->x_bytes.p,
+                                 src->x_nbytes, (const int64_t*)src->x_off.p, (const int64_t*)src->x_ver.p, src->x_hdr,
+                                 boundaries_out);
+    dst->i_ms_host = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return rc;
+}
+
+int fdbcs_history_import_timing(fdbcs_conflict_set* cs, double* ms_kernels, double* ms_host) {
+    if (!cs || !ms_kernels || !ms_host) return FDBCS_E_INVALID;
+    *ms_kernels = cs->i_ms_kernels;
+    *ms_host = cs->i_ms_host;
     return FDBCS_OK;
 }
 

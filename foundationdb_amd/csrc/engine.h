@@ -493,4 +493,61 @@ int64_t export_tiles(int64_t n);
 // mode: the compaction search's (1: lane_lower_bound, 2: the long-key form).
 void launch_export(hipStream_t s, const ExportArgs& a, const MaxLevels& basem, uint64_t* granules, int mode);
 
+// ---- history import (fdbcs_history_import / fdbcs_history_import_pending): folds an exported range
+// into both tiers, H'(k) = max(H(k), I(k)) over [lo, hi).  Reads the current buffers, writes only
+// scratch and the non-current base buffer and tail arena; the host switches to them on success.
+// Device words of one import (zeroed before its launches).
+enum ImportWord {
+    kIwError,      // int: 1 invalid input, 4 a merged position out of range, 8 a capacity bound
+    kIwJlo,        // imported boundaries <= lo
+    kIwM,          // overlay boundaries: lo, the imported ones inside (lo, hi), hi
+    kIwKept,       // boundaries of the new base
+    kIwTailUnits,  // 8-byte units used in the new tail arena
+    kIwMaxVer,     // greatest version of the new base (k_import_max, after its levels are rebuilt)
+    kIwScan,       // int counter, int error of the fold's scan
+    kIwWords = 8
+};
+struct ImportArgs {
+    Hist base, delta;      // the receiving set's tiers
+    const uint8_t* htail;  // their tail arena
+    int64_t nb, nd;        // exact tier sizes (the set is idle)
+    int64_t hdr;           // the set's header version
+    // the imported arrays, on the device, in the layout fdbcs_load_history takes
+    int64_t n;
+    const uint8_t* bytes;  // 8-byte aligned, >= 16 readable bytes past nbytes
+    int64_t nbytes;
+    const int64_t* offsets;
+    const int64_t* versions;
+    int64_t ihdr;
+    int32_t has_lo, has_hi;
+    int32_t lo_len, hi_len;
+    const uint8_t* bnd;    // lo's bytes at 0, hi's at bnd_hi (8-byte aligned, >= 16 readable bytes past each)
+    int64_t bnd_hi;
+    // the overlay: a third stream shaped like the delta tier (kHole outside [lo, hi), I inside)
+    Hist ov;
+    uint8_t* otail;        // its tails: imported boundary j at unit (offsets[j] >> 3) + j, then lo's and hi's
+    int64_t otail_lo, otail_hi;  // units of lo's and hi's tails
+    int64_t ovhdr;         // version below the first overlay boundary (kHole with a lower bound, else ihdr)
+    int64_t* words;        // [kIwWords] ImportWord
+    // the merged stream of the three (on equal keys: delta, overlay, base): per position the
+    // version H' at the element's key, its prefix words and (len | bit 31: tail in otail, tail unit)
+    int64_t* m_val;
+    ulonglong2* m_key;
+    uint2* m_lt;       // zeroed before the launches: a position nobody wrote reads as an empty key
+    int64_t* d_blt;    // [nd] base boundaries below delta boundary j
+    int64_t* v_blt;    // [m] base boundaries below overlay boundary e
+    // result: the non-current base buffer and tail arena
+    Hist dst;
+    uint8_t* tdst;
+    int64_t dst_cap, tdst_units;
+    int64_t new_hdr;       // the set's header after the import
+};
+// Validate the imported arrays, place lo / hi in them and normalize the overlay (phase 1); the host
+// reads the words (error, overlay size) before phase 2.
+void launch_import_overlay(hipStream_t s, const ImportArgs& a);
+// Merge the three streams and write the new base (phase 2).  m: the overlay size phase 1 reported.
+void launch_import_fold(hipStream_t s, const ImportArgs& a, int64_t m, uint64_t* granules);
+// The greatest version of the tier whose levels `m` were just rebuilt, into *out (device, atomicMax).
+void launch_import_max(hipStream_t s, const MaxLevels& m, int64_t lvl3_n, int64_t* out);
+
 }  // namespace fdbcs

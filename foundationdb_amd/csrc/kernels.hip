@@ -4595,4 +4595,314 @@ void launch_export(hipStream_t s, const ExportArgs& a, const MaxLevels& basem, u
     fdb_launch(k_export_scan, dim3((unsigned)tiles), dim3(kScanThreads), 0, s, a, st);
 }
 
+// ------------------------------------------------------------------ history import
+//
+// H'(k) = max(H(k), I(k)) for lo <= k < hi and H(k) elsewhere, I the step function of the imported
+// arrays (the export's layout).  The import becomes a third stream shaped like the delta tier, the
+// overlay: a boundary at lo carrying I(lo), the imported boundaries inside (lo, hi), a boundary at
+// hi carrying kHole (no lo: the overlay's header is the imported header; no hi: no closing hole).
+// With H the two tiers' value, H' = overlay == kHole ? H : max(H, overlay) at every key.
+//   k_import_check      one lane per imported boundary: offsets inside the byte array, lengths not
+//                       negative, neighbours strictly ascending (full byte compare) -> error word
+//   k_import_bounds     imported boundaries <= lo and < hi (plain binary searches), overlay size
+//   k_import_normalize  one lane per overlay boundary: big-endian prefix words, (len, tail unit),
+//                       version, and the bytes past 16 as zero-padded 8-byte words (the inverse of
+//                       export_put_key; source keys start at any byte).  Tail units need no scan:
+//                       imported boundary j owns unit (offsets[j] >> 3) + j, which never overlaps
+//                       its neighbours' and wastes at most 15 bytes per key of scratch.
+//   k_import_rank<S>    one lane per element of stream S: its lower bounds in the other two give
+//                       its position in the merged order (on equal keys delta, overlay, base) and
+//                       all three streams' values at its key, hence H'.  Later elements of a tie
+//                       repeat their predecessor's value, so no case is special.  The element's
+//                       prefix words, (len, tail unit) and H' go to its merged position.  Base
+//                       boundaries (S = 0, launched last) search no keys: their ranks follow from
+//                       the lower bounds the other two streams' elements found in the base.
+//   k_scan<ImportFold>  flags value changes along the merged stream, scans (kept, tail units) with
+//                       the look-back and writes the kept boundaries into the non-current base
+//                       buffer, their tails packed into the non-current arena; every read of the
+//                       merged stream is coalesced.
+// Nothing current is written: the host switches buffers after reading the result words.
+
+__device__ __forceinline__ uint64_t import_load8(const uint8_t* p) {  // bytes p[0..8), p[0] lowest
+    const uintptr_t a = (uintptr_t)p;
+    const uint64_t* w = (const uint64_t*)(a & ~(uintptr_t)7);
+    const uint32_t sh = (uint32_t)(a & 7u) * 8u;
+    const uint64_t x = w[0];
+    return sh ? (x >> sh) | (w[1] << (64u - sh)) : x;
+}
+
+// memcmp-then-length order of two byte strings at any alignment, 8 bytes per step.
+__device__ __forceinline__ int import_cmp(const uint8_t* a, uint32_t al, const uint8_t* b, uint32_t bl) {
+    const uint32_t n = al < bl ? al : bl;
+    uint32_t i = 0;
+    for (; i + 8u <= n; i += 8u) {
+        const uint64_t x = __builtin_bswap64(import_load8(a + i)), y = __builtin_bswap64(import_load8(b + i));
+        if (x != y) return x < y ? -1 : 1;
+    }
+    if (i < n) {
+        const uint64_t msk = ~0ull << (64u - 8u * (n - i));
+        const uint64_t x = __builtin_bswap64(import_load8(a + i)) & msk, y = __builtin_bswap64(import_load8(b + i)) & msk;
+        if (x != y) return x < y ? -1 : 1;
+    }
+    return (al > bl) - (al < bl);
+}
+
+// Imported boundary j's bytes; false (and an empty key) unless its offsets lie inside the byte array.
+__device__ __forceinline__ bool import_key(const ImportArgs& a, int64_t j, const uint8_t*& p, uint32_t& len) {
+    const int64_t o0 = a.offsets[j], o1 = a.offsets[j + 1];
+    p = a.bytes;
+    len = 0;
+    if (o0 < 0 || o1 < o0 || o1 > a.nbytes || o1 - o0 > (int64_t)INT32_MAX) return false;
+    p = a.bytes + o0;
+    len = (uint32_t)(o1 - o0);
+    return true;
+}
+
+__global__ __launch_bounds__(kBlock) void k_import_check(ImportArgs a) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= a.n) return;
+    const uint8_t *p, *q;
+    uint32_t pl, ql;
+    bool ok = import_key(a, j, p, pl);
+    if (j == 0) {
+        ok = ok && a.offsets[0] == 0;
+    } else if (ok) {
+        ok = import_key(a, j - 1, q, ql) && import_cmp(q, ql, p, pl) < 0;
+    }
+    if (!ok) atomicOr((int*)&a.words[kIwError], 1);
+}
+
+__global__ __launch_bounds__(64) void k_import_bounds(ImportArgs a) {
+    __shared__ int64_t r[2];  // imported boundaries <= lo, < hi
+    const int t = threadIdx.x;
+    if (t < 2) {
+        const bool is_hi = t == 1;
+        int64_t lo = 0, hi = a.n;
+        if (!(is_hi ? a.has_hi : a.has_lo)) {
+            lo = is_hi ? a.n : 0;
+        } else {
+            const uint8_t* b = a.bnd + (is_hi ? a.bnd_hi : 0);
+            const uint32_t bl = (uint32_t)(is_hi ? a.hi_len : a.lo_len);
+            while (lo < hi) {
+                const int64_t mid = lo + (hi - lo) / 2;
+                const uint8_t* p;
+                uint32_t pl;
+                import_key(a, mid, p, pl);
+                const int c = import_cmp(p, pl, b, bl);
+                if (c < 0 || (!is_hi && c == 0))
+                    lo = mid + 1;
+                else
+                    hi = mid;
+            }
+        }
+        r[t] = lo;
+    }
+    __syncthreads();
+    if (t != 0) return;
+    const int64_t inner = r[1] > r[0] ? r[1] - r[0] : 0;
+    a.words[kIwJlo] = r[0];
+    a.words[kIwM] = (a.has_lo ? 1 : 0) + inner + (a.has_hi ? 1 : 0);
+}
+
+__global__ __launch_bounds__(kBlock) void k_import_normalize(ImportArgs a) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t m = a.words[kIwM], jlo = a.words[kIwJlo];
+    if (e >= m || e >= a.n + 2) return;
+    const uint8_t* p;
+    uint32_t len;
+    int64_t ver, unit;
+    if (a.has_lo && e == 0) {  // the range's first boundary carries I(lo)
+        p = a.bnd;
+        len = (uint32_t)a.lo_len;
+        ver = jlo > 0 ? a.versions[jlo - 1] : a.ihdr;
+        unit = a.otail_lo;
+    } else if (a.has_hi && e == m - 1) {  // the synthetic boundary that closes the range
+        p = a.bnd + a.bnd_hi;
+        len = (uint32_t)a.hi_len;
+        ver = kHole;
+        unit = a.otail_hi;
+    } else {
+        const int64_t j = jlo + e - (a.has_lo ? 1 : 0);
+        if (j < 0 || j >= a.n || !import_key(a, j, p, len)) {
+            atomicOr((int*)&a.words[kIwError], 1);
+            return;
+        }
+        ver = a.versions[j];
+        unit = (a.offsets[j] >> 3) + j;
+    }
+    uint64_t w0 = len ? import_load8(p) : 0ull, w1 = len > 8u ? import_load8(p + 8) : 0ull;
+    if (len < 8u) w0 &= (1ull << (8u * len)) - 1ull;
+    if (len < 16u) w1 &= len > 8u ? (1ull << (8u * (len - 8u))) - 1ull : 0ull;
+    // the first key byte is the lowest of the loaded word and the highest of the prefix word
+    a.ov.key[e] = make_ulonglong2(__builtin_bswap64(w0), __builtin_bswap64(w1));
+    a.ov.lt[e] = make_uint2(len, len > 16u ? (uint32_t)unit : 0u);
+    a.ov.ver[e] = ver;
+    if (len > 16u) {
+        const uint32_t nt = len - 16u, nu = (nt + 7u) >> 3;
+        uint64_t* d = (uint64_t*)hist_tail(a.otail, (uint32_t)unit);
+        for (uint32_t u = 0; u < nu; u++) {
+            uint64_t w = import_load8(p + 16u + 8u * u);
+            const uint32_t left = nt - 8u * u;
+            if (left < 8u) w &= (1ull << (8u * left)) - 1ull;  // zero padded
+            d[u] = w;
+        }
+    }
+}
+
+// Boundaries of a tier below q, and whether the next one equals it.
+__device__ __forceinline__ int64_t import_lower(const Hist& h, int64_t n, const uint8_t* arena, const DKey& q,
+                                                const uint8_t* qtail, bool& exact) {
+    const int64_t lb = export_bound(h, n, arena, q, qtail, false);
+    exact = lb < n && hist_cmp(h, lb, arena, q, qtail) == 0;
+    return lb;
+}
+
+// Entries of the ascending array x[0..n) that are <= v.
+__device__ __forceinline__ int64_t import_count_le(const int64_t* x, int64_t n, int64_t v) {
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (x[mid] <= v)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+constexpr uint32_t kImportOvTail = 1u << 31;  // ImportArgs::m_lt len bit: the tail is in the overlay's arena
+
+// S: the stream of this launch's elements (0 base, 1 delta, 2 overlay), one lane each.
+template <int S>
+__global__ __launch_bounds__(kBlock) void k_import_rank(ImportArgs a, int64_t m) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t total = a.nb + a.nd + m;
+    if (i >= (S == 0 ? a.nb : S == 1 ? a.nd : m)) return;
+    ulonglong2 k;
+    uint2 lt;
+    const uint8_t* arena = S == 2 ? a.otail : a.htail;
+    if constexpr (S == 0) k = a.base.key[i], lt = a.base.lt[i];
+    if constexpr (S == 1) k = a.delta.key[i], lt = a.delta.lt[i];
+    if constexpr (S == 2) k = a.ov.key[i], lt = a.ov.lt[i];
+    DKey q;
+    q.hi = k.x;
+    q.lo = k.y;
+    q.len = lt.x;
+    q.tail = 0;  // the query's tail starts at qtail
+    const uint8_t* qtail = hist_tail(arena, lt.x > 16u ? lt.y : 0u);
+    // boundaries below the key (lt) and at or below it (le) in each stream
+    int64_t b_lt = i, b_le = i + 1, d_lt = i, d_le = i + 1, v_lt = i, v_le = i + 1;
+    [[maybe_unused]] bool ex;
+    if constexpr (S == 0) {
+        // a base boundary's ranks in the other two streams follow from their elements' lower bounds
+        // in the base (k_import_rank<1>, <2> ran first): the delta boundaries at or below base key i
+        // are those with at most i base boundaries below them.  A search over a dense ascending
+        // array of integers, no key compares.
+        d_le = import_count_le(a.d_blt, a.nd, i);
+        v_le = import_count_le(a.v_blt, m, i);
+    } else {
+        b_lt = import_lower(a.base, a.nb, a.htail, q, qtail, ex);
+        b_le = b_lt + (ex ? 1 : 0);
+        (S == 1 ? a.d_blt : a.v_blt)[i] = b_lt;
+    }
+    if constexpr (S == 2) {
+        d_lt = import_lower(a.delta, a.nd, a.htail, q, qtail, ex);
+        d_le = d_lt + (ex ? 1 : 0);
+    }
+    if constexpr (S == 1) {
+        v_lt = import_lower(a.ov, m, a.otail, q, qtail, ex);
+        v_le = v_lt + (ex ? 1 : 0);
+    }
+    // on equal keys: delta, then overlay, then base
+    const int64_t pos = S == 1 ? d_lt + v_lt + b_lt : S == 2 ? v_lt + d_le + b_lt : b_lt + d_le + v_le;
+    const int64_t dv = d_le > 0 ? a.delta.ver[d_le - 1] : kHole;
+    const int64_t bv = b_le > 0 ? a.base.ver[b_le - 1] : a.hdr;
+    const int64_t ov = v_le > 0 ? a.ov.ver[v_le - 1] : a.ovhdr;
+    int64_t v = dv != kHole ? dv : bv;
+    if (ov != kHole && ov > v) v = ov;
+    if (pos < 0 || pos >= total) {  // streams out of order: never index past the merged arrays
+        atomicOr((int*)&a.words[kIwError], 4);
+        return;
+    }
+    a.m_val[pos] = v;
+    a.m_key[pos] = k;
+    a.m_lt[pos] = make_uint2(lt.x | (S == 2 ? kImportOvTail : 0u), lt.x > 16u ? lt.y : 0u);
+}
+
+struct ImportFold {
+    ImportArgs a;
+    __device__ bool keep(int64_t p) const { return a.m_val[p] != (p ? a.m_val[p - 1] : a.new_hdr); }
+    // [0] kept boundaries, [1] their tail units (offsets in the new arena)
+    __device__ void load(int64_t p, uint32_t (&x)[2]) const {
+        const bool kp = keep(p);
+        x[0] = kp ? 1u : 0u;
+        x[1] = kp ? tail_units(a.m_lt[p].x & ~kImportOvTail) : 0u;
+    }
+    __device__ void store(int64_t p, const uint32_t (&ex)[2]) const {
+        if (!keep(p)) return;
+        uint2 lt = a.m_lt[p];
+        const bool ovt = (lt.x & kImportOvTail) != 0;
+        lt.x &= ~kImportOvTail;
+        const int64_t o = ex[0], v = a.m_val[p];
+        const uint32_t nu = tail_units(lt.x);
+        if (o >= a.dst_cap || (int64_t)ex[1] + nu > a.tdst_units) {  // never past the buffers the host sized
+            atomicOr((int*)&a.words[kIwError], 8);
+            return;
+        }
+        if (nu) {
+            const uint8_t* arena = a.htail;
+            if (ovt) arena = a.otail;
+            const uint64_t* src = (const uint64_t*)hist_tail(arena, lt.y);
+            uint64_t* d = (uint64_t*)hist_tail(a.tdst, ex[1]);
+            for (uint32_t u = 0; u < nu; u++) d[u] = src[u];
+        }
+        lt.y = nu ? ex[1] : 0u;
+        a.dst.key[o] = a.m_key[p];
+        a.dst.lt[o] = lt;
+        a.dst.ver[o] = v;
+    }
+    __device__ void finish(const uint32_t (&tot)[2]) const {
+        a.words[kIwKept] = tot[0];
+        a.words[kIwTailUnits] = tot[1];
+    }
+};
+
+// The greatest version of a tier from the top level of its range-max hierarchy (every wave of the
+// rebuild raised one of its words; unused words hold LLONG_MIN), into *out by atomicMax.
+__global__ __launch_bounds__(kBlock) void k_import_max(const int64_t* lvl3, int64_t words, int64_t* out) {
+    long long x = LLONG_MIN;
+    for (int64_t i = threadIdx.x; i < words; i += blockDim.x) {
+        const long long y = lvl3[i * kL3Pad];
+        x = y > x ? y : x;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const long long y = __shfl_xor(x, o, 64);
+        x = y > x ? y : x;
+    }
+    if ((threadIdx.x & 63) == 0 && x != LLONG_MIN) atomicMax((long long*)out, x);
+}
+
+void launch_import_max(hipStream_t s, const MaxLevels& m, int64_t lvl3_n, int64_t* out) {
+    fdb_launch(k_import_max, dim3(1), dim3(kBlock), 0, s, (const int64_t*)m.lvl[3], lvl3_n * kL3Rep, out);
+}
+
+void launch_import_overlay(hipStream_t s, const ImportArgs& a) {
+    if (a.n > 0) fdb_launch(k_import_check, dim3((unsigned)((a.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, a);
+    fdb_launch(k_import_bounds, dim3(1), dim3(64), 0, s, a);
+    fdb_launch(k_import_normalize, dim3((unsigned)((a.n + 2 + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, a);
+}
+
+void launch_import_fold(hipStream_t s, const ImportArgs& a, int64_t m, uint64_t* granules) {
+    auto grid = [](int64_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); };
+    if (a.nd > 0) fdb_launch(k_import_rank<1>, grid(a.nd), dim3(kBlock), 0, s, a, m);
+    if (m > 0) fdb_launch(k_import_rank<2>, grid(m), dim3(kBlock), 0, s, a, m);
+    if (a.nb > 0) fdb_launch(k_import_rank<0>, grid(a.nb), dim3(kBlock), 0, s, a, m);  // reads d_blt, v_blt
+    ScanState st;
+    st.granules = granules;
+    st.counter = (int*)&a.words[kIwScan];
+    st.error = st.counter + 1;
+    launch_scan<2>(s, ImportFold{a}, (const int64_t*)nullptr, a.nb + a.nd + m, st);
+}
+
 }  // namespace fdbcs

@@ -182,6 +182,37 @@ int fdbcs_history_export_read(fdbcs_conflict_set* cs, uint8_t* key_bytes, int64_
                               int64_t* key_offsets, int64_t* versions, int64_t cap);
 /* Diagnostics: device time of the last export's kernels and host time of the last read's copies (ms). */
 int fdbcs_history_export_timing(fdbcs_conflict_set* cs, double* ms_kernels, double* ms_d2h);
+/* Merge an exported history range into a live set, on the device: the receiving half of a range
+ * hand-over.  No reference counterpart.  The arrays are in the layout of fdbcs_load_history and the
+ * export and describe a step function I: I(k) is the version of the last imported boundary <= k,
+ * header_version if there is none.  With H(k) the version a read of k sees in this set, afterwards
+ *   H'(k) = max(H(k), I(k)) for lo <= k < hi,  H'(k) = H(k) elsewhere
+ * (lo_len < 0: from below every key, and the set's header becomes max(header, header_version);
+ * hi_len < 0: to the end).  Imported boundaries need not lie inside the range: one <= lo only
+ * determines I(lo), one >= hi is ignored.  lo == hi changes nothing but still validates the arrays;
+ * lo > hi is FDBCS_E_INVALID.  INT64_MIN is not a version.
+ * Both tiers are folded into a new base (O(set), like a compaction) and the delta becomes empty;
+ * *boundaries_out is the history size afterwards.  The oldest version does not move and no floor is
+ * applied; a later detect with `now` below the greatest version the import left in the history is
+ * FDBCS_E_VERSION.  A pending export result of this set is dropped.  Capacity grows as for
+ * fdbcs_load_history; the directory code fixed at the last load / clear is kept.
+ * Atomic: FDBCS_E_STATE with batches in flight, FDBCS_E_INVALID for keys not strictly ascending, a
+ * negative key length, key_offsets[0] != 0 or offsets outside the bytes, FDBCS_E_NOMEM for a
+ * capacity failure; in each case the set is exactly as before.  The host does no per-boundary work:
+ * the three arrays are uploaded as they are and validated, normalized, searched and folded by
+ * kernels. */
+int fdbcs_history_import(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, /* lo_len < 0: no lower bound */
+                         const uint8_t* hi_key, int32_t hi_len,                       /* hi_len < 0: no upper bound */
+                         int64_t n, const uint8_t* key_bytes, const int64_t* key_offsets,
+                         const int64_t* versions, int64_t header_version, int64_t* boundaries_out);
+/* The same import, reading src's pending export result (fdbcs_history_export) straight from src's
+ * device buffers: no host copy of keys, offsets or versions.  src must be another set on the same
+ * device (else FDBCS_E_INVALID) with a pending export (else FDBCS_E_STATE), which stays pending and
+ * readable. */
+int fdbcs_history_import_pending(fdbcs_conflict_set* dst, fdbcs_conflict_set* src, const uint8_t* lo_key,
+                                 int32_t lo_len, const uint8_t* hi_key, int32_t hi_len, int64_t* boundaries_out);
+/* Diagnostics: device time of the last import's kernels and host time of the whole call (ms). */
+int fdbcs_history_import_timing(fdbcs_conflict_set* cs, double* ms_kernels, double* ms_host);
 int fdbcs_get_stats(fdbcs_conflict_set* cs, fdbcs_stats* out);
 int fdbcs_reset_stats(fdbcs_conflict_set* cs);
 /* Pre-size device capacity (history boundaries, history tail bytes, and the largest batch

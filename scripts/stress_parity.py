@@ -6,12 +6,18 @@ read at set creation (directory slot budget, split check, stream layout, submitt
 compaction and GC cadence, and a sequence of batches whose snapshots straddle the oldest version; verdicts and
 conflicting-read reports must match oracle/skiplist_baseline.cpp batch by batch.
 
-    python3 scripts/stress_parity.py [seconds] [first_seed] [--state-every K]
+    python3 scripts/stress_parity.py [seconds] [first_seed] [--state-every K] [--import-every K]
 
 --state-every K (default off) also feeds the semantic oracle and compares the engine's exported
 history (ConflictSet.dump_history at floor = oldest version) with the canonical form of the oracle's
 step function every K batches: a wrong version or a lost boundary shows in the batch that made it,
 not when a later read happens to meet it.
+
+--import-every K (default off; implies --state-every 1 unless given) merges, every K batches, a
+random key range of a second set's history into the engine (ConflictSet.merge_history, every other
+time merge_pending_export), compares the exported state with merge_max over the canonical forms
+(tests/import_helpers.py) and reloads both oracles with it, so the batches that follow check the
+verdicts the merged history gives.
 
 Exit status 1 and the failing seed on the first mismatch."""
 import os
@@ -28,6 +34,7 @@ from foundationdb_amd.packing import CommitTransaction, KeyRange, PackedBatch  #
 from oracle import oracle  # noqa: E402
 from tests.export_helpers import canon, split_dump  # noqa: E402
 from tests.helpers import EngineDriver  # noqa: E402
+from tests.import_helpers import merge_max_fast, pack  # noqa: E402
 
 KNOBS = {
     "FDBCS_DIR_BITS": ["0", "0", "16", "18"],
@@ -38,7 +45,41 @@ KNOBS = {
 }
 
 
-def one(seed, state_every=0):
+def merge_round(rng, e, o, so, key, hdr, now, pending):
+    """Merge a random range of a second set's random history (versions up to `now`) into the engine
+    and reload the oracles with merge_max; returns (error, the first set's header afterwards)."""
+    ks = sorted({key(True) for _ in range(int(rng.integers(0, 3000)))})
+    e2 = C.ConflictSet(0)
+    e2.load_history(*pack((int(rng.integers(0, now + 1)), ks, rng.integers(0, now + 1, size=len(ks)))))
+    lo = key() if rng.random() < 0.7 else None
+    hi = key() if rng.random() < 0.7 else None
+    if lo is not None and hi is not None and lo > hi:
+        lo, hi = hi, lo
+    dump = e2.dump_history(lo, hi, C.NO_FLOOR)
+    oldest = so.oldest_version
+    own = canon(*so.dump_history(), hdr, oldest)
+    merged = merge_max_fast(own, split_dump(dump), lo, hi)
+    want = canon(merged[1], merged[2], merged[0], oldest)
+    if pending:
+        e2.export_history(lo, hi, C.NO_FLOOR)
+        e.cs.merge_pending_export(e2, lo, hi)
+    else:
+        e.cs.merge_history(*dump, lo=lo, hi=hi)
+    e2.close()
+    got = split_dump(e.cs.dump_history())
+    if got != want:
+        return f"merged state [{lo!r}, {hi!r}) pending={pending}: {len(got[1])} boundaries, merge_max {len(want[1])}", hdr
+    kb, ko, vv, h = pack(want)
+    for x in (o, so):
+        if len(vv):
+            x.load_history(kb, ko, vv, h)
+        else:
+            x.clear(h)
+        x.set_oldest_version(oldest)
+    return None, h
+
+
+def one(seed, state_every=0, import_every=0):
     rng = np.random.default_rng(seed)
     for k, vals in KNOBS.items():
         os.environ[k] = vals[int(rng.integers(0, len(vals)))]
@@ -78,7 +119,7 @@ def one(seed, state_every=0):
     if state_every:  # the skip-list restatement has no dump: the semantic oracle holds the state
         so = oracle.OracleConflictSet()
         so.load_history(kb, ko, vers)
-    now, oldest = 1000, 0
+    now, oldest, hdr, merges = 1000, 0, 0, 0
     for i in range(int(rng.integers(3, 10))):
         now += int(rng.integers(1, 200))
         txns = []
@@ -105,10 +146,15 @@ def one(seed, state_every=0):
             so.detect(pb, now, oldest)
             if (i + 1) % state_every == 0:
                 keys, hv = so.dump_history()
-                want = canon(keys, hv, 0, so.oldest_version)
+                want = canon(keys, hv, hdr, so.oldest_version)
                 got = split_dump(e.cs.dump_history())
                 if got != want:
                     return f"exported state batch {i}: {len(got[1])} boundaries, oracle {len(want[1])}"
+            if import_every and (i + 1) % import_every == 0:
+                err, hdr = merge_round(rng, e, o, so, key, hdr, now, merges & 1)
+                merges += 1
+                if err:
+                    return f"batch {i}: {err}"
     e.cs.close()
     return None
 
@@ -120,13 +166,19 @@ def main():
         k = args.index("--state-every")
         state_every = int(args[k + 1])
         del args[k:k + 2]
+    import_every = 0
+    if "--import-every" in args:
+        k = args.index("--import-every")
+        import_every = int(args[k + 1])
+        del args[k:k + 2]
+        state_every = state_every or 1
     budget = float(args[0]) if len(args) > 0 else 120.0
     seed = int(args[1]) if len(args) > 1 else 1
     oracle.build()
     t0 = time.time()
     n = 0
     while time.time() - t0 < budget:
-        err = one(seed, state_every)
+        err = one(seed, state_every, import_every)
         knobs = {k: os.environ[k] for k in KNOBS}
         if err:
             print(f"MISMATCH seed {seed} knobs {knobs}: {err}", flush=True)
