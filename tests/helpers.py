@@ -141,3 +141,99 @@ def oracle_scenario_lists(oracle_mod, scenarios):
             res.append((v, nc, to, nc2))
         out.append(res)
     return out
+
+
+# ---- sequences shared by the verdict tests (test_gpu_parity.py) and the stored-state tests
+# (test_gpu_state_paths.py): one copy, so both run the same batches
+
+
+def prefixed(pb, prefix):
+    """The same batch with `prefix` prepended to every key (order and overlaps unchanged)."""
+    lens = np.diff(pb.key_offsets)
+    parts = [np.frombuffer(prefix, np.uint8)]
+    out = []
+    for k in range(len(lens)):
+        out.append(parts[0])
+        out.append(pb.key_bytes[pb.key_offsets[k] : pb.key_offsets[k + 1]])
+    kb = np.concatenate(out) if out else np.zeros(0, np.uint8)
+    ko = np.concatenate([[0], np.cumsum(lens + len(prefix))]).astype(np.int64)
+    return PackedBatch(pb.read_snapshot, pb.report, pb.read_offsets, pb.write_offsets, kb, ko)
+
+
+# Every engine knob that selects a different kernel or submission path (DESIGN.md §5 "Engine knobs").
+PIPELINE_KNOBS = [{"FDBCS_SPLIT_CHECK": "1"}, {"FDBCS_SPLIT_CHECK": "0"},
+                  {"FDBCS_SORT_COLD": "1"},
+                  {"FDBCS_SUBMIT_THREAD": "0", "FDBCS_SPLIT_CHECK": "1"}, {"FDBCS_SUBMIT_THREAD": "0"},
+                  {"FDBCS_WRITE_GROUPS": "0"}, {"FDBCS_SERIAL": "1"},
+                  {"FDBCS_DIRECTORY": "0"}, {"FDBCS_SKIP_EDGES": "0"}]
+
+SORT_BUCKETS = [("3000", "0"), ("600", "0"), ("40", "0"), ("160", "1"), ("64", "1"), ("8", "0")]
+
+
+class knob_env:
+    """Engine knobs in the environment while a set is created (they are read at creation)."""
+
+    def __init__(self, knobs):
+        self.knobs = knobs
+
+    def __enter__(self):
+        self.saved = {k: os.environ.get(k) for k in self.knobs}
+        os.environ.update(self.knobs)
+
+    def __exit__(self, *exc):
+        for k, v in self.saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def pipeline_variant_batches():
+    """20 batches of (PackedBatch, now, new_oldest): keys up to 3 bytes, up to 24 (short-key lookups)
+    and up to 40 (long-key lookups) in some batches."""
+    from foundationdb_amd import workloads as W
+
+    rng = np.random.default_rng(71)
+    now = 10
+    for i in range(20):
+        pb = W.random_small_batch(rng, 250, alphabet=6 if i % 2 else 200,
+                                  max_len=24 if i % 3 == 0 else (40 if i % 5 == 1 else 3), now=now, staleness=12)
+        yield pb, now, now - 9
+        now += 4
+
+
+def sort_bucket_batches():
+    """6 batches of 700 transactions; every second one behind a shared 17-byte prefix (prefix ties
+    resolved by the tail bytes, warm splitters that no longer fit the keys)."""
+    from foundationdb_amd import workloads as W
+
+    rng = np.random.default_rng(31)
+    seq = []
+    now = 10
+    for i in range(6):
+        pb = W.random_small_batch(rng, 700, alphabet=3, max_len=4, now=now, staleness=10, report_frac=0.5)
+        if i % 2:
+            pb = prefixed(pb, b"\x02tenant\x00orders\x00\x15\x01")
+        seq.append((pb, now, now - 3))
+        now += 2
+    return seq
+
+
+def sequential_fallback_batches():
+    """4 batches dense enough to overflow a candidate-edge capacity of 8 (FDBCS_EDGE_CAP)."""
+    from foundationdb_amd import workloads as W
+
+    rng = np.random.default_rng(8)
+    seq = []
+    now = 10
+    for _ in range(4):
+        seq.append((W.random_small_batch(rng, 100, alphabet=2, max_len=3, now=now, staleness=10, report_frac=1.0),
+                    now, now - 3))
+        now += 2
+    return seq
+
+
+def shift_batch(pb, D):
+    """The same batch with D added to every read snapshot (the version axis moved by D)."""
+    return PackedBatch(pb.read_snapshot + np.int64(D), pb.report, pb.read_offsets, pb.write_offsets, pb.key_bytes,
+                       pb.key_offsets)

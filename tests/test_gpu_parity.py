@@ -2,14 +2,14 @@
 conflicting-key reports, on the reference's known answers, frozen fixtures, live random batches,
 the BASELINE configurations (reduced where the oracle must keep up) and size-independent
 properties at full size."""
-import os
-
 import numpy as np
 import pytest
 
 from foundationdb_amd import workloads as W
 from foundationdb_amd.packing import CommitTransaction, KeyRange, PackedBatch
-from tests.helpers import EngineDriver, load_json, nonempty, random_fixture_sequences, scenario_batches
+from tests.helpers import (PIPELINE_KNOBS, SORT_BUCKETS, EngineDriver, knob_env, load_json, nonempty,
+                           pipeline_variant_batches, random_fixture_sequences, scenario_batches,
+                           sequential_fallback_batches, sort_bucket_batches)
 
 pytestmark = pytest.mark.gpu
 
@@ -207,9 +207,11 @@ def test_long_shared_prefix_runs(engine, oracle_mod, monkeypatch, split, tail_ma
 
 @pytest.mark.parametrize("directory,split,gc", [("1", "2", 2), ("1", "1", 2), ("0", "2", 2), ("1", "2", 0)])
 def test_radix_directory_slots(engine, oracle_mod, monkeypatch, directory, split, gc):
-    """The base tier's radix directory (first two key bytes -> level-0 samples): sparse slots
-    counted directly, a crowded slot (one 2-byte prefix holding thousands of boundaries) taking
-    the tree, keys at the slot edges (empty key, 0x0000.., 0xffff.., bare 2-byte keys), and
+    """The base tier's radix directory (engine.h: a slot is the order-preserving rank code of the
+    key bytes after the prefix every loaded key shares, and holds the first skey8 group start,
+    every 8th boundary, not below it): sparse slots counted directly, a crowded slot (one 2-byte
+    prefix holding thousands of boundaries) taking the tree, keys at the slot edges (empty key,
+    0x0000.., 0xffff.., bare 2-byte keys), and
     compactions rebuilding the directory between batches; gc=0 keeps every batch in the delta
     tier, whose directory k_epilogue refills per batch under a new epoch (runs over kDirRun slots
     stay stale and take the tree)."""
@@ -566,8 +568,7 @@ def test_add_packed_rejects_inverted_ranges(engine, oracle_mod, n_txn):
     cs.close()
 
 
-@pytest.mark.parametrize("bucket,cold", [("3000", "0"), ("600", "0"), ("40", "0"), ("160", "1"), ("64", "1"),
-                                         ("8", "0")])
+@pytest.mark.parametrize("bucket,cold", SORT_BUCKETS)
 def test_sort_bucket_sizes_match(engine, oracle_mod, monkeypatch, bucket, cold):
     """Buckets past the per-wave capacity (ranked by their workgroup, the overflow list gathered),
     tiny ones, cold-start splitters from the batch's own samples, and warm splitters that no longer
@@ -575,44 +576,15 @@ def test_sort_bucket_sizes_match(engine, oracle_mod, monkeypatch, bucket, cold):
     with keys longer than the 16-byte prefix, give the same verdicts and reports."""
     monkeypatch.setenv("FDBCS_SORT_BUCKET", bucket)
     monkeypatch.setenv("FDBCS_SORT_COLD", cold)
-    rng = np.random.default_rng(31)
-    seq = []
-    now = 10
-    for i in range(6):
-        pb = W.random_small_batch(rng, 700, alphabet=3, max_len=4, now=now, staleness=10, report_frac=0.5)
-        if i % 2:  # every key behind a shared 17-byte prefix: prefix ties resolved by the tail bytes
-            pb = prefixed(pb, b"\x02tenant\x00orders\x00\x15\x01")
-        seq.append((pb, now, now - 3))
-        now += 2
-    e, _ = run_pair(engine, oracle_mod, seq)
+    e, _ = run_pair(engine, oracle_mod, sort_bucket_batches())
     if bucket in ("3000", "600"):
         assert e.cs.stats()["sort_big_buckets"] > 0  # the workgroup path ran
-
-
-def prefixed(pb, prefix):
-    """The same batch with `prefix` prepended to every key (order and overlaps unchanged)."""
-    lens = np.diff(pb.key_offsets)
-    parts = [np.frombuffer(prefix, np.uint8)]
-    out = []
-    for k in range(len(lens)):
-        out.append(parts[0])
-        out.append(pb.key_bytes[pb.key_offsets[k] : pb.key_offsets[k + 1]])
-    kb = np.concatenate(out) if out else np.zeros(0, np.uint8)
-    ko = np.concatenate([[0], np.cumsum(lens + len(prefix))]).astype(np.int64)
-    return PackedBatch(pb.read_snapshot, pb.report, pb.read_offsets, pb.write_offsets, kb, ko)
 
 
 def test_sequential_fallback_matches(engine, oracle_mod, monkeypatch):
     """Force the candidate-edge overflow path (sequential MiniConflictSet replay on the GPU)."""
     monkeypatch.setenv("FDBCS_EDGE_CAP", "8")
-    rng = np.random.default_rng(8)
-    seq = []
-    now = 10
-    for _ in range(4):
-        seq.append((W.random_small_batch(rng, 100, alphabet=2, max_len=3, now=now, staleness=10, report_frac=1.0),
-                    now, now - 3))
-        now += 2
-    run_pair(engine, oracle_mod, seq)
+    run_pair(engine, oracle_mod, sequential_fallback_batches())
 
 
 def test_full_size_c2_properties(engine, oracle_mod):
@@ -727,38 +699,20 @@ def test_empty_batches(engine, oracle_mod):
 
 # Every engine knob that selects a different kernel or submission path (DESIGN.md §5 "Engine knobs")
 # is parity-tested here; knobs measured slower and not kept were deleted with their code.
-@pytest.mark.parametrize("knobs", [{"FDBCS_SPLIT_CHECK": "1"}, {"FDBCS_SPLIT_CHECK": "0"},
-                                   {"FDBCS_SORT_COLD": "1"},
-                                   {"FDBCS_SUBMIT_THREAD": "0", "FDBCS_SPLIT_CHECK": "1"}, {"FDBCS_SUBMIT_THREAD": "0"},
-                                   {"FDBCS_WRITE_GROUPS": "0"}, {"FDBCS_SERIAL": "1"},
-                                   {"FDBCS_DIRECTORY": "0"}, {"FDBCS_SKIP_EDGES": "0"}])
+@pytest.mark.parametrize("knobs", PIPELINE_KNOBS)
 def test_pipeline_variants_match_oracle(engine, oracle_mod, knobs):
     """The engine's remaining path-selecting knobs stay exact: the unsplit and split read checks,
     cold-start splitters on every batch, one submitting thread, one candidate edge per writer (the
     production path past 12288 writes), the serial stream layout, base lookups without the radix
     directory, the no-edge launches kept."""
-    saved = {k: os.environ.get(k) for k in knobs}
-    os.environ.update(knobs)
-    try:
+    with knob_env(knobs):
         eng = EngineDriver(engine, gc_interval=0, delta_limit=400)  # compactions every few batches
-    finally:
-        for k, v in saved.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
     ora = oracle_mod.OracleConflictSet()
-    rng = np.random.default_rng(71)
-    now = 10
-    for i in range(20):
-        # keys up to 24 bytes (short-key lookups) and up to 40 (long-key lookups) in some batches
-        pb = W.random_small_batch(rng, 250, alphabet=6 if i % 2 else 200,
-                                  max_len=24 if i % 3 == 0 else (40 if i % 5 == 1 else 3), now=now, staleness=12)
-        ve, ce = eng.detect(pb, now, now - 9)
-        vo, co = ora.detect(pb, now, now - 9)
+    for pb, now, new_oldest in pipeline_variant_batches():
+        ve, ce = eng.detect(pb, now, new_oldest)
+        vo, co = ora.detect(pb, now, new_oldest)
         assert (ve == vo).all()
         assert ce == {t: sorted(v) for t, v in co.items()}
-        now += 4
     assert eng.cs.history_size() > 0
 
 
