@@ -156,6 +156,8 @@ SIGNATURES = {
                                               _VP, _I64, _VP, ctypes.c_uint32]),
     "fdbcs_batch_routed_info": (ctypes.c_int, [_VP, ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I32),
                                                ctypes.POINTER(_VP), ctypes.POINTER(_VP)]),
+    "fdbcs_batch_set_report_output": (ctypes.c_int, [_VP, _VP, _I64]),
+    "fdbcs_batch_report_entries": (ctypes.c_int, [_VP, _VP, _I32]),
     "fdbcs_debug_kernel_time": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
     "fdbcs_kernel_profile": (ctypes.c_int, [_VP, _I32, ctypes.c_char_p, _I32, ctypes.POINTER(_I64),
                                             ctypes.POINTER(ctypes.c_double)]),
@@ -578,6 +580,23 @@ class ConflictBatch:
         _check(load_library().fdbcs_batch_set_conflict_output(self._h, _VP(ids.ctypes.data if ids.size else 0),
                                                               int(n_global), _VP(dev_out)), "setConflictOutput")
 
+    def set_report_output(self, dev_out: int, n_global_reads: int) -> None:
+        """fdbcs_batch_set_report_output: on a routed batch created with a
+        conflicting_key_range_map, detect also writes the report bytes, one per read of the
+        concatenated shares (`n_global_reads` of them), into device memory `dev_out` (an address):
+        1 where this resolver's conflictingKeyRangeMap holds the read, for sharding.
+        combine_report_bytes / an all-reduce MAX."""
+        _check(load_library().fdbcs_batch_set_report_output(self._h, _VP(dev_out or None), int(n_global_reads)),
+               "setReportOutput")
+
+    def report_entries(self) -> np.ndarray:
+        """fdbcs_batch_report_entries: uint8 per transaction, 1 where the reference would have
+        created conflictingKeyRangeMap[t] (SkipList.cpp:770-784).  Valid after detect."""
+        n = len(self.verdicts) if self.verdicts is not None else self.transaction_count
+        out = np.zeros(n, np.uint8)
+        _check(load_library().fdbcs_batch_report_entries(self._h, _p(out), n), "reportEntries")
+        return out
+
     def get_too_old_transactions(self, too_old_transactions: List[int]) -> None:
         """GetTooOldTransactions (SkipList.cpp:836-842): appends the transactions whose add-time
         TooOld test held (SkipList.cpp:770); valid right after addTransaction, before detect."""
@@ -599,6 +618,14 @@ class ConflictBatch:
     def _collect_conflicting_keys(self) -> None:
         m = self.conflicting_key_range_map
         if m is None:
+            return
+        if getattr(self, "_routed", False):
+            # a routed batch's sub-transactions were placed on the device: the engine says which
+            # have an entry; the indices are the sub-transaction's own (this resolver's map)
+            for t in np.flatnonzero(self.report_entries()).tolist():
+                entry = m.setdefault(t, [])
+                if self.verdicts[t] == TransactionConflict:
+                    entry.extend(self.conflicting_reads(t))
             return
         # the reference creates (*conflictingKeyRangeMap)[t] while registering the read ranges of a
         # reporting, admitted transaction (SkipList.cpp:777-784): only transactions with reads get

@@ -437,6 +437,7 @@ struct BatchSlot {
     HBuf pin_inv;  // fdbcs_batch_set_conflict_output: global -> batch transaction map (host-mapped)
     // device routing (fdbcs_batch_add_routed): scan state, global -> batch map, read ids, totals
     DBuf rt_scan, rt_inv, rt_rids, rt_dres, rt_info, rt_txpre;
+    DBuf rt_gids;  // global read index of each kept read (reporting routed batches only)
     HBuf rt_res;
     hipEvent_t ev_rt0 = nullptr, ev_rt1 = nullptr;  // around the routing kernels
     bool rt_timed = false;
@@ -493,6 +494,14 @@ struct fdbcs_batch {
     bool routed = false, route_pending = false;
     int32_t rT = 0, rR = 0, rW = 0;
     size_t r_tail = 0;
+    int64_t r_global_R = 0;  // reads of all shares
+    // fdbcs_batch_set_report_output: device bytes per global read, written at detect
+    uint8_t* rep_dev = nullptr;
+    int64_t rep_n = 0;
+    // a routed reporting batch's roff [T+1] and flags [T], copied into the result buffer at detect
+    // (the wait-time report loop reads them; other batches read the host vectors above)
+    const int32_t* h_roff = nullptr;
+    const uint8_t* h_flags = nullptr;
 
     int32_t T() const { return routed ? rT : (int32_t)snap.size(); }
     int32_t R() const { return routed ? rR : roff.back(); }
@@ -979,6 +988,7 @@ void release_slot(BatchSlot* sl) {
     sl->rt_scan.release();
     sl->rt_inv.release();
     sl->rt_rids.release();
+    sl->rt_gids.release();
     sl->rt_dres.release();
     sl->rt_info.release();
     sl->rt_txpre.release();
@@ -1037,9 +1047,10 @@ inline void fast_prefix(const uint8_t* p, uint32_t len, uint64_t* hi, uint64_t* 
 }
 
 // Result buffer of a batch (host-mapped, written by the kernels): verdicts | scalars | completion
-// flag, then the report copies rconf | hist | first_conf.
+// flag, then the report copies rconf | hist | first_conf and, for a routed reporting batch (whose
+// transactions the host never saw), roff | flags.
 struct ResultLayout {
-    size_t sc, fl, rc, hc, fc, total;
+    size_t sc, fl, rc, hc, fc, ro, fg, total;
 };
 ResultLayout result_layout(size_t T, size_t R) {
     ResultLayout L;
@@ -1048,7 +1059,9 @@ ResultLayout result_layout(size_t T, size_t R) {
     L.rc = L.fl + 64;
     L.hc = align_up(L.rc + R + 1, 64);
     L.fc = align_up(L.hc + T + 1, 64);
-    L.total = L.fc + 4 * (T + 1);
+    L.ro = align_up(L.fc + 4 * (T + 1), 64);
+    L.fg = align_up(L.ro + 4 * (T + 1), 64);
+    L.total = L.fg + T + 1;
     return L;
 }
 
@@ -2475,7 +2488,13 @@ int fdbcs_batch_add_routed(fdbcs_batch* b, const void* shares, int64_t stride, i
     const int64_t n_elems = (int64_t)n_shares * max_share_txns;
     // ranges of one share: each takes 48 bytes of endpoint records, so the stride bounds them
     const int64_t rstride = std::max<int64_t>(1, (stride - (int64_t)sizeof(ShareHeader)) / (2 * (int64_t)sizeof(DKey)));
-    if ((rc = sl->rt_scan.ensure(8 * (size_t)route_scan_words(n_elems)))) return rc;
+    // a batch created with report_keys routes the shares' report flags too: a seventh scan counter
+    // and the global read index of each kept read (int32: bounded by the ranges the shares can hold)
+    const bool reports = b->report_enabled != 0;
+    if (reports && (int64_t)n_shares * rstride > INT32_MAX) return FDBCS_E_INVALID;
+    const size_t scan_bytes = 8 * (size_t)route_scan_words(n_elems, reports);
+    if ((rc = sl->rt_scan.ensure(scan_bytes))) return rc;
+    if (reports && (rc = sl->rt_gids.ensure(4 * ((size_t)cap_reads + 1)))) return rc;
     if ((rc = sl->rt_info.ensure(4 * (size_t)(n_shares * rstride)))) return rc;
     if ((rc = sl->rt_txpre.ensure(16 * (size_t)std::max<int64_t>(n_elems, 1)))) return rc;
     if ((rc = sl->rt_inv.ensure(4 * (size_t)std::max<int64_t>(n_elems, 1)))) return rc;
@@ -2491,7 +2510,7 @@ int fdbcs_batch_add_routed(fdbcs_batch* b, const void* shares, int64_t stride, i
     a.stride = stride;
     a.n_shares = n_shares;
     a.tcap = std::max(1, max_share_txns);
-    a.report_enabled = 0;  // conflicting-key reports go through the host-routed path (sharding.py)
+    a.report_enabled = reports ? 1 : 0;
     a.cap_T = cap_txns;
     a.cap_R = cap_reads;
     a.cap_W = cap_writes;
@@ -2510,6 +2529,7 @@ int fdbcs_batch_add_routed(fdbcs_batch* b, const void* shares, int64_t stride, i
     a.inv = (int32_t*)sl->rt_inv.p;
     a.inv_n = std::max<int64_t>(n_elems, 1);
     a.read_ids = (int32_t*)sl->rt_rids.p;
+    a.read_gids = reports ? (int32_t*)sl->rt_gids.p : nullptr;
     a.out_zero = conflict_out;
     a.out_n = n_global;
     a.res = (RouteResult*)sl->rt_res.dp;
@@ -2522,7 +2542,7 @@ int fdbcs_batch_add_routed(fdbcs_batch* b, const void* shares, int64_t stride, i
     a.ready_value = ready_value;
     a.wait_ticks = (uint64_t)cs->route_timeout_ms * 100000ull;  // 100 MHz wall clock
     a.wait_err = (uint32_t*)((uint64_t*)sl->rt_scan.p + 2);
-    HIPOK(hipMemsetAsync(sl->rt_scan.p, 0, 8 * (size_t)route_scan_words(n_elems), us));
+    HIPOK(hipMemsetAsync(sl->rt_scan.p, 0, scan_bytes, us));
     // global indices past the shares' transactions stay "not routed here"
     HIPOK(hipMemsetAsync(sl->rt_inv.p, 0xFF, 4 * (size_t)a.inv_n, us));
     uint64_t* sw = (uint64_t*)sl->rt_scan.p;
@@ -2549,6 +2569,8 @@ int fdbcs_batch_add_routed(fdbcs_batch* b, const void* shares, int64_t stride, i
     b->out_dev = conflict_out;
     b->out_n = n_global;
     b->out_ids.clear();
+    b->rep_dev = nullptr;
+    b->rep_n = 0;
     b->state = 1;
     return FDBCS_OK;
 }
@@ -2570,6 +2592,8 @@ static int finish_route(fdbcs_batch* b) {
         b->routed = b->route_pending = false;
         b->out_dev = nullptr;
         b->out_n = 0;
+        b->rep_dev = nullptr;
+        b->rep_n = 0;
         b->state = 0;
         return r.error == 2 ? FDBCS_E_TIMEOUT
                             : r.error == 1 ? FDBCS_E_NOMEM : r.error == 3 ? FDBCS_E_INVALID : FDBCS_E_DEVICE;
@@ -2588,6 +2612,7 @@ static int finish_route(fdbcs_batch* b) {
     b->wtail = r.tail_bytes + 14 * (int64_t)r.W;
     b->max_len = r.n_gt24 ? 25 : (r.n_gt19 ? 20 : 16);
     b->any_report = r.reports > 0;
+    b->r_global_R = r.global_R;
     b->route_pending = false;
     return FDBCS_OK;
 }
@@ -2628,6 +2653,15 @@ int fdbcs_batch_detect_async(fdbcs_batch* b, int64_t now, int64_t new_oldest_ver
     HIPOK(hipSetDevice(cs->device));
     if (now < cs->max_written) return FDBCS_E_VERSION;
     if (int rc0 = finish_route(b)) return rc0;  // a routed batch's sizes (its route ran ahead)
+    if (b->routed && b->rep_dev && b->rep_n != b->r_global_R) {
+        // report bytes for every read of the shares, no more and no fewer (like the conflict
+        // output's size, error 3 of the routing): the batch is empty again, to be routed anew
+        b->routed = false;
+        b->out_dev = b->rep_dev = nullptr;
+        b->out_n = b->rep_n = 0;
+        b->state = 0;
+        return FDBCS_E_INVALID;
+    }
     if (b->T() > kMaxTxnLds) return FDBCS_E_INVALID;
     // tail offsets are 32-bit: refuse a batch that could overflow the arena (GC repacks it long before)
     // history tail bytes this batch can append (each inserted tail padded to 8 bytes)
@@ -2664,6 +2698,8 @@ int fdbcs_batch_detect_async(fdbcs_batch* b, int64_t now, int64_t new_oldest_ver
     b->h_rconf = (uint8_t*)(ho + o_rc);
     b->h_hist = (uint8_t*)(ho + o_hc);
     b->h_first = (int32_t*)(ho + o_fc);
+    b->h_roff = b->routed ? (const int32_t*)(ho + RL.ro) : b->roff.data();
+    b->h_flags = b->routed ? (const uint8_t*)(ho + RL.fg) : b->flags.data();
     if ((rc = sl->dverdict.ensure(T + 64))) return rc;
     if (b->out_dev && b->out_n > 0 && !b->routed) {
         // global -> batch transaction map, read by k_conflict_output straight from host-mapped
@@ -2888,7 +2924,15 @@ int fdbcs_batch_detect_async(fdbcs_batch* b, int64_t now, int64_t new_oldest_ver
         if (R) launch_copy_bytes(s, hdv + o_rc, w.rconf, R);
         launch_copy_bytes(s, hdv + o_hc, w.hist_conf, T);
         launch_copy_bytes(s, hdv + o_fc, w.first_conf, 4 * T);
+        if (b->routed) {  // the report loop's roff and flags (TooOld included: stage A is done)
+            launch_copy_bytes(s, hdv + RL.ro, bd.roff, 4 * (T + 1));
+            launch_copy_bytes(s, hdv + RL.fg, bd.flags, T);
+        }
     }
+    // the multi-resolver report input (zeros when no sub-transaction reports); history conflicts
+    // are reported without candidate edges too, so outside the resolution's skip group
+    if (b->routed && b->rep_dev && b->rep_n > 0)
+        launch_report_bytes(s, bd, w, (const int32_t*)sl->rt_gids.p, b->rep_n, b->rep_dev);
     mark(kPhIntra);
     mark(kPhCombine);
     // ---- half Y: D.MergeWrite, compaction / GC, epilogue, after X
@@ -3138,11 +3182,14 @@ int fdbcs_batch_wait(fdbcs_batch* b, uint8_t* verdicts, int32_t* n_committed, in
         b->conf_off.assign(T + 1, 0);
         b->conf_idx.clear();
         if (b->any_report) {
+            // (a routed batch: the sub-transaction's own indexInTx, as the resolver's map holds it)
+            const int32_t* roff = b->h_roff;
+            const uint8_t* flags = b->h_flags;
             for (int32_t t = 0; t < T; t++) {
-                if ((b->flags[t] & kFlagReport) && b->h_verdict[t] == FDBCS_TRANSACTION_CONFLICT) {
+                if ((flags[t] & kFlagReport) && b->h_verdict[t] == FDBCS_TRANSACTION_CONFLICT) {
                     if (b->h_hist[t]) {
-                        for (int32_t r = b->roff[t]; r < b->roff[t + 1]; r++)
-                            if (b->h_rconf[r]) b->conf_idx.push_back(r - b->roff[t]);
+                        for (int32_t r = roff[t]; r < roff[t + 1]; r++)
+                            if (b->h_rconf[r]) b->conf_idx.push_back(r - roff[t]);
                     } else if (b->h_first[t] != INT_MAX) {
                         b->conf_idx.push_back(b->h_first[t]);
                     }
@@ -3308,6 +3355,27 @@ int fdbcs_batch_set_conflict_output(fdbcs_batch* b, const int32_t* txn_ids, int3
     b->out_ids.assign(txn_ids, txn_ids + T);
     b->out_n = n_global;
     b->out_dev = dev_out;
+    return FDBCS_OK;
+}
+
+int fdbcs_batch_set_report_output(fdbcs_batch* b, uint8_t* dev_out, int64_t n_global_reads) {
+    if (!b || !dev_out || n_global_reads < 0) return FDBCS_E_INVALID;
+    if (!b->cs || !b->routed || !b->report_enabled || b->state >= 2) return FDBCS_E_STATE;
+    // the size is compared with the shares' reads at detect, once the routing kernels have run
+    b->rep_dev = dev_out;
+    b->rep_n = n_global_reads;
+    return FDBCS_OK;
+}
+
+int fdbcs_batch_report_entries(fdbcs_batch* b, uint8_t* entry_out, int32_t cap) {
+    if (!b || cap < 0 || (cap > 0 && !entry_out)) return FDBCS_E_INVALID;
+    if (b->state != 3) return FDBCS_E_STATE;
+    // conflictingKeyRangeMap[t] exists iff addTransaction registered a read range of a reporting,
+    // admitted (not TooOld) transaction (SkipList.cpp:770-784)
+    const int32_t n = std::min(cap, b->T());
+    for (int32_t t = 0; t < n; t++)
+        entry_out[t] = b->any_report && (b->h_flags[t] & kFlagReport) && b->h_roff[t + 1] > b->h_roff[t] &&
+                       b->h_verdict[t] != FDBCS_TRANSACTION_TOO_OLD;
     return FDBCS_OK;
 }
 

@@ -333,6 +333,7 @@ struct RouteResult {
                              // shares' ready flag was never set; 3: conflict output size != global T
     int32_t pad;
     int64_t global_T;        // transactions of all shares
+    int64_t global_R;        // reads of all shares (the size of a report output)
 };
 struct RouteArgs {
     const uint8_t* shares;  // n_shares shares, `stride` bytes apart
@@ -341,7 +342,8 @@ struct RouteArgs {
     int32_t has_lo, has_hi;  // this resolver owns [lo, hi): lo absent for the first, hi for the last
     DKey lo, hi;
     const uint8_t* btail;    // tails of lo / hi
-    int32_t report_enabled;
+    int32_t report_enabled;  // the batch collects conflicting-key reports: a placed sub-transaction
+                             // copies its share's report flag (CommitProxyServer.actor.cpp:181-186)
     int32_t cap_T, cap_R, cap_W;  // capacity of the output layout
     int64_t cap_tail;
     // outputs: the routed batch at capacity offsets of the upload layout
@@ -356,6 +358,8 @@ struct RouteArgs {
     int32_t* inv;       // [inv_n] batch index of each global transaction, -1 if not routed here
     int64_t inv_n;      // n_shares * tcap (every global index fits)
     int32_t* read_ids;  // [R'] index of each kept read in its transaction (txReadConflictRangeIndexMap)
+    int32_t* read_gids; // [R'] index of each kept read among the reads of the concatenated shares
+                        // (reporting batches only, else null)
     uint8_t* out_zero;  // conflict output to zero for this batch (or null), out_n global transactions
     int64_t out_n;
     RouteResult* res;   // host-mapped
@@ -368,7 +372,8 @@ struct RouteArgs {
 // Route the all-gathered shares into this resolver's batch (two launches on `s`).  grid_n: bound
 // on n_shares * tcap (global elements); the scan state's granules are zeroed by the caller.
 void launch_route(hipStream_t s, const RouteArgs& a, ScanState st);
-int64_t route_scan_words(int64_t n_elems);
+// reports: the scan of a reporting batch (RouteArgs::report_enabled) carries a seventh counter
+int64_t route_scan_words(int64_t n_elems, bool reports = false);
 // TooOld (SkipList.cpp:770) of a routed batch against the oldest version at detect time.
 void launch_route_too_old(hipStream_t s, const BatchDev& b, int64_t oldest);
 
@@ -444,6 +449,10 @@ void init_kernel_attributes();
 // Byte copy (device -> host-mapped result buffer), as a kernel.
 void launch_copy_bytes(hipStream_t s, void* dst, const void* src, int64_t n);
 // Multi-resolver conflict bytes out[g] = 2 - verdict of batch transaction inv[g] (0 if inv[g] < 0).
+// Report bytes of a routed batch (fdbcs_batch_set_report_output): out[0, n) zeroed, then 1 at
+// gid[r] of every routed read r the resolver's conflictingKeyRangeMap would hold.  After the
+// resolution (and k_intra_report), before the epilogue re-zeroes hist_conf and rconf.
+void launch_report_bytes(hipStream_t s, const BatchDev& b, const Work& w, const int32_t* gid, int64_t n, uint8_t* out);
 void launch_conflict_output(hipStream_t s, const BatchDev& b, const Work& w, const int32_t* inv, int64_t n,
                             uint8_t* out);
 int64_t scan_arena_words(int64_t T, int64_t R, int64_t W, int64_t hist_cap, int64_t delta_cap);

@@ -3796,6 +3796,7 @@ __global__ __launch_bounds__(kBlock) void k_route_mark(RouteArgs a) {
 // One element per transaction of every share (element i = share i / tcap, transaction i % tcap;
 // past the share's T: padding): what this resolver keeps of it, as counts; the store places the
 // sub-transaction and leaves its prefixes for k_route_write.
+template <int K>
 struct RouteScan {
     RouteArgs a;
     __device__ const ShareHeader* at(int64_t i, int& p, int& t, int64_t& gid) const {
@@ -3809,7 +3810,7 @@ struct RouteScan {
         return h;
     }
     // counts: sub-transaction, kept reads, kept writes, kept tail bytes, ranges with a key > 19 / > 24 bytes
-    __device__ bool visit(int64_t i, uint32_t (&v)[6], bool& any, int& p, int& t, int64_t& gid,
+    __device__ bool visit(int64_t i, uint32_t (&v)[K], bool& any, int& p, int& t, int64_t& gid,
                           const ShareHeader*& h) const {
         h = at(i, p, t, gid);
         if (!h) return false;
@@ -3843,17 +3844,18 @@ struct RouteScan {
         v[3] = tl;
         v[4] = g19;
         v[5] = g24;
+        if constexpr (K > 6) v[6] = (base + h->off_report)[t] ? 1u : 0u;  // a reporting sub-transaction
         return true;
     }
-    __device__ void load(int64_t i, uint32_t (&v)[6]) const {
+    __device__ void load(int64_t i, uint32_t (&v)[K]) const {
         bool any;
         int p, t;
         int64_t gid;
         const ShareHeader* h;
         visit(i, v, any, p, t, gid, h);
     }
-    __device__ void store(int64_t i, const uint32_t (&ex)[6]) const {
-        uint32_t v[6] = {0, 0, 0, 0, 0, 0};
+    __device__ void store(int64_t i, const uint32_t (&ex)[K]) const {
+        uint32_t v[K] = {};
         bool any;
         int p, t;
         int64_t gid;
@@ -3867,15 +3869,23 @@ struct RouteScan {
         if (!fits) return;
         const uint8_t* base = (const uint8_t*)h;
         a.snap[lt] = ((const int64_t*)(base + h->off_snap))[t];
-        a.flags[lt] = 0;  // TooOld is decided when the batch is detected (k_route_too_old)
+        // the share's report flag (CommitProxyServer.actor.cpp:181-186) when the batch collects
+        // reports; TooOld is decided when the batch is detected (k_route_too_old ORs it in)
+        uint8_t fl = 0;
+        if constexpr (K > 6) fl = v[6] ? kFlagReport : 0;
+        a.flags[lt] = fl;
         a.roff[lt] = (int32_t)ex[1];
         a.woff[lt] = (int32_t)ex[2];
     }
-    __device__ void finish(const uint32_t (&tot)[6]) const {
+    __device__ void finish(const uint32_t (&tot)[K]) const {
         RouteResult r{};
         if (!*a.wait_err)
-            for (int q = 0; q < a.n_shares; q++) r.global_T += share_at(a, q)->T;
+            for (int q = 0; q < a.n_shares; q++) {
+                r.global_T += share_at(a, q)->T;
+                r.global_R += share_at(a, q)->R;
+            }
         r.T = (int32_t)tot[0];
+        if constexpr (K > 6) r.reports = (int32_t)tot[6];
         r.R = (int32_t)tot[1];
         r.W = (int32_t)tot[2];
         r.tail_bytes = tot[3];
@@ -3930,6 +3940,11 @@ __global__ __launch_bounds__(kBlock) void k_route_write(RouteArgs a) {
     if (is_read) {
         a.rown[pre.y + rank] = pre.x;
         if (a.read_ids) a.read_ids[pre.y + rank] = j - roff[t];
+        if (a.read_gids) {  // read j of share p among the reads of the concatenated shares
+            int32_t g = j;
+            for (int q = 0; q < p; q++) g += share_at(a, q)->R;
+            a.read_gids[pre.y + rank] = g;
+        }
     } else {
         a.wown[pre.z + rank] = pre.x;
     }
@@ -3965,13 +3980,19 @@ void launch_route_too_old(hipStream_t s, const BatchDev& b, int64_t oldest) {
     fdb_launch(k_route_too_old, dim3((unsigned)((b.T + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, b, oldest);
 }
 
-int64_t route_scan_words(int64_t n_elems) { return 8 + scan_granules(n_elems, 6, kRouteScanP); }
+int64_t route_scan_words(int64_t n_elems, bool reports) {
+    return 8 + scan_granules(n_elems, reports ? 7 : 6, kRouteScanP);
+}
 
 void launch_route(hipStream_t s, const RouteArgs& a, ScanState st) {
     const dim3 grid((unsigned)std::max<int64_t>(1, (a.rstride + kBlock - 1) / kBlock), (unsigned)a.n_shares);
     fdb_launch(k_route_wait, dim3(1), dim3(64), 0, s, a.ready, a.ready_value, a.wait_err, a.wait_ticks);
     fdb_launch(k_route_mark, grid, dim3(kBlock), 0, s, a);
-    launch_scan<6, kRouteScanP>(s, RouteScan{a}, nullptr, (int64_t)a.n_shares * a.tcap, st);
+    // a reporting batch counts its reporting sub-transactions with a seventh component
+    if (a.report_enabled)
+        launch_scan<7, kRouteScanP>(s, RouteScan<7>{a}, nullptr, (int64_t)a.n_shares * a.tcap, st);
+    else
+        launch_scan<6, kRouteScanP>(s, RouteScan<6>{a}, nullptr, (int64_t)a.n_shares * a.tcap, st);
     fdb_launch(k_route_write, grid, dim3(kBlock), 0, s, a);
 }
 
@@ -4242,6 +4263,47 @@ void launch_conflict_output(hipStream_t s, const BatchDev& b, const Work& w, con
     blocks = blocks > 1024 ? 1024 : blocks;
     fdb_launch(k_conflict_output, dim3((unsigned)blocks), dim3(kBlock), 0, s, b, (const uint8_t*)w.status, inv, n,
                out);
+}
+
+// Multi-resolver report input (fdbcs_batch_set_report_output), the analogue of the conflict bytes
+// for conflictingKeyRangeMap: out[gid[r]] = 1 for every routed read r this resolver's map would
+// hold for a reporting sub-transaction t it judged Conflict: every conflicting read of a history
+// conflict (SkipList.cpp:641-645), the first of an intra-batch conflict (:821-828, k_intra_report's
+// first_conf; INT_MAX, which no read index equals, when there is none).  A TooOld sub-transaction
+// reports nothing (:770-784), whatever its status byte.  out[0, n) is zeroed by the launch before
+// (k_zero_bytes), so reads not routed here hold 0; each routed read owns its byte, so plain stores
+// suffice.  An element-wise MAX all-reduce over the resolvers is the set of the proxy's
+// conflictingKRIndices (CommitProxyServer.actor.cpp:1243-1261).
+__global__ __launch_bounds__(kBlock) void k_zero_bytes(uint8_t* __restrict__ out, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        out[i] = 0;
+}
+
+__global__ __launch_bounds__(kBlock) void k_report_bytes(BatchDev b, const uint8_t* __restrict__ status,
+                                                         const uint8_t* __restrict__ hist_conf,
+                                                         const uint8_t* __restrict__ rconf,
+                                                         const int32_t* __restrict__ first_conf,
+                                                         const int32_t* __restrict__ gid, int64_t n,
+                                                         uint8_t* __restrict__ out) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= b.R) return;
+    const int64_t g = gid[r];
+    if (g < 0 || g >= n) return;
+    const int t = b.rowner[r];
+    if (!(b.flags[t] & kFlagReport) || verdict_byte(b, t, status[t]) != 0) return;
+    const bool hit = hist_conf[t] ? rconf[r] != 0 : first_conf[t] == r - b.roff[t];
+    if (hit) out[g] = 1;
+}
+
+void launch_report_bytes(hipStream_t s, const BatchDev& b, const Work& w, const int32_t* gid, int64_t n, uint8_t* out) {
+    if (n <= 0) return;
+    int64_t blocks = (n + kBlock - 1) / kBlock;
+    blocks = blocks > 1024 ? 1024 : blocks;
+    fdb_launch(k_zero_bytes, dim3((unsigned)blocks), dim3(kBlock), 0, s, out, n);
+    if (b.R <= 0) return;
+    fdb_launch(k_report_bytes, dim3((unsigned)((b.R + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, b,
+               (const uint8_t*)w.status, (const uint8_t*)w.hist_conf, (const uint8_t*)w.rconf,
+               (const int32_t*)w.first_conf, gid, n, out);
 }
 
 // fdbcs_debug_hold: holds a stream until the host writes the release word (host-mapped), so batches

@@ -22,6 +22,8 @@ Restates the commit proxy's multi-resolver routing (fdbserver/CommitProxyServer.
 * conflicting-key reports: for a reporting transaction that did not commit, the proxy concatenates
   each resolver's reported read indices, resolvers in ascending order, mapped back to the
   transaction's own read indices through txReadConflictRangeIndexMap (:144-165, :1243-1261).
+  On GPUs each resolver writes a byte per read of the global batch (``report_bytes``) and an
+  all-reduce MAX (``combine_report_bytes``) holds the sorted set of that list.
 
 ``KeyRangeSharding`` is the static split (no version history) with a vectorized fast path for
 one-byte split keys; both produce the same ``ShardBatch`` form.
@@ -187,6 +189,36 @@ def combine_conflicting_keys(pb: PackedBatch, shards: List[ShardBatch], maps: Li
                 idx.append(int(s.read_ids[r0 + int(i)]))
         out[t] = idx
     return out
+
+
+def report_bytes(pb: PackedBatch, shard: ShardBatch, conf_map: Dict[int, Sequence[int]]) -> np.ndarray:
+    """One resolver's conflicting-key reports as bytes over the batch's reads, the analogue of
+    ``conflict_bytes`` (the host restatement of fdbcs_batch_set_report_output): 1 at the global read
+    index (position in ``pb``'s reads, i.e. in the concatenated shares) of every read index the
+    resolver's conflictingKeyRangeMap ``conf_map`` holds (sub-transaction -> local read indices;
+    the reference fills an entry only for a sub-transaction it judged Conflict), 0 elsewhere."""
+    out = np.zeros(pb.n_reads, np.uint8)
+    sub = shard.batch
+    for lt, idx in conf_map.items():
+        if not len(idx):
+            continue
+        r0 = int(sub.read_offsets[lt])
+        g0 = int(pb.read_offsets[int(shard.txn_ids[lt])])
+        out[g0 + shard.read_ids[r0 + np.asarray(idx, np.int64)]] = 1
+    return out
+
+
+def combine_report_bytes(pb: PackedBatch, shards: List[ShardBatch],
+                         maps: List[Dict[int, Sequence[int]]]) -> np.ndarray:
+    """Element-wise max of the resolvers' report bytes (an all-reduce MAX on GPUs).  Per
+    transaction, the set positions are the sorted set of the proxy's conflictingKRIndices
+    (``combine_conflicting_keys``): a resolver reports only sub-transactions it judged Conflict,
+    so a transaction has ones iff some resolver conflicted, which is when the proxy reports it.
+    The proxy's list holds an index twice when a read spans a split key and both owners report it."""
+    c = np.zeros(pb.n_reads, np.uint8)
+    for s, m in zip(shards, maps):
+        np.maximum(c, report_bytes(pb, s, m), out=c)
+    return c
 
 
 # ---------------------------------------------------------------- static split

@@ -266,7 +266,9 @@ int fdbcs_batch_detect_conflicts(fdbcs_batch* b, int64_t now, int64_t new_oldest
 int fdbcs_batch_detect_async(fdbcs_batch* b, int64_t now, int64_t new_oldest_version);
 int fdbcs_batch_wait(fdbcs_batch* b, uint8_t* verdicts, int32_t* n_committed, int32_t* n_too_old);
 /* conflictingKeyRangeMap[txn] (SkipList.cpp:641-645, 822-825): read-range
- * indices (indexInTx) that conflicted, ascending.  Valid after detect. */
+ * indices (indexInTx) that conflicted, ascending.  Valid after detect.  On a routed batch
+ * (fdbcs_batch_add_routed, created with report_keys) txn is the sub-transaction and the indices
+ * are its own, as this resolver's map holds them. */
 int fdbcs_batch_conflicting_reads(fdbcs_batch* b, int32_t txn, int32_t* idx_out, int32_t cap,
                                   int32_t* n_out);
 /* ConflictBatch::GetTooOldTransactions (SkipList.cpp:836-842): indices of the transactions added
@@ -308,8 +310,13 @@ int fdbcs_batch_set_conflict_output(fdbcs_batch* b, const int32_t* txn_ids, int3
  *     routed batch, TooOld sub-transactions' ranges included (FDBCS_E_NOMEM at detect if passed).
  *     conflict_out (optional, n_global bytes of device memory, n_global = the transactions of all
  *     shares, FDBCS_E_INVALID at detect otherwise): as fdbcs_batch_set_conflict_output, with the
- *     global index of a sub-transaction = its position in the concatenated shares.  Conflicting-key
- *     reports are not collected for routed batches.  Detect and wait as for any batch; detect
+ *     global index of a sub-transaction = its position in the concatenated shares.  A batch
+ *     created with report_keys copies each share's report flag to its sub-transaction (:181-186);
+ *     after detect, fdbcs_batch_conflicting_reads returns the sub-transaction's own indexInTx (what
+ *     this resolver's conflictingKeyRangeMap holds; the read-id view below maps it back to the
+ *     transaction's index), fdbcs_batch_report_entries which sub-transactions have a map entry, and
+ *     fdbcs_batch_set_report_output makes detect write the reports as device bytes.  A batch
+ *     created without report_keys collects none and pays nothing.  Detect and wait as for any batch; detect
  *     blocks until the routing kernels have run (issue the next batch's routing first).  The wait
  *     for the ready flag is bounded by FDBCS_ROUTE_TIMEOUT_MS (default 60000): past it detect
  *     returns FDBCS_E_TIMEOUT and the batch is empty again, to be routed anew.  The capacity
@@ -326,6 +333,28 @@ int fdbcs_batch_add_routed(fdbcs_batch* b, const void* shares, int64_t stride, i
                            uint32_t ready_value);
 int fdbcs_batch_routed_info(fdbcs_batch* b, int32_t* n_txn, int32_t* n_reads, int32_t* n_writes, void** inv_dev,
                             void** read_ids_dev);
+/* Routed batches only, after fdbcs_batch_add_routed and before detect.  Detect then also writes
+ * dev_out[0, n_global_reads) (device memory of this GPU, any allocator): 1 at the global read
+ * index of every read this resolver's conflictingKeyRangeMap would hold (every conflicting read
+ * of a history conflict, SkipList.cpp:641-645; the first of an intra-batch conflict, :821-828)
+ * for a reporting sub-transaction whose verdict here is Conflict, 0 everywhere else, complete
+ * when the batch is.  The global read index of read j of share p is its position among the reads
+ * of the concatenated shares, sum of the earlier shares' reads + j.  An element-wise MAX
+ * all-reduce over the resolvers is the set of the proxy's conflictingKRIndices
+ * (CommitProxyServer.actor.cpp:1243-1261): the proxy's list holds an index twice when a read spans
+ * a split key and both owners report it; the bytes are the sorted set of that list.  A resolver
+ * writes ones only for sub-transactions it judged Conflict, so after the MAX a transaction has
+ * ones iff some resolver conflicted, which is when the proxy reports it.
+ * FDBCS_E_STATE on a batch that is not routed, was created without report_keys, or has been
+ * detected; FDBCS_E_INVALID for a NULL handle or pointer or a negative size.  n_global_reads
+ * differing from the reads of all shares is found at detect: FDBCS_E_INVALID, and the batch is
+ * empty again, to be routed anew. */
+int fdbcs_batch_set_report_output(fdbcs_batch* b, uint8_t* dev_out, int64_t n_global_reads);
+/* Valid after detect, for any batch: entry_out[t] = 1 iff the reference would have created
+ * conflictingKeyRangeMap[t] (report flag set, at least one read range, not TooOld:
+ * SkipList.cpp:770-784), for the first min(cap, transactions) transactions.  A routed batch's
+ * caller never saw its sub-transactions and learns the map's keys here. */
+int fdbcs_batch_report_entries(fdbcs_batch* b, uint8_t* entry_out, int32_t cap);
 
 /* Diagnostics (tuning, not part of the ConflictSet contract): average device time of one launch
  * of a pipeline kernel over `reps` back-to-back launches on the uploaded batch `b` against the
