@@ -105,6 +105,18 @@ class Stats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class _CKeyResolvers(ctypes.Structure):
+    """fdbcs_key_resolvers."""
+    _fields_ = [
+        ("n_ranges", ctypes.c_int32),
+        ("bound_bytes", ctypes.c_void_p),
+        ("bound_offsets", ctypes.c_void_p),
+        ("hist_offsets", ctypes.c_void_p),
+        ("hist_versions", ctypes.c_void_p),
+        ("hist_resolvers", ctypes.c_void_p),
+    ]
+
+
 # C-ABI symbol table: name -> (restype, argtypes).  tests/ check that the library exports
 # every function include/fdb_conflict_set.h declares.
 _VP, _I32, _I64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
@@ -156,6 +168,9 @@ SIGNATURES = {
                                               _VP, _I64, _VP, ctypes.c_uint32]),
     "fdbcs_batch_routed_info": (ctypes.c_int, [_VP, ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I32),
                                                ctypes.POINTER(_VP), ctypes.POINTER(_VP)]),
+    "fdbcs_route_map_pack": (ctypes.c_int, [ctypes.POINTER(_CKeyResolvers), _I32, _VP, _VP]),
+    "fdbcs_batch_add_routed_map": (ctypes.c_int, [_VP, _VP, _I64, _I32, _I32, ctypes.POINTER(_CKeyResolvers), _I32,
+                                                  _I32, _I32, _I32, _I64, _VP, _I64, _VP, ctypes.c_uint32]),
     "fdbcs_batch_set_report_output": (ctypes.c_int, [_VP, _VP, _I64]),
     "fdbcs_batch_report_entries": (ctypes.c_int, [_VP, _VP, _I32]),
     "fdbcs_debug_kernel_time": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
@@ -199,6 +214,32 @@ def share_pack(pb: PackedBatch, out: Optional[np.ndarray] = None) -> np.ndarray:
     used = _I64()
     _check(L.fdbcs_share_pack(ctypes.byref(cs), _VP(out.ctypes.data), out.nbytes, ctypes.byref(used)), "sharePack")
     return out[: used.value]
+
+
+def _key_resolvers_struct(kr):
+    """(fdbcs_key_resolvers, the arrays it points into) of a sharding.KeyResolvers, or of a dict
+    holding the arrays of its flat() form."""
+    f = kr.flat() if hasattr(kr, "flat") else kr
+    arrs = [np.ascontiguousarray(f["bound_bytes"], np.uint8), np.ascontiguousarray(f["bound_offsets"], np.int64),
+            np.ascontiguousarray(f["hist_offsets"], np.int64), np.ascontiguousarray(f["hist_versions"], np.int64),
+            np.ascontiguousarray(f["hist_resolvers"], np.int32)]
+    c = _CKeyResolvers(int(f.get("n_ranges", len(arrs[1]) - 1)), *[a.ctypes.data for a in arrs])
+    return c, arrs
+
+
+def route_map_pack(kr, resolver: int) -> Tuple[np.ndarray, np.ndarray]:
+    """fdbcs_route_map_pack (host only): (own uint8[M], until int64[M]) of the keyResolvers map `kr`
+    for one resolver.  own bit 0: the newest owner of the range; bit 1: in an older history entry,
+    and then a read at snapshot s still goes to it iff until >= s."""
+    c, keep = _key_resolvers_struct(kr)
+    n = max(int(c.n_ranges), 0)
+    own = np.zeros(n, np.uint8)
+    until = np.zeros(n, np.int64)
+    rc = load_library().fdbcs_route_map_pack(ctypes.byref(c), int(resolver), _VP(own.ctypes.data), _VP(until.ctypes.data))
+    if rc != FDBCS_OK:
+        raise FdbcsError(rc, "routeMapPack")
+    del keep
+    return own, until
 
 
 def strerror(status: int) -> str:
@@ -520,6 +561,24 @@ class ConflictBatch:
             len(lo_b) if lo is not None else -1, ctypes.cast(hi_buf, _VP), len(hi_b) if hi is not None else -1,
             int(caps[0]), int(caps[1]), int(caps[2]), int(caps[3]), _VP(conflict_out or None), int(n_global),
             _VP(ready_ptr or None), int(ready_value) & 0xFFFFFFFF), "addRouted")
+        self._routed = True
+
+    def add_routed_map(self, shares_ptr: int, stride: int, n_shares: int, max_share_txns: int, key_resolvers,
+                       resolver: int, caps: Tuple[int, int, int, int], conflict_out: int = 0, n_global: int = 0,
+                       ready_ptr: int = 0, ready_value: int = 0) -> None:
+        """fdbcs_batch_add_routed_map: add_routed under a keyResolvers map with its ownership history
+        (a sharding.KeyResolvers, or the arrays of its flat() form) instead of a static [lo, hi):
+        this batch is routed as resolver `resolver` of that map.  The map is read during the call
+        and travels with the batch, so the next batch may pass another one.  Any error status,
+        FDBCS_E_INVALID of an invalid map included, raises FdbcsError."""
+        c, keep = _key_resolvers_struct(key_resolvers)
+        rc = load_library().fdbcs_batch_add_routed_map(
+            self._h, _VP(shares_ptr), int(stride), int(n_shares), int(max_share_txns), ctypes.byref(c), int(resolver),
+            int(caps[0]), int(caps[1]), int(caps[2]), int(caps[3]), _VP(conflict_out or None), int(n_global),
+            _VP(ready_ptr or None), int(ready_value) & 0xFFFFFFFF)
+        del keep
+        if rc != FDBCS_OK:
+            raise FdbcsError(rc, "routedMap")
         self._routed = True
 
     def routed_info(self) -> Tuple[int, int, int, int, int]:

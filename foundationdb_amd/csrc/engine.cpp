@@ -438,6 +438,10 @@ struct BatchSlot {
     // device routing (fdbcs_batch_add_routed): scan state, global -> batch map, read ids, totals
     DBuf rt_scan, rt_inv, rt_rids, rt_dres, rt_info, rt_txpre;
     DBuf rt_gids;  // global read index of each kept read (reporting routed batches only)
+    // fdbcs_batch_add_routed_map: the keyResolvers map the batch is routed under (route_map_layout)
+    // and the pinned staging it is copied from
+    DBuf rt_map;
+    HBuf rt_map_pin;
     HBuf rt_res;
     hipEvent_t ev_rt0 = nullptr, ev_rt1 = nullptr;  // around the routing kernels
     bool rt_timed = false;
@@ -989,6 +993,8 @@ void release_slot(BatchSlot* sl) {
     sl->rt_inv.release();
     sl->rt_rids.release();
     sl->rt_gids.release();
+    sl->rt_map.release();
+    sl->rt_map_pin.release();
     sl->rt_dres.release();
     sl->rt_info.release();
     sl->rt_txpre.release();
@@ -2434,10 +2440,101 @@ int fdbcs_share_pack(const fdbcs_packed_batch* pb, void* out, int64_t cap, int64
     return FDBCS_OK;
 }
 
-int fdbcs_batch_add_routed(fdbcs_batch* b, const void* shares, int64_t stride, int32_t n_shares, int32_t max_share_txns,
-                           const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key, int32_t hi_len, int32_t cap_txns,
-                           int32_t cap_reads, int32_t cap_writes, int64_t cap_tail, uint8_t* conflict_out,
-                           int64_t n_global, const uint32_t* ready_flag, uint32_t ready_value) {
+// ---- keyResolvers maps (fdbcs_route_map_pack, fdbcs_batch_add_routed_map)
+
+// The map's own validity (the header's list) and the resolver id.
+static int route_map_check(const fdbcs_key_resolvers* m, int32_t resolver) {
+    if (!m || resolver < 0 || m->n_ranges < 1 || m->n_ranges > kRouteMapMaxRanges || !m->bound_offsets ||
+        !m->hist_offsets || !m->hist_versions || !m->hist_resolvers)
+        return FDBCS_E_INVALID;
+    const int32_t M = m->n_ranges;
+    const int64_t *bo = m->bound_offsets, *ho = m->hist_offsets;
+    if (bo[0] < 0 || bo[1] != bo[0] || ho[0] < 0) return FDBCS_E_INVALID;  // the first bound is the empty key
+    for (int32_t i = 0; i < M; i++) {
+        if (bo[i + 1] < bo[i] || bo[i + 1] - bo[i] > INT32_MAX) return FDBCS_E_INVALID;
+        if (ho[i + 1] <= ho[i]) return FDBCS_E_INVALID;  // a range without an owner
+    }
+    if (bo[M] > bo[0] && !m->bound_bytes) return FDBCS_E_INVALID;
+    for (int32_t i = 1; i < M; i++)
+        if (cmp_bytes(m->bound_bytes + bo[i - 1], (int32_t)(bo[i] - bo[i - 1]), m->bound_bytes + bo[i],
+                      (int32_t)(bo[i + 1] - bo[i])) >= 0)
+            return FDBCS_E_INVALID;
+    for (int32_t i = 0; i < M; i++)
+        for (int64_t k = ho[i]; k < ho[i + 1]; k++) {
+            if (m->hist_resolvers[k] < 0) return FDBCS_E_INVALID;
+            if (k > ho[i] && m->hist_versions[k] < m->hist_versions[k - 1]) return FDBCS_E_INVALID;
+        }
+    return FDBCS_OK;
+}
+
+// own[] and until[] of a checked map for one resolver (engine.h RouteArgs::map).
+static void route_map_derive(const fdbcs_key_resolvers* m, int32_t resolver, uint8_t* own, int64_t* until) {
+    for (int32_t i = 0; i < m->n_ranges; i++) {
+        const int64_t h0 = m->hist_offsets[i], h1 = m->hist_offsets[i + 1];
+        uint8_t o = m->hist_resolvers[h1 - 1] == resolver ? 1 : 0;
+        int64_t u = INT64_MIN;
+        for (int64_t k = h0; k + 1 < h1; k++)
+            if (m->hist_resolvers[k] == resolver) {
+                o |= 2;
+                u = std::max(u, m->hist_versions[k + 1]);
+            }
+        own[i] = o;
+        until[i] = u;
+    }
+}
+
+int fdbcs_route_map_pack(const fdbcs_key_resolvers* map, int32_t resolver, uint8_t* own_out, int64_t* until_out) {
+    if (!own_out || !until_out) return FDBCS_E_INVALID;
+    if (int rc = route_map_check(map, resolver)) return rc;
+    route_map_derive(map, resolver, own_out, until_out);
+    return FDBCS_OK;
+}
+
+// Bytes of a checked map's device block (route_map_layout, its bounds' tails each padded to 8, and
+// the slack tail_cmp's aligned loads need).
+static size_t route_map_bytes(const fdbcs_key_resolvers* m) {
+    int64_t tails = 0;
+    for (int32_t i = 0; i < m->n_ranges; i++) tails += padded_tail((int32_t)(m->bound_offsets[i + 1] - m->bound_offsets[i]));
+    return (size_t)(route_map_layout(m->n_ranges).tail + tails + 64);
+}
+
+// The block itself, into `out` (pinned staging of route_map_bytes bytes).
+static void route_map_fill(const fdbcs_key_resolvers* m, int32_t resolver, uint8_t* out, size_t bytes) {
+    const int32_t M = m->n_ranges;
+    const RouteMapLayout L = route_map_layout(M);
+    memset(out + L.own, 0, bytes - (size_t)L.own);  // padding, summaries' padding, tail slack
+    DKey* bounds = (DKey*)(out + L.bounds);
+    int64_t* until = (int64_t*)(out + L.until);
+    int64_t* sum_until = (int64_t*)(out + L.sum_until);
+    uint8_t *own = out + L.own, *sum_own = out + L.sum_own, *tail = out + L.tail;
+    route_map_derive(m, resolver, own, until);
+    uint32_t tb = 0;
+    for (int32_t i = 0; i < M; i++) {
+        const uint8_t* k = m->bound_bytes + m->bound_offsets[i];
+        const int32_t len = (int32_t)(m->bound_offsets[i + 1] - m->bound_offsets[i]);
+        DKey d;
+        fast_prefix(k, (uint32_t)len, &d.hi, &d.lo);
+        d.len = (uint32_t)len;
+        d.tail = 0;
+        if (len > 16) {
+            d.tail = tb;
+            memcpy(tail + tb, k + 16, (size_t)len - 16);
+            tb += (uint32_t)padded_tail(len);
+        }
+        bounds[i] = d;
+        if (i % kRouteMapSum == 0) sum_until[i / kRouteMapSum] = INT64_MIN;
+        sum_own[i / kRouteMapSum] |= own[i];
+        sum_until[i / kRouteMapSum] = std::max(sum_until[i / kRouteMapSum], until[i]);
+    }
+}
+
+// fdbcs_batch_add_routed (map null: the static range [lo, hi)) and fdbcs_batch_add_routed_map (map
+// checked by the caller; lo / hi unused).
+static int add_routed_impl(fdbcs_batch* b, const void* shares, int64_t stride, int32_t n_shares, int32_t max_share_txns,
+                           const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key, int32_t hi_len,
+                           const fdbcs_key_resolvers* map, int32_t resolver, int32_t cap_txns, int32_t cap_reads,
+                           int32_t cap_writes, int64_t cap_tail, uint8_t* conflict_out, int64_t n_global,
+                           const uint32_t* ready_flag, uint32_t ready_value) {
     if (!b || !shares || stride <= (int64_t)sizeof(ShareHeader) || n_shares <= 0 || max_share_txns < 0 || cap_txns < 0 ||
         cap_reads < 0 || cap_writes < 0 || cap_tail < 0 || (lo_len > 0 && !lo_key) || (hi_len > 0 && !hi_key) ||
         n_global < 0 || (conflict_out && n_global > (int64_t)n_shares * max_share_txns))
@@ -2449,39 +2546,49 @@ int fdbcs_batch_add_routed(fdbcs_batch* b, const void* shares, int64_t stride, i
     HIPOK(hipSetDevice(cs->device));
     BatchSlot* sl = b->slot;
     int rc;
-    // bounds of this resolver's key range: prefixes by value, tails in a small device arena
-    std::vector<uint8_t> want;
-    auto put_len = [&](int32_t n) {
-        for (int i = 0; i < 4; i++) want.push_back((uint8_t)((uint32_t)n >> (8 * i)));
-    };
-    put_len(lo_len);
-    if (lo_len > 0) want.insert(want.end(), lo_key, lo_key + lo_len);
-    put_len(hi_len);
-    if (hi_len > 0) want.insert(want.end(), hi_key, hi_key + hi_len);
     RouteArgs a{};
-    std::vector<uint8_t> btail;
-    auto bound = [&](const uint8_t* k, int32_t len, DKey* d) {
-        fast_prefix(k, (uint32_t)len, &d->hi, &d->lo);
-        d->len = (uint32_t)len;
-        d->tail = 0;
-        if (len > 16) {
-            d->tail = (uint32_t)btail.size();
-            btail.insert(btail.end(), k + 16, k + len);
-            while (btail.size() % 8) btail.push_back(0);
+    size_t map_bytes = 0;
+    if (map) {
+        // the map travels with the batch: a block of its slot, filled and copied below
+        map_bytes = route_map_bytes(map);
+        if ((rc = sl->rt_map.ensure(map_bytes))) return rc;
+        if ((rc = sl->rt_map_pin.ensure(map_bytes))) return rc;
+        a.map = (const uint8_t*)sl->rt_map.p;
+        a.map_n = map->n_ranges;
+    } else {
+        // bounds of this resolver's key range: prefixes by value, tails in a small device arena
+        std::vector<uint8_t> want;
+        auto put_len = [&](int32_t n) {
+            for (int i = 0; i < 4; i++) want.push_back((uint8_t)((uint32_t)n >> (8 * i)));
+        };
+        put_len(lo_len);
+        if (lo_len > 0) want.insert(want.end(), lo_key, lo_key + lo_len);
+        put_len(hi_len);
+        if (hi_len > 0) want.insert(want.end(), hi_key, hi_key + hi_len);
+        std::vector<uint8_t> btail;
+        auto bound = [&](const uint8_t* k, int32_t len, DKey* d) {
+            fast_prefix(k, (uint32_t)len, &d->hi, &d->lo);
+            d->len = (uint32_t)len;
+            d->tail = 0;
+            if (len > 16) {
+                d->tail = (uint32_t)btail.size();
+                btail.insert(btail.end(), k + 16, k + len);
+                while (btail.size() % 8) btail.push_back(0);
+            }
+        };
+        a.has_lo = lo_len >= 0;
+        a.has_hi = hi_len >= 0;
+        if (a.has_lo) bound(lo_key, lo_len, &a.lo);
+        if (a.has_hi) bound(hi_key, hi_len, &a.hi);
+        btail.resize(btail.size() + 64, 0);
+        if (want != cs->route_bounds) {
+            if ((rc = sync_all(cs))) return rc;
+            if ((rc = cs->route_btail.ensure(btail.size()))) return rc;
+            HIPOK(hipMemcpy(cs->route_btail.p, btail.data(), btail.size(), hipMemcpyHostToDevice));
+            cs->route_bounds = want;
         }
-    };
-    a.has_lo = lo_len >= 0;
-    a.has_hi = hi_len >= 0;
-    if (a.has_lo) bound(lo_key, lo_len, &a.lo);
-    if (a.has_hi) bound(hi_key, hi_len, &a.hi);
-    btail.resize(btail.size() + 64, 0);
-    if (want != cs->route_bounds) {
-        if ((rc = sync_all(cs))) return rc;
-        if ((rc = cs->route_btail.ensure(btail.size()))) return rc;
-        HIPOK(hipMemcpy(cs->route_btail.p, btail.data(), btail.size(), hipMemcpyHostToDevice));
-        cs->route_bounds = want;
+        a.btail = (const uint8_t*)cs->route_btail.p;
     }
-    a.btail = (const uint8_t*)cs->route_btail.p;
     // the routed batch's layout at capacity offsets (upload layout)
     const UploadLayout L = upload_layout((size_t)cap_txns, (size_t)cap_reads, (size_t)cap_writes, (size_t)cap_tail);
     if ((rc = ensure_slot(sl, L.total, (size_t)cap_txns, (size_t)cap_reads))) return rc;
@@ -2545,6 +2652,13 @@ int fdbcs_batch_add_routed(fdbcs_batch* b, const void* shares, int64_t stride, i
     HIPOK(hipMemsetAsync(sl->rt_scan.p, 0, scan_bytes, us));
     // global indices past the shares' transactions stay "not routed here"
     HIPOK(hipMemsetAsync(sl->rt_inv.p, 0xFF, 4 * (size_t)a.inv_n, us));
+    if (map) {
+        // derived for this resolver into the slot's pinned staging (its last copy is over: the
+        // slot's previous routing was waited for), then onto the device ahead of the kernels; no
+        // drain, and the batches in flight keep the blocks of their own slots
+        route_map_fill(map, resolver, (uint8_t*)sl->rt_map_pin.p, map_bytes);
+        HIPOK(hipMemcpyAsync(sl->rt_map.p, sl->rt_map_pin.p, map_bytes, hipMemcpyHostToDevice, us));
+    }
     uint64_t* sw = (uint64_t*)sl->rt_scan.p;
     ScanState st{sw + 8, (int*)sw, (int*)(sw + 1)};
     t_record = nullptr;
@@ -2573,6 +2687,24 @@ int fdbcs_batch_add_routed(fdbcs_batch* b, const void* shares, int64_t stride, i
     b->rep_n = 0;
     b->state = 1;
     return FDBCS_OK;
+}
+
+int fdbcs_batch_add_routed(fdbcs_batch* b, const void* shares, int64_t stride, int32_t n_shares, int32_t max_share_txns,
+                           const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key, int32_t hi_len, int32_t cap_txns,
+                           int32_t cap_reads, int32_t cap_writes, int64_t cap_tail, uint8_t* conflict_out,
+                           int64_t n_global, const uint32_t* ready_flag, uint32_t ready_value) {
+    return add_routed_impl(b, shares, stride, n_shares, max_share_txns, lo_key, lo_len, hi_key, hi_len, nullptr, 0,
+                           cap_txns, cap_reads, cap_writes, cap_tail, conflict_out, n_global, ready_flag, ready_value);
+}
+
+int fdbcs_batch_add_routed_map(fdbcs_batch* b, const void* shares, int64_t stride, int32_t n_shares,
+                               int32_t max_share_txns, const fdbcs_key_resolvers* map, int32_t resolver,
+                               int32_t cap_txns, int32_t cap_reads, int32_t cap_writes, int64_t cap_tail,
+                               uint8_t* conflict_out, int64_t n_global, const uint32_t* ready_flag,
+                               uint32_t ready_value) {
+    if (int rc = route_map_check(map, resolver)) return rc;  // before the batch is touched
+    return add_routed_impl(b, shares, stride, n_shares, max_share_txns, nullptr, -1, nullptr, -1, map, resolver,
+                           cap_txns, cap_reads, cap_writes, cap_tail, conflict_out, n_global, ready_flag, ready_value);
 }
 
 // Sizes of a routed batch, once its route kernels are done (blocks until then).

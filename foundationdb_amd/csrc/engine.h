@@ -335,6 +335,32 @@ struct RouteResult {
     int64_t global_T;        // transactions of all shares
     int64_t global_R;        // reads of all shares (the size of a report output)
 };
+// A keyResolvers map as one resolver sees it (fdbcs_batch_add_routed_map; CommitProxyServer.actor.cpp:
+// 147-174): M map ranges [bound[m], bound[m+1]) (bound[0] the empty key, the last range unbounded)
+// and per range own[m] (bit 0: this resolver is the newest owner, bit 1: it appears in an older
+// history entry) and until[m] (the largest version of an entry that follows one of its older
+// entries; INT64_MIN without bit 1).  A read at snapshot s is kept iff some range it meets has bit 0,
+// or bit 1 and until >= s; a write iff some range it meets has bit 0.  Per 32 ranges a summary (OR
+// of own, max of until) bounds the walk of a range that spans many map ranges.  One block of the
+// batch's slot, copied from pinned staging ahead of the routing kernels: offsets by route_map_layout.
+constexpr int32_t kRouteMapMaxRanges = 65536;  // fdbcs_route_map_pack refuses a larger map
+constexpr int32_t kRouteMapLds = 256;          // k_route_mark_map stages a map up to this in LDS
+constexpr int32_t kRouteMapSum = 32;           // map ranges per summary entry
+struct RouteMapLayout {
+    int64_t bounds, until, sum_until, own, sum_own, tail;  // byte offsets (each 8-aligned)
+};
+__host__ __device__ inline RouteMapLayout route_map_layout(int32_t M) {
+    const int64_t nb = ((int64_t)M + kRouteMapSum - 1) / kRouteMapSum;
+    RouteMapLayout L;
+    L.bounds = 0;
+    L.until = L.bounds + (int64_t)sizeof(DKey) * M;
+    L.sum_until = L.until + 8 * (int64_t)M;
+    L.own = L.sum_until + 8 * nb;
+    L.sum_own = L.own + ((int64_t)M + 7) / 8 * 8;
+    L.tail = L.sum_own + (nb + 7) / 8 * 8;
+    return L;
+}
+
 struct RouteArgs {
     const uint8_t* shares;  // n_shares shares, `stride` bytes apart
     int64_t stride;
@@ -342,6 +368,8 @@ struct RouteArgs {
     int32_t has_lo, has_hi;  // this resolver owns [lo, hi): lo absent for the first, hi for the last
     DKey lo, hi;
     const uint8_t* btail;    // tails of lo / hi
+    const uint8_t* map;      // a keyResolvers map instead of [lo, hi) (route_map_layout), or null:
+    int32_t map_n;           // its ranges; launch_route then marks with k_route_mark_map
     int32_t report_enabled;  // the batch collects conflicting-key reports: a placed sub-transaction
                              // copies its share's report flag (CommitProxyServer.actor.cpp:181-186)
     int32_t cap_T, cap_R, cap_W;  // capacity of the output layout
@@ -371,6 +399,8 @@ struct RouteArgs {
 };
 // Route the all-gathered shares into this resolver's batch (two launches on `s`).  grid_n: bound
 // on n_shares * tcap (global elements); the scan state's granules are zeroed by the caller.
+// With RouteArgs::map set the ranges are marked by k_route_mark_map instead of k_route_mark; the
+// scan and the write are the same.
 void launch_route(hipStream_t s, const RouteArgs& a, ScanState st);
 // reports: the scan of a reporting batch (RouteArgs::report_enabled) carries a seventh counter
 int64_t route_scan_words(int64_t n_elems, bool reports = false);

@@ -16,7 +16,8 @@
 //   stage B Y D.MergeWrite       k_seg_prep, k_merge_copy<BatchIns>; compaction: k_compact_search,
 //                                k_scan<CompactSumScan>, k_merge_copy<CompactIns>
 //             D.RemoveBefore     k_scan<GcScan> (with a compaction); k_epilogue: levels, index, scalars
-//   routing   (multi-resolver)   k_route_mark, k_scan<RouteScan>, k_route_write
+//   routing   (multi-resolver)   k_route_mark (or k_route_mark_map under a keyResolvers map),
+//                                k_scan<RouteScan>, k_route_write
 //
 // Memory-bound integer/byte work: no MFMA anywhere (BASELINE.json north_star).
 #include <hip/hip_runtime.h>
@@ -3793,6 +3794,96 @@ __global__ __launch_bounds__(kBlock) void k_route_mark(RouteArgs a) {
         (in ? 1u : 0u) | ((kb.len > 19u || ke.len > 19u) ? 2u : 0u) | ((kb.len > 24u || ke.len > 24u) ? 4u : 0u) | (tl << 8);
 }
 
+// Does this resolver receive the range [kb, ke) under a keyResolvers map (engine.h RouteArgs::map;
+// CommitProxyServer.actor.cpp:147-174)?  m0 = rangeContaining(begin) is the last bound <= begin,
+// m1 = max(m0, the last bound < end): two binary searches, the second over (m0, M) only, which
+// takes the max.  Then the predicate over [m0, m1], a whole summary block of kRouteMapSum ranges
+// at a time where the span covers one: at most 2 * (kRouteMapSum - 1) + M / kRouteMapSum steps.
+// mb / own / until / sown / suntil point into LDS (a staged map) or global memory.
+__device__ __forceinline__ bool route_map_keep(const DKey* mb, const uint8_t* mtail, const uint8_t* own,
+                                               const int64_t* until, const uint8_t* sown, const int64_t* suntil,
+                                               int M, const DKey& kb, const DKey& ke, const uint8_t* tb, bool is_read,
+                                               int64_t snap) {
+    int lo = 1, hi = M;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (dkey_cmp(mb[mid], mtail, kb, tb) <= 0) lo = mid + 1; else hi = mid;
+    }
+    const int m0 = lo - 1;
+    hi = M;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (dkey_cmp(mb[mid], mtail, ke, tb) < 0) lo = mid + 1; else hi = mid;
+    }
+    const int m1 = lo - 1;
+    for (int m = m0; m <= m1;) {
+        if ((m & (kRouteMapSum - 1)) == 0 && m + kRouteMapSum - 1 <= m1) {
+            const uint32_t o = sown[m / kRouteMapSum];
+            if ((o & 1u) || (is_read && (o & 2u) && suntil[m / kRouteMapSum] >= snap)) return true;
+            m += kRouteMapSum;
+        } else {
+            const uint32_t o = own[m];
+            if ((o & 1u) || (is_read && (o & 2u) && until[m] >= snap)) return true;
+            m++;
+        }
+    }
+    return false;
+}
+
+// k_route_mark under a keyResolvers map (fdbcs_batch_add_routed_map): the same info word per range
+// of every share, kept iff route_map_keep; a read's snapshot comes through the share's owner[] and
+// snap[].  A map of up to kRouteMapLds ranges (the normal case: keyResolvers holds a few ranges per
+// resolver) is staged in LDS once per workgroup and searched there, its bounds' tails excepted; a
+// larger one is searched in global memory.  Workgroups past the share's ranges leave before staging.
+__global__ __launch_bounds__(kBlock) void k_route_mark_map(RouteArgs a) {
+    if (*a.wait_err) return;
+    const int p = blockIdx.y;
+    const ShareHeader* h = share_at(a, p);
+    const int64_t nr = (int64_t)h->R + h->W;
+    const int64_t n = nr < a.rstride ? nr : a.rstride;
+    if ((int64_t)blockIdx.x * blockDim.x >= n) return;
+    const int M = a.map_n;
+    const RouteMapLayout L = route_map_layout(M);
+    const DKey* mb = (const DKey*)(a.map + L.bounds);
+    const int64_t* until = (const int64_t*)(a.map + L.until);
+    const int64_t* suntil = (const int64_t*)(a.map + L.sum_until);
+    const uint8_t* own = a.map + L.own;
+    const uint8_t* sown = a.map + L.sum_own;
+    const uint8_t* mtail = a.map + L.tail;
+    __shared__ DKey s_b[kRouteMapLds];
+    __shared__ int64_t s_until[kRouteMapLds];
+    __shared__ int64_t s_suntil[kRouteMapLds / kRouteMapSum];
+    __shared__ uint8_t s_own[kRouteMapLds];
+    __shared__ uint8_t s_sown[kRouteMapLds / kRouteMapSum];
+    const bool staged = M <= kRouteMapLds;
+    if (staged) {
+        for (int m = threadIdx.x; m < M; m += blockDim.x) {
+            s_b[m] = mb[m];
+            s_until[m] = until[m];
+            s_own[m] = own[m];
+            if (m % kRouteMapSum == 0) {
+                s_suntil[m / kRouteMapSum] = suntil[m / kRouteMapSum];
+                s_sown[m / kRouteMapSum] = sown[m / kRouteMapSum];
+            }
+        }
+        __syncthreads();
+    }
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const uint8_t* base = (const uint8_t*)h;
+    const DKey* keys = (const DKey*)(base + h->off_keys);
+    const uint8_t* tb = base + h->off_tail;
+    const DKey kb = keys[2 * j], ke = keys[2 * j + 1];
+    const bool is_read = j < h->R;
+    int64_t snap = 0;
+    if (is_read) snap = ((const int64_t*)(base + h->off_snap))[((const int32_t*)(base + h->off_owner))[j]];
+    const bool in = staged ? route_map_keep(s_b, mtail, s_own, s_until, s_sown, s_suntil, M, kb, ke, tb, is_read, snap)
+                           : route_map_keep(mb, mtail, own, until, sown, suntil, M, kb, ke, tb, is_read, snap);
+    const uint32_t tl = (kb.len > 16u ? kb.len - 16u : 0u) + (ke.len > 16u ? ke.len - 16u : 0u);
+    a.info[(int64_t)p * a.rstride + j] =
+        (in ? 1u : 0u) | ((kb.len > 19u || ke.len > 19u) ? 2u : 0u) | ((kb.len > 24u || ke.len > 24u) ? 4u : 0u) | (tl << 8);
+}
+
 // One element per transaction of every share (element i = share i / tcap, transaction i % tcap;
 // past the share's T: padding): what this resolver keeps of it, as counts; the store places the
 // sub-transaction and leaves its prefixes for k_route_write.
@@ -3987,7 +4078,10 @@ int64_t route_scan_words(int64_t n_elems, bool reports) {
 void launch_route(hipStream_t s, const RouteArgs& a, ScanState st) {
     const dim3 grid((unsigned)std::max<int64_t>(1, (a.rstride + kBlock - 1) / kBlock), (unsigned)a.n_shares);
     fdb_launch(k_route_wait, dim3(1), dim3(64), 0, s, a.ready, a.ready_value, a.wait_err, a.wait_ticks);
-    fdb_launch(k_route_mark, grid, dim3(kBlock), 0, s, a);
+    if (a.map)
+        fdb_launch(k_route_mark_map, grid, dim3(kBlock), 0, s, a);
+    else
+        fdb_launch(k_route_mark, grid, dim3(kBlock), 0, s, a);
     // a reporting batch counts its reporting sub-transactions with a seventh component
     if (a.report_enabled)
         launch_scan<7, kRouteScanP>(s, RouteScan<7>{a}, nullptr, (int64_t)a.n_shares * a.tcap, st);

@@ -342,6 +342,22 @@ class KeyResolvers:
         """(begin, current owner) per map range."""
         return [(b, h[-1][1]) for b, h in zip(self.bounds, self.hist)]
 
+    def flat(self) -> Dict[str, np.ndarray]:
+        """The map as the arrays of the C-ABI's fdbcs_key_resolvers: bound_bytes (uint8),
+        bound_offsets and hist_offsets (int64, one more than the ranges), hist_versions (int64) and
+        hist_resolvers (int32)."""
+        bo = np.zeros(len(self.bounds) + 1, np.int64)
+        np.cumsum([len(b) for b in self.bounds], out=bo[1:])
+        ho = np.zeros(len(self.hist) + 1, np.int64)
+        np.cumsum([len(h) for h in self.hist], out=ho[1:])
+        return {
+            "bound_bytes": np.frombuffer(b"".join(self.bounds), np.uint8).copy(),
+            "bound_offsets": bo,
+            "hist_offsets": ho,
+            "hist_versions": np.array([v for h in self.hist for v, _ in h], np.int64),
+            "hist_resolvers": np.array([r for h in self.hist for _, r in h], np.int32),
+        }
+
     # -- routing
     def masks(self, pb: PackedBatch) -> Tuple[np.ndarray, np.ndarray]:
         R, W = pb.n_reads, pb.n_writes

@@ -333,6 +333,47 @@ int fdbcs_batch_add_routed(fdbcs_batch* b, const void* shares, int64_t stride, i
                            uint32_t ready_value);
 int fdbcs_batch_routed_info(fdbcs_batch* b, int32_t* n_txn, int32_t* n_reads, int32_t* n_writes, void** inv_dev,
                             void** read_ids_dev);
+
+/* Device routing under a keyResolvers map with its ownership history (ProxyCommitData::keyResolvers,
+ * CommitProxyServer.actor.cpp:147-174, 622-626): a key range may move between resolvers while the
+ * batches are routed on the GPUs.  The map has n_ranges ranges [bound m, bound m+1): bound m is
+ * bound_bytes[bound_offsets[m], bound_offsets[m+1]), bound 0 is the empty key and the last range is
+ * unbounded.  Range m's history is entries [hist_offsets[m], hist_offsets[m+1]) of hist_versions /
+ * hist_resolvers, oldest first.  A conflict range [b, e) meets the ranges m0 = rangeContaining(b)
+ * to m1 = max(m0, the last m with bound m < e) (an empty range: rangeContaining(b)).  A write goes
+ * to resolver g iff g is the newest owner of one of them; a read at snapshot s iff, for one of them,
+ * walking its history from the newest entry and stopping after the first entry whose version is
+ * < s, g is met.
+ * A map is invalid (FDBCS_E_INVALID) with n_ranges < 1 or > 65536, a non-empty first bound, bounds
+ * not strictly ascending, a range without a history entry, versions decreasing within a range, or
+ * a negative resolver id (the argument or an entry). */
+typedef struct fdbcs_key_resolvers {
+    int32_t n_ranges;
+    const uint8_t* bound_bytes;
+    const int64_t* bound_offsets; /* [n_ranges + 1] */
+    const int64_t* hist_offsets;  /* [n_ranges + 1] */
+    const int64_t* hist_versions;
+    const int32_t* hist_resolvers;
+} fdbcs_key_resolvers;
+/* Host only (no device needed, like fdbcs_share_pack): checks the map and writes what the routing
+ * kernel reads of it for one resolver.  own_out[m] bit 0: the resolver is range m's newest owner;
+ * bit 1: it appears in an older entry.  until_out[m]: the largest version of an entry that follows
+ * one of its older entries (INT64_MIN without bit 1).  A read at snapshot s is kept iff some range
+ * it meets has bit 0, or bit 1 and until >= s; a write iff some range it meets has bit 0. */
+int fdbcs_route_map_pack(const fdbcs_key_resolvers* map, int32_t resolver, uint8_t* own_out, int64_t* until_out);
+/* fdbcs_batch_add_routed with the key range [lo_key, hi_key) replaced by (map, resolver): the same
+ * states, capacities, conflict_out, ready flag and error codes, and the same calls afterwards
+ * (fdbcs_batch_routed_info, fdbcs_batch_set_report_output, fdbcs_batch_conflicting_reads,
+ * fdbcs_batch_report_entries).  An invalid map is FDBCS_E_INVALID at the call and leaves the batch
+ * untouched.  The map is read during the call and travels with the batch: its derived form is
+ * copied to device memory of the batch ahead of the routing kernels, so every batch may pass a
+ * different map at no extra synchronisation, and batches in flight keep the map they were routed
+ * under. */
+int fdbcs_batch_add_routed_map(fdbcs_batch* b, const void* shares, int64_t stride, int32_t n_shares,
+                               int32_t max_share_txns, const fdbcs_key_resolvers* map, int32_t resolver,
+                               int32_t cap_txns, int32_t cap_reads, int32_t cap_writes, int64_t cap_tail,
+                               uint8_t* conflict_out, int64_t n_global, const uint32_t* ready_flag,
+                               uint32_t ready_value);
 /* Routed batches only, after fdbcs_batch_add_routed and before detect.  Detect then also writes
  * dev_out[0, n_global_reads) (device memory of this GPU, any allocator): 1 at the global read
  * index of every read this resolver's conflictingKeyRangeMap would hold (every conflicting read
