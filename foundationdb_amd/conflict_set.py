@@ -136,6 +136,11 @@ SIGNATURES = {
     "fdbcs_history_import": (ctypes.c_int, [_VP, _VP, _I32, _VP, _I32, _I64, _VP, _VP, _VP, _I64,
                                             ctypes.POINTER(_I64)]),
     "fdbcs_history_import_pending": (ctypes.c_int, [_VP, _VP, _VP, _I32, _VP, _I32, ctypes.POINTER(_I64)]),
+    "fdbcs_history_import_delta": (ctypes.c_int, [_VP, _VP, _I32, _VP, _I32, _I64, _VP, _VP, _VP, _I64,
+                                                  ctypes.POINTER(_I64)]),
+    "fdbcs_history_import_delta_pending": (ctypes.c_int, [_VP, _VP, _VP, _I32, _VP, _I32, ctypes.POINTER(_I64)]),
+    "fdbcs_history_import_info": (ctypes.c_int, [_VP, ctypes.POINTER(_I32), ctypes.POINTER(_I64),
+                                                 ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     "fdbcs_history_import_timing": (ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_double),
                                                    ctypes.POINTER(ctypes.c_double)]),
     "fdbcs_get_stats": (ctypes.c_int, [_VP, ctypes.POINTER(Stats)]),
@@ -412,29 +417,54 @@ class ConflictSet:
         kh = np.frombuffer(hi if hi is not None else b"", np.uint8)
         return kl, (len(kl) if lo is not None else -1), kh, (len(kh) if hi is not None else -1)
 
+    @staticmethod
+    def _into(into: str) -> bool:
+        if into not in ("base", "delta"):
+            raise ValueError(f"into must be 'base' or 'delta', not {into!r}")
+        return into == "delta"
+
     def merge_history(self, key_bytes, key_offsets, versions, header_version: int = 0,
-                      lo: Optional[bytes] = None, hi: Optional[bytes] = None) -> int:
+                      lo: Optional[bytes] = None, hi: Optional[bytes] = None, into: str = "base") -> int:
         """fdbcs_history_import: fold an exported history (the arrays dump_history returns) into
         this set over [lo, hi): every key there afterwards reads the greater of the version it read
         before and the imported one.  Returns the history size afterwards.
-        dst.merge_history(*src.dump_history(lo, hi), lo=lo, hi=hi) hands [lo, hi) over."""
+        dst.merge_history(*src.dump_history(lo, hi), lo=lo, hi=hi) hands [lo, hi) over.
+        into="delta" (fdbcs_history_import_delta) writes the delta tier only, at a cost that does not
+        depend on the base's size; import_info() tells which path ran."""
+        delta = self._into(into)
         kb = np.ascontiguousarray(key_bytes, np.uint8)
         ko = np.ascontiguousarray(key_offsets, np.int64)
         vv = np.ascontiguousarray(versions, np.int64)
         kl, ll, kh, hl = self._bounds(lo, hi)
         out = _I64()
-        _check(load_library().fdbcs_history_import(self._h, _p(kl), ll, _p(kh), hl, len(vv), _p(kb), _p(ko), _p(vv),
-                                                   header_version, ctypes.byref(out)), "historyImport")
+        L = load_library()
+        f = L.fdbcs_history_import_delta if delta else L.fdbcs_history_import
+        _check(f(self._h, _p(kl), ll, _p(kh), hl, len(vv), _p(kb), _p(ko), _p(vv), header_version, ctypes.byref(out)),
+               "historyImportDelta" if delta else "historyImport")
         return out.value
 
-    def merge_pending_export(self, src: "ConflictSet", lo: Optional[bytes] = None, hi: Optional[bytes] = None) -> int:
+    def merge_pending_export(self, src: "ConflictSet", lo: Optional[bytes] = None, hi: Optional[bytes] = None,
+                             into: str = "base") -> int:
         """fdbcs_history_import_pending: the same import, reading the result of src.export_history()
-        from src's device buffers (same device; no host copy).  src's result stays readable."""
+        from src's device buffers (same device; no host copy).  src's result stays readable.
+        into="delta": fdbcs_history_import_delta_pending."""
+        delta = self._into(into)
         kl, ll, kh, hl = self._bounds(lo, hi)
         out = _I64()
-        _check(load_library().fdbcs_history_import_pending(self._h, src._h, _p(kl), ll, _p(kh), hl, ctypes.byref(out)),
-               "historyImportPending")
+        L = load_library()
+        f = L.fdbcs_history_import_delta_pending if delta else L.fdbcs_history_import_pending
+        _check(f(self._h, src._h, _p(kl), ll, _p(kh), hl, ctypes.byref(out)),
+               "historyImportDeltaPending" if delta else "historyImportPending")
         return out.value
+
+    def import_info(self) -> dict:
+        """fdbcs_history_import_info: the last successful import's path (0: folded into a new base,
+        1: merged into the delta), the base tier's size after it and the delta tier's around it."""
+        path, base, before, after = _I32(), _I64(), _I64(), _I64()
+        _check(load_library().fdbcs_history_import_info(self._h, ctypes.byref(path), ctypes.byref(base),
+                                                        ctypes.byref(before), ctypes.byref(after)), "importInfo")
+        return {"path": path.value, "base_boundaries": base.value, "delta_before": before.value,
+                "delta_after": after.value}
 
     def import_timing(self) -> Tuple[float, float]:
         """Milliseconds of the last import's kernels (device) and of the whole call (host)."""

@@ -419,6 +419,11 @@ struct fdbcs_conflict_set {
     DBuf i_bytes, i_off, i_ver, i_bnd, i_okey, i_olt, i_over, i_otail, i_mval, i_mkey, i_mlt, i_dblt, i_vblt, i_state;
     hipEvent_t i_ev[6] = {};                      // around the import's three groups of kernels
     double i_ms_kernels = 0, i_ms_host = 0;       // of the last import (fdbcs_history_import_timing)
+    // fdbcs_history_import_delta: its words + scan granules (allocated by the first delta import), and
+    // what the last successful import of either kind did (fdbcs_history_import_info)
+    DBuf i_dstate;
+    int32_t i_path = 0;                           // 0: folded into a new base, 1: merged into the delta
+    int64_t i_info_base = 0, i_info_before = 0, i_info_after = 0;  // base size; delta size around it
 };
 
 // Host/device staging of one batch.  Batches are short-lived (one per commit batch, as the
@@ -1421,7 +1426,7 @@ void fdbcs_destroy_conflict_set(fdbcs_conflict_set* cs) {
     if (cs->x_ev0) (void)hipEventDestroy(cs->x_ev0);
     if (cs->x_ev1) (void)hipEventDestroy(cs->x_ev1);
     for (DBuf* x : {&cs->i_bytes, &cs->i_off, &cs->i_ver, &cs->i_bnd, &cs->i_okey, &cs->i_olt, &cs->i_over, &cs->i_otail,
-                    &cs->i_mval, &cs->i_mkey, &cs->i_mlt, &cs->i_dblt, &cs->i_vblt, &cs->i_state})
+                    &cs->i_mval, &cs->i_mkey, &cs->i_mlt, &cs->i_dblt, &cs->i_vblt, &cs->i_state, &cs->i_dstate})
         x->release();
     for (hipEvent_t e : cs->i_ev)
         if (e) (void)hipEventDestroy(e);
@@ -1680,6 +1685,14 @@ int fdbcs_history_export_timing(fdbcs_conflict_set* cs, double* ms_kernels, doub
     return FDBCS_OK;
 }
 
+// What the last successful import did (fdbcs_history_import_info).
+static void import_note(fdbcs_conflict_set* cs, int32_t path, int64_t base, int64_t delta_before, int64_t delta_after) {
+    cs->i_path = path;
+    cs->i_info_base = base;
+    cs->i_info_before = delta_before;
+    cs->i_info_after = delta_after;
+}
+
 // The import proper, on device arrays (both entry points end here).  The set is idle, its streams
 // drained; d_bytes is 8-byte aligned with >= 16 readable bytes past nbytes.  The host does no
 // per-boundary work: it sizes buffers from n and nbytes, reads the import words back after the
@@ -1771,6 +1784,7 @@ static int import_device(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t 
     if (words[kIwError]) return FDBCS_E_DEVICE;
     if (has_lo && has_hi && cmp_bytes(lo_key, lo_len, hi_key, hi_len) == 0) {  // an empty range: validated, nothing to do
         *boundaries_out = nb + nd;
+        import_note(cs, 0, nb, nd, nd);
         return FDBCS_OK;
     }
     const int64_t m = words[kIwM];
@@ -1811,6 +1825,186 @@ static int import_device(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t 
     cs->nd_ub = 0;
     cs->tail_ub = tail_used;
     *boundaries_out = kept;
+    import_note(cs, 0, kept, nd, 0);
+    return FDBCS_OK;
+}
+
+// The import into the delta tier, on device arrays (same contract as import_device).  Phase 1
+// validates the arrays, builds the overlay and places lo and hi in both tiers; the host then knows
+// an upper bound of the delta afterwards and either goes on (phase 2 writes the non-current delta
+// buffer and arena bytes past tail_used, and the host switches to them after reading the result
+// words) or hands the whole import to the fold, which leaves an empty delta.
+static int import_delta_device(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key,
+                               int32_t hi_len, int64_t n, const uint8_t* d_bytes, int64_t nbytes, const int64_t* d_off,
+                               const int64_t* d_ver, int64_t ihdr, int64_t* boundaries_out) {
+    Scalars sc;
+    HIPOK(hipMemcpy(&sc, cs->scal.p, sizeof(sc), hipMemcpyDeviceToHost));
+    const int64_t nb = sc.n, nd = sc.ndb[cs->dcur];
+    if (nb + nd + n + 2 >= ((int64_t)1 << 31)) return FDBCS_E_NOMEM;  // as the fold refuses
+    const bool has_lo = lo_len >= 0, has_hi = hi_len >= 0;
+    const int64_t ll = has_lo ? lo_len : 0, hl = has_hi ? hi_len : 0;
+    // overlay tails as in import_device; at most that many units are appended to the arena
+    const int64_t u_lo = ((nbytes + 7) >> 3) + n + 1, u_hi = u_lo + ((ll + 7) >> 3) + 1, u_end = u_hi + ((hl + 7) >> 3) + 1;
+    const int64_t tail_base = (sc.tail_used + 7) >> 3;
+    const int64_t tail_need = 8 * (tail_base + u_end);
+    if (tail_need + 1 >= kTailLimit) return FDBCS_E_NOMEM;
+    int rc;
+    const int64_t bnd_hi = (ll + 7) / 8 * 8 + 16;
+    if ((rc = cs->i_bnd.ensure((size_t)(bnd_hi + hl + 64)))) return rc;
+    if ((rc = cs->i_okey.ensure(16 * (size_t)(n + 2)))) return rc;
+    if ((rc = cs->i_olt.ensure(8 * (size_t)(n + 2)))) return rc;
+    if ((rc = cs->i_over.ensure(8 * (size_t)(n + 2)))) return rc;
+    if ((rc = cs->i_otail.ensure(8 * (size_t)u_end + kTailSlack))) return rc;
+    if ((rc = cs->i_vblt.ensure(8 * (size_t)(n + 2)))) return rc;
+    if ((rc = cs->i_state.ensure(8 * (size_t)kIwWords))) return rc;
+    if ((rc = cs->i_dstate.ensure(8 * (size_t)kIdWords))) return rc;
+    for (hipEvent_t& e : cs->i_ev)
+        if (!e) HIPOK(hipEventCreate(&e));
+    ImportDeltaArgs d{};
+    ImportArgs& a = d.a;
+    auto tiers = [&] {  // (again after a capacity change: the buffers may have moved)
+        a.base = hist_of(cs, cs->cur);
+        a.delta = delta_of(cs, cs->dcur);
+        a.htail = (const uint8_t*)cs->htail[cs->tcur].p;
+        a.dst = delta_of(cs, cs->dcur ^ 1);
+        a.tdst = (uint8_t*)cs->htail[cs->tcur].p;
+        a.dst_cap = cs->delta_cap;
+        a.tdst_units = cs->tail_cap / 8;
+    };
+    tiers();
+    a.nb = nb;
+    a.nd = nd;
+    a.hdr = cs->header_version;
+    a.n = n;
+    a.bytes = d_bytes;
+    a.nbytes = nbytes;
+    a.offsets = d_off;
+    a.versions = d_ver;
+    a.ihdr = ihdr;
+    a.has_lo = has_lo;
+    a.has_hi = has_hi;
+    a.lo_len = (int32_t)ll;
+    a.hi_len = (int32_t)hl;
+    a.bnd = (const uint8_t*)cs->i_bnd.p;
+    a.bnd_hi = bnd_hi;
+    a.ov.key = (ulonglong2*)cs->i_okey.p;
+    a.ov.lt = (uint2*)cs->i_olt.p;
+    a.ov.ver = (int64_t*)cs->i_over.p;
+    a.otail = (uint8_t*)cs->i_otail.p;
+    a.otail_lo = u_lo;
+    a.otail_hi = u_hi;
+    a.ovhdr = has_lo ? kHole : ihdr;
+    a.words = (int64_t*)cs->i_state.p;
+    a.v_blt = (int64_t*)cs->i_vblt.p;
+    a.new_hdr = has_lo ? cs->header_version : std::max(cs->header_version, ihdr);
+    d.dwords = (int64_t*)cs->i_dstate.p;
+    d.tail_base = tail_base;
+    hipStream_t s = cs->stream;
+    if (ll) HIPOK(hipMemcpyAsync(cs->i_bnd.p, lo_key, (size_t)ll, hipMemcpyHostToDevice, s));
+    if (hl) HIPOK(hipMemcpyAsync((uint8_t*)cs->i_bnd.p + bnd_hi, hi_key, (size_t)hl, hipMemcpyHostToDevice, s));
+    HIPOK(hipMemsetAsync(cs->i_state.p, 0, 8 * (size_t)kIwWords, s));
+    HIPOK(hipMemsetAsync(cs->i_dstate.p, 0, 8 * (size_t)kIdWords, s));
+    const int64_t none = kHole;
+    HIPOK(hipMemcpyAsync(&a.words[kIwMaxVer], &none, 8, hipMemcpyHostToDevice, s));
+    int64_t words[kIwWords], dw[kIdWords];
+    HIPOK(hipEventRecord(cs->i_ev[0], s));
+    launch_import_overlay(s, a);
+    launch_import_delta_bounds(s, d);
+    HIPOK(take_launch_error());
+    HIPOK(hipEventRecord(cs->i_ev[1], s));
+    HIPOK(hipMemcpyAsync(words, cs->i_state.p, sizeof(words), hipMemcpyDeviceToHost, s));
+    HIPOK(hipMemcpyAsync(dw, cs->i_dstate.p, sizeof(dw), hipMemcpyDeviceToHost, s));
+    HIPOK(hipStreamSynchronize(s));
+    cs->i_ms_kernels = ev_ms(cs->i_ev[0], cs->i_ev[1]);
+    if ((int32_t)words[kIwError] & 1) return FDBCS_E_INVALID;
+    if (words[kIwError]) return FDBCS_E_DEVICE;
+    if (has_lo && has_hi && cmp_bytes(lo_key, lo_len, hi_key, hi_len) == 0) {  // an empty range: validated, nothing to do
+        *boundaries_out = nb + nd;
+        import_note(cs, 1, nb, nd, nd);
+        return FDBCS_OK;
+    }
+    const int64_t m = words[kIwM];
+    if (m < (has_lo ? 1 : 0) + (has_hi ? 1 : 0) || m > n + 2) return FDBCS_E_DEVICE;
+    d.p_lo = dw[kIdPlo];
+    d.p_hi = dw[kIdPhi];
+    d.q_lo = dw[kIdQlo];
+    d.q_hi = dw[kIdQhi];
+    d.e_ver = dw[kIdEver];
+    d.e_skip = dw[kIdEskip] ? 1 : 0;
+    if (d.p_lo < 0 || d.p_lo > d.p_hi || d.p_hi > nd || d.q_lo < 0 || d.q_lo > d.q_hi || d.q_hi > nb) return FDBCS_E_DEVICE;
+    const int64_t ndr = d.p_hi - d.p_lo, nbr = d.q_hi - d.q_lo;
+    d.mr = m - (has_hi ? 1 : 0);
+    d.R = ndr + nbr + d.mr;
+    // the delta afterwards holds at most its boundaries outside the range, the range's and the closing one
+    const int64_t nd_bound = nd + nbr + m + 2;
+    bool fold = nd_bound > delta_limit_for(cs, cs->n_ub);
+    if (!fold) {
+        rc = ensure_delta(cs, nd_bound);
+        if (rc == FDBCS_E_NOMEM)
+            fold = true;
+        else if (rc)
+            return rc;
+    }
+    if (fold) {  // the existing path takes every range this one cannot hold: exact, with an empty delta
+        const double ms = cs->i_ms_kernels;
+        rc = import_device(cs, lo_key, lo_len, hi_key, hi_len, n, d_bytes, nbytes, d_off, d_ver, ihdr, boundaries_out);
+        cs->i_ms_kernels += ms;
+        return rc;
+    }
+    if ((rc = ensure_history(cs, cs->hist_cap, tail_need + 1))) return rc;
+    const int64_t total = d.R + (has_hi ? 1 : 0);
+    const int64_t gran = scan_granules(total, 2);
+    if ((rc = cs->i_mval.ensure(8 * (size_t)(total + 1)))) return rc;
+    if ((rc = cs->i_mkey.ensure(16 * (size_t)(total + 1)))) return rc;
+    if ((rc = cs->i_mlt.ensure(8 * (size_t)(total + 1)))) return rc;
+    if ((rc = cs->i_dblt.ensure(8 * (size_t)(nd + 1)))) return rc;
+    if ((rc = cs->i_dstate.ensure(8 * (size_t)(kIdWords + gran)))) return rc;
+    tiers();
+    a.m_val = (int64_t*)cs->i_mval.p;
+    a.m_key = (ulonglong2*)cs->i_mkey.p;
+    a.m_lt = (uint2*)cs->i_mlt.p;
+    a.d_blt = (int64_t*)cs->i_dblt.p;
+    d.dwords = (int64_t*)cs->i_dstate.p;
+    HIPOK(hipMemsetAsync(cs->i_dstate.p, 0, 8 * (size_t)(kIdWords + gran), s));
+    HIPOK(hipEventRecord(cs->i_ev[2], s));
+    HIPOK(hipMemsetAsync(cs->i_mlt.p, 0, 8 * (size_t)(total + 1), s));
+    launch_import_delta_merge(s, d, (uint64_t*)cs->i_dstate.p + kIdWords);
+    HIPOK(take_launch_error());
+    HIPOK(hipEventRecord(cs->i_ev[3], s));
+    HIPOK(hipMemcpyAsync(dw, cs->i_dstate.p, sizeof(dw), hipMemcpyDeviceToHost, s));
+    HIPOK(hipStreamSynchronize(s));
+    cs->i_ms_kernels += ev_ms(cs->i_ev[2], cs->i_ev[3]);
+    if ((int32_t)dw[kIdError] & 8) return FDBCS_E_NOMEM;
+    if (dw[kIdError] || ((const int32_t*)&dw[kIdScan])[1]) return FDBCS_E_DEVICE;
+    const int64_t kept = dw[kIdKept], units = dw[kIdTailUnits];
+    const int64_t nd_new = d.p_lo + kept + (nd - d.p_hi);
+    if (kept < 0 || kept > total || nd_new > cs->delta_cap || units < 0 || units > u_end) return FDBCS_E_DEVICE;
+    // success: the delta buffer the kernels filled becomes current, the appended tails count
+    const int64_t tail_used = units ? 8 * (tail_base + units) : sc.tail_used;
+    cs->dcur ^= 1;
+    sc.nd = nd_new;
+    sc.ndb[cs->dcur] = nd_new;
+    sc.tail_used = tail_used;
+    HIPOK(hipMemcpyAsync(cs->scal.p, &sc, sizeof(sc), hipMemcpyHostToDevice, s));
+    cs->ddir_epoch[0] = cs->ddir_epoch[1] = 0;  // the delta's directory is not trusted until an epilogue refills it
+    cs->prev_segs = false;
+    HIPOK(hipEventRecord(cs->i_ev[4], s));
+    // levels and sample index of the new delta buffer, as ensure_delta rebuilds them after a regrow
+    launch_rangemax(s, dlevels_of(cs, cs->dcur), (Scalars*)cs->scal.p, &((Scalars*)cs->scal.p)->ndb[cs->dcur],
+                    cs->dlvl3_n, cs->dlvl2_n, std::max<int64_t>(nd_new, 1));
+    // the greatest version left in the new delta: the top of its rebuilt levels (holes are INT64_MIN)
+    launch_import_max(s, dlevels_of(cs, cs->dcur), cs->dlvl3_n, &a.words[kIwMaxVer]);
+    HIPOK(take_launch_error());
+    HIPOK(hipEventRecord(cs->i_ev[5], s));
+    HIPOK(hipMemcpyAsync(&words[kIwMaxVer], &a.words[kIwMaxVer], 8, hipMemcpyDeviceToHost, s));
+    HIPOK(hipStreamSynchronize(s));
+    cs->i_ms_kernels += ev_ms(cs->i_ev[4], cs->i_ev[5]);
+    cs->header_version = a.new_hdr;
+    cs->max_written = std::max({cs->max_written, a.new_hdr, words[kIwMaxVer]});
+    cs->nd_ub = nd_new;  // exact: the next batch's compaction trigger counts the import
+    cs->tail_ub = tail_used;
+    *boundaries_out = nb + nd_new;
+    import_note(cs, 1, nb, nd, nd_new);
     return FDBCS_OK;
 }
 
@@ -1820,9 +2014,9 @@ static int import_bounds_ok(const uint8_t* lo_key, int32_t lo_len, const uint8_t
     return FDBCS_OK;
 }
 
-int fdbcs_history_import(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key,
+static int import_arrays(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key,
                          int32_t hi_len, int64_t n, const uint8_t* key_bytes, const int64_t* key_offsets,
-                         const int64_t* versions, int64_t header_version, int64_t* boundaries_out) {
+                         const int64_t* versions, int64_t header_version, int64_t* boundaries_out, bool to_delta) {
     if (!cs || !boundaries_out || n < 0 || (n > 0 && (!key_offsets || !versions))) return FDBCS_E_INVALID;
     if (int rc = import_bounds_ok(lo_key, lo_len, hi_key, hi_len)) return rc;
     const int64_t nbytes = n ? key_offsets[n] : 0;
@@ -1843,14 +2037,15 @@ int fdbcs_history_import(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t 
         HIPOK(hipMemcpyAsync(cs->i_off.p, key_offsets, 8 * (size_t)(n + 1), hipMemcpyHostToDevice, s));
         HIPOK(hipMemcpyAsync(cs->i_ver.p, versions, 8 * (size_t)n, hipMemcpyHostToDevice, s));
     }
-    rc = import_device(cs, lo_key, lo_len, hi_key, hi_len, n, (const uint8_t*)cs->i_bytes.p, nbytes,
-                       (const int64_t*)cs->i_off.p, (const int64_t*)cs->i_ver.p, header_version, boundaries_out);
+    rc = (to_delta ? import_delta_device : import_device)(
+        cs, lo_key, lo_len, hi_key, hi_len, n, (const uint8_t*)cs->i_bytes.p, nbytes, (const int64_t*)cs->i_off.p,
+        (const int64_t*)cs->i_ver.p, header_version, boundaries_out);
     cs->i_ms_host = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return rc;
 }
 
-int fdbcs_history_import_pending(fdbcs_conflict_set* dst, fdbcs_conflict_set* src, const uint8_t* lo_key, int32_t lo_len,
-                                 const uint8_t* hi_key, int32_t hi_len, int64_t* boundaries_out) {
+static int import_pending(fdbcs_conflict_set* dst, fdbcs_conflict_set* src, const uint8_t* lo_key, int32_t lo_len,
+                          const uint8_t* hi_key, int32_t hi_len, int64_t* boundaries_out, bool to_delta) {
     if (!dst || !src || src == dst || !boundaries_out || src->device != dst->device) return FDBCS_E_INVALID;
     if (int rc = import_bounds_ok(lo_key, lo_len, hi_key, hi_len)) return rc;
     if (dst->inflight || src->inflight || !src->x_valid) return FDBCS_E_STATE;
@@ -1860,11 +2055,45 @@ int fdbcs_history_import_pending(fdbcs_conflict_set* dst, fdbcs_conflict_set* sr
     dst->x_valid = false;
     // src's export finished on its own stream before fdbcs_history_export returned: its result
     // arrays are read in place, and stay pending
-    const int rc = import_device(dst, lo_key, lo_len, hi_key, hi_len, src->x_n, (const uint8_t*)src->x_bytes.p,
-                                 src->x_nbytes, (const int64_t*)src->x_off.p, (const int64_t*)src->x_ver.p, src->x_hdr,
-                                 boundaries_out);
+    const int rc = (to_delta ? import_delta_device : import_device)(
+        dst, lo_key, lo_len, hi_key, hi_len, src->x_n, (const uint8_t*)src->x_bytes.p, src->x_nbytes,
+        (const int64_t*)src->x_off.p, (const int64_t*)src->x_ver.p, src->x_hdr, boundaries_out);
     dst->i_ms_host = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return rc;
+}
+
+int fdbcs_history_import(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key,
+                         int32_t hi_len, int64_t n, const uint8_t* key_bytes, const int64_t* key_offsets,
+                         const int64_t* versions, int64_t header_version, int64_t* boundaries_out) {
+    return import_arrays(cs, lo_key, lo_len, hi_key, hi_len, n, key_bytes, key_offsets, versions, header_version,
+                         boundaries_out, false);
+}
+
+int fdbcs_history_import_pending(fdbcs_conflict_set* dst, fdbcs_conflict_set* src, const uint8_t* lo_key, int32_t lo_len,
+                                 const uint8_t* hi_key, int32_t hi_len, int64_t* boundaries_out) {
+    return import_pending(dst, src, lo_key, lo_len, hi_key, hi_len, boundaries_out, false);
+}
+
+int fdbcs_history_import_delta(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key,
+                               int32_t hi_len, int64_t n, const uint8_t* key_bytes, const int64_t* key_offsets,
+                               const int64_t* versions, int64_t header_version, int64_t* boundaries_out) {
+    return import_arrays(cs, lo_key, lo_len, hi_key, hi_len, n, key_bytes, key_offsets, versions, header_version,
+                         boundaries_out, true);
+}
+
+int fdbcs_history_import_delta_pending(fdbcs_conflict_set* dst, fdbcs_conflict_set* src, const uint8_t* lo_key,
+                                       int32_t lo_len, const uint8_t* hi_key, int32_t hi_len, int64_t* boundaries_out) {
+    return import_pending(dst, src, lo_key, lo_len, hi_key, hi_len, boundaries_out, true);
+}
+
+int fdbcs_history_import_info(fdbcs_conflict_set* cs, int32_t* path, int64_t* base_boundaries, int64_t* delta_before,
+                              int64_t* delta_after) {
+    if (!cs || !path || !base_boundaries || !delta_before || !delta_after) return FDBCS_E_INVALID;
+    *path = cs->i_path;
+    *base_boundaries = cs->i_info_base;
+    *delta_before = cs->i_info_before;
+    *delta_after = cs->i_info_after;
+    return FDBCS_OK;
 }
 
 int fdbcs_history_import_timing(fdbcs_conflict_set* cs, double* ms_kernels, double* ms_host) {

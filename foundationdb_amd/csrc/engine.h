@@ -589,4 +589,43 @@ void launch_import_fold(hipStream_t s, const ImportArgs& a, int64_t m, uint64_t*
 // The greatest version of the tier whose levels `m` were just rebuilt, into *out (device, atomicMax).
 void launch_import_max(hipStream_t s, const MaxLevels& m, int64_t lvl3_n, int64_t* out);
 
+// ---- history import into the delta tier (fdbcs_history_import_delta / _delta_pending): the same
+// definition, written as delta boundaries over [lo, hi) only.  Reads the current buffers, writes only
+// scratch, the non-current delta buffer and arena bytes past tail_used; the host switches on success.
+// Device words of one delta import (zeroed before its launches).
+enum ImportDeltaWord {
+    kIdError,      // int: 4 a merged position out of range, 8 a capacity bound
+    kIdPlo,        // delta boundaries below lo
+    kIdPhi,        // delta boundaries below hi
+    kIdQlo,        // base boundaries below lo
+    kIdQhi,        // base boundaries below hi
+    kIdEver,       // the delta's value at hi: the version of its last boundary <= hi, kHole if none
+    kIdEskip,      // the delta has a boundary at hi (no closing boundary is written)
+    kIdKept,       // boundaries the fold wrote at the delta position of lo
+    kIdTailUnits,  // 8-byte units it appended to the arena
+    kIdScan,       // int counter, int error of the fold's scan
+    kIdWords = 12
+};
+struct ImportDeltaArgs {
+    // the tiers, the imported arrays, the overlay and the merged arrays as for the fold; dst is the
+    // non-current delta buffer (dst_cap its capacity), tdst the current arena (tdst_units its capacity)
+    ImportArgs a;
+    int64_t* dwords;       // [kIdWords] ImportDeltaWord
+    // what k_impd_bounds found, read back by the host and passed to the later launches by value
+    int64_t p_lo, p_hi;    // the delta's boundaries in the range: [p_lo, p_hi)
+    int64_t q_lo, q_hi;    // the base's: [q_lo, q_hi)
+    int64_t mr;            // overlay boundaries in the range: [0, mr) (all but the closing one)
+    int64_t R;             // boundaries of the three in the range; with an upper bound the closing
+                           // boundary takes position R of the merged arrays
+    int64_t e_ver;         // its version (kIdEver)
+    int32_t e_skip;        // kIdEskip
+    int64_t tail_base;     // first free unit of the arena (tail_used / 8)
+};
+// Positions of lo and hi in both tiers and the delta's value at hi; after launch_import_overlay, in
+// phase 1 (the host reads both word blocks in one go).
+void launch_import_delta_bounds(hipStream_t s, const ImportDeltaArgs& d);
+// Rank the three streams' boundaries inside the range, fold them into the non-current delta buffer at
+// p_lo and copy the delta's prefix and suffix around them (phase 2).
+void launch_import_delta_merge(hipStream_t s, const ImportDeltaArgs& d, uint64_t* granules);
+
 }  // namespace fdbcs

@@ -5061,4 +5061,242 @@ void launch_import_fold(hipStream_t s, const ImportArgs& a, int64_t m, uint64_t*
     launch_scan<2>(s, ImportFold{a}, (const int64_t*)nullptr, a.nb + a.nd + m, st);
 }
 
+// ------------------------------------------------------------------ history import into the delta tier
+//
+// The same H' as above, written as delta boundaries over [lo, hi) instead of a new base: the work is
+// O(boundaries of the three streams inside the range + size of the delta), whatever the base holds.
+// Inside the range the new delta carries H' at every key where a stream has a boundary, base
+// boundaries included (equal neighbours coalesced), so no delta entry at an imported version spans a
+// base boundary of a greater one (the delta invariant: a delta version is kHole or at least every
+// base version it covers).  The boundary at lo is always written; at hi a closing boundary carries
+// what the delta held there before (as the E of a batch merge), unless the delta has a boundary at
+// hi.  Outside the range the delta is copied as it is.
+//   k_impd_bounds     positions of lo and hi in the base and in the delta (plain binary searches,
+//                     full key compare), the delta's value at hi
+//   k_impd_rank<S>    k_import_rank<S> over the sub-ranges only: one lane per boundary of stream S
+//                     inside the range, its place among the three in-range streams (on equal keys
+//                     delta, overlay, base) and H' at its key.  Values come from the whole tiers
+//                     (the boundary covering lo may lie before the range); the searches are plain
+//                     binary searches over the sub-ranges, log2(range) steps instead of log2(tier)
+//                     (the base's directory, lane_lower_bound, is not used: an in-range search is
+//                     already short, and the base boundaries again search only integer arrays).
+//   k_scan<ImportDeltaFold>  flags value changes along the in-range stream, scans (kept, tail units
+//                     of kept overlay keys) on granules of the import's own and writes the kept
+//                     boundaries into the non-current delta buffer from p_lo on, one lane each.
+//                     Base and delta boundaries keep their tail offsets (the arena is shared);
+//                     kept overlay keys longer than 16 bytes append theirs past tail_used.
+//   k_impd_copy       the delta's prefix [0, p_lo) as it is and its suffix [p_hi, nd) shifted behind
+//                     the kept boundaries, grid-stride.
+// The greatest version is read off the rebuilt delta's top level (k_import_max), never per element.
+
+__device__ __forceinline__ void impd_key(const Hist& h, int64_t i, const uint8_t* arena, DKey& q,
+                                         const uint8_t*& qtail) {
+    const ulonglong2 k = h.key[i];
+    const uint2 lt = h.lt[i];
+    q.hi = k.x;
+    q.lo = k.y;
+    q.len = lt.x;
+    q.tail = 0;  // the query's tail starts at qtail
+    qtail = hist_tail(arena, lt.x > 16u ? lt.y : 0u);
+}
+
+// Boundaries of h[lo, hi) below q counted from 0 (the answer lies in [lo, hi]), and whether the
+// next one equals it.
+__device__ __forceinline__ int64_t impd_lower(const Hist& h, int64_t lo, int64_t hi, const uint8_t* arena,
+                                              const DKey& q, const uint8_t* qtail, bool& exact) {
+    const int64_t end = hi;
+    while (lo < hi) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (hist_cmp(h, mid, arena, q, qtail) < 0)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    exact = lo < end && hist_cmp(h, lo, arena, q, qtail) == 0;
+    return lo;
+}
+
+__global__ __launch_bounds__(64) void k_impd_bounds(ImportDeltaArgs d) {
+    const ImportArgs& a = d.a;
+    __shared__ int64_t r[4];  // boundaries below lo in base, delta; below hi in base, delta
+    const int t = threadIdx.x;
+    const int64_t m = a.words[kIwM];
+    // an invalid import leaves nothing to place (the host refuses it after reading the words)
+    const bool ok = a.words[kIwError] == 0 && m >= (a.has_lo ? 1 : 0) + (a.has_hi ? 1 : 0) && m <= a.n + 2;
+    if (t < 4) {
+        const bool is_hi = t >= 2, is_delta = t & 1;
+        const int64_t n = is_delta ? a.nd : a.nb;
+        int64_t x = is_hi ? n : 0;
+        if (ok && (is_hi ? a.has_hi : a.has_lo)) {
+            DKey q;
+            const uint8_t* qtail;
+            impd_key(a.ov, is_hi ? m - 1 : 0, a.otail, q, qtail);
+            x = export_bound(is_delta ? a.delta : a.base, n, a.htail, q, qtail, false);
+        }
+        r[t] = x;
+    }
+    __syncthreads();
+    if (t != 0) return;
+    const int64_t q_lo = r[0], p_lo = r[1], q_hi = r[2] > r[0] ? r[2] : r[0], p_hi = r[3] > r[1] ? r[3] : r[1];
+    int64_t skip = 0;
+    if (ok && a.has_hi && p_hi < a.nd) {
+        DKey q;
+        const uint8_t* qtail;
+        impd_key(a.ov, m - 1, a.otail, q, qtail);
+        skip = hist_cmp(a.delta, p_hi, a.htail, q, qtail) == 0 ? 1 : 0;
+    }
+    d.dwords[kIdPlo] = p_lo;
+    d.dwords[kIdPhi] = p_hi;
+    d.dwords[kIdQlo] = q_lo;
+    d.dwords[kIdQhi] = q_hi;
+    d.dwords[kIdEver] = p_hi > 0 ? a.delta.ver[p_hi - 1] : kHole;
+    d.dwords[kIdEskip] = skip;
+}
+
+// S: the stream of this launch's elements (0 base, 1 delta, 2 overlay), one lane per boundary inside
+// the range; the overlay's launch has one more lane for the closing boundary.
+template <int S>
+__global__ __launch_bounds__(kBlock) void k_impd_rank(ImportDeltaArgs d) {
+    const ImportArgs& a = d.a;
+    const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t ndr = d.p_hi - d.p_lo, nbr = d.q_hi - d.q_lo;
+    if (i0 >= (S == 0 ? nbr : S == 1 ? ndr : d.mr + (a.has_hi ? 1 : 0))) return;
+    if (S == 2 && i0 == d.mr) {  // the closing boundary: hi's key, the delta's old value there
+        const uint2 lt = a.ov.lt[i0];
+        a.m_val[d.R] = d.e_ver;
+        a.m_key[d.R] = a.ov.key[i0];
+        a.m_lt[d.R] = make_uint2(lt.x | kImportOvTail, lt.x > 16u ? lt.y : 0u);
+        return;
+    }
+    const int64_t i = i0 + (S == 0 ? d.q_lo : S == 1 ? d.p_lo : 0);
+    const Hist& h = S == 0 ? a.base : S == 1 ? a.delta : a.ov;
+    const ulonglong2 k = h.key[i];
+    const uint2 lt = h.lt[i];
+    DKey q;
+    const uint8_t* qtail;
+    impd_key(h, i, S == 2 ? a.otail : a.htail, q, qtail);
+    // boundaries below the key (lt) and at or below it (le) in each stream, counted over the whole stream
+    int64_t b_lt = i, b_le = i + 1, d_lt = i, d_le = i + 1, v_lt = i, v_le = i + 1;
+    [[maybe_unused]] bool ex;
+    if constexpr (S == 0) {
+        // as k_import_rank<0>: the in-range delta / overlay boundaries at or below base key i are
+        // those with at most i base boundaries below them (k_impd_rank<1>, <2> ran first)
+        d_le = d.p_lo + import_count_le(a.d_blt + d.p_lo, ndr, i);
+        v_le = import_count_le(a.v_blt, d.mr, i);
+    } else {
+        b_lt = impd_lower(a.base, d.q_lo, d.q_hi, a.htail, q, qtail, ex);
+        b_le = b_lt + (ex ? 1 : 0);
+        (S == 1 ? a.d_blt : a.v_blt)[i] = b_lt;
+    }
+    if constexpr (S == 2) {
+        d_lt = impd_lower(a.delta, d.p_lo, d.p_hi, a.htail, q, qtail, ex);
+        d_le = d_lt + (ex ? 1 : 0);
+    }
+    if constexpr (S == 1) {
+        v_lt = impd_lower(a.ov, 0, d.mr, a.otail, q, qtail, ex);
+        v_le = v_lt + (ex ? 1 : 0);
+    }
+    // on equal keys: delta, then overlay, then base; positions count from the range's start
+    const int64_t pos = S == 1   ? (d_lt - d.p_lo) + v_lt + (b_lt - d.q_lo)
+                        : S == 2 ? v_lt + (d_le - d.p_lo) + (b_lt - d.q_lo)
+                                 : (b_lt - d.q_lo) + (d_le - d.p_lo) + v_le;
+    const int64_t dv = d_le > 0 ? a.delta.ver[d_le - 1] : kHole;
+    const int64_t bv = b_le > 0 ? a.base.ver[b_le - 1] : a.hdr;
+    const int64_t ov = v_le > 0 ? a.ov.ver[v_le - 1] : a.ovhdr;
+    int64_t v = dv != kHole ? dv : bv;
+    if (ov != kHole && ov > v) v = ov;
+    if (pos < 0 || pos >= d.R) {  // streams out of order: never index past the merged arrays
+        atomicOr((int*)&d.dwords[kIdError], 4);
+        return;
+    }
+    a.m_val[pos] = v;
+    a.m_key[pos] = k;
+    a.m_lt[pos] = make_uint2(lt.x | (S == 2 ? kImportOvTail : 0u), lt.x > 16u ? lt.y : 0u);
+}
+
+struct ImportDeltaFold {
+    ImportDeltaArgs d;
+    __device__ bool keep(int64_t p) const {
+        const ImportArgs& a = d.a;
+        if (p == d.R && d.e_skip) return false;  // the delta's own boundary at hi follows
+        // the boundary at lo always stands; without a lower bound the delta's implicit header is a hole
+        if (p == 0) return a.has_lo || a.m_val[0] != kHole;
+        return a.m_val[p] != a.m_val[p - 1];
+    }
+    // [0] kept boundaries, [1] tail units appended to the arena (kept overlay keys only)
+    __device__ void load(int64_t p, uint32_t (&x)[2]) const {
+        const bool kp = keep(p);
+        const uint32_t len = d.a.m_lt[p].x;
+        x[0] = kp ? 1u : 0u;
+        x[1] = kp && (len & kImportOvTail) ? tail_units(len & ~kImportOvTail) : 0u;
+    }
+    __device__ void store(int64_t p, const uint32_t (&ex)[2]) const {
+        if (!keep(p)) return;
+        const ImportArgs& a = d.a;
+        uint2 lt = a.m_lt[p];
+        const bool ovt = (lt.x & kImportOvTail) != 0;
+        lt.x &= ~kImportOvTail;
+        const int64_t o = d.p_lo + (int64_t)ex[0];
+        const uint32_t nu = ovt ? tail_units(lt.x) : 0u;
+        const int64_t unit = d.tail_base + (int64_t)ex[1];
+        if (o >= a.dst_cap || unit + nu > a.tdst_units) {  // never past the buffers the host sized
+            atomicOr((int*)&d.dwords[kIdError], 8);
+            return;
+        }
+        if (nu) {  // past tail_used: invisible until the host raises it
+            const uint64_t* src = (const uint64_t*)hist_tail(a.otail, lt.y);
+            uint64_t* dst = (uint64_t*)(a.tdst + 8 * (size_t)unit);
+            for (uint32_t u = 0; u < nu; u++) dst[u] = src[u];
+            lt.y = (uint32_t)unit;
+        }
+        a.dst.key[o] = a.m_key[p];
+        a.dst.lt[o] = lt;
+        a.dst.ver[o] = a.m_val[p];
+    }
+    __device__ void finish(const uint32_t (&tot)[2]) const {
+        d.dwords[kIdKept] = tot[0];
+        d.dwords[kIdTailUnits] = tot[1];
+    }
+};
+
+__global__ __launch_bounds__(kBlock) void k_impd_copy(ImportDeltaArgs d) {
+    const ImportArgs& a = d.a;
+    const int64_t kept = d.dwords[kIdKept];
+    const int64_t n = a.nd - (d.p_hi - d.p_lo);  // boundaries outside the range
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const bool pre = i < d.p_lo;
+        const int64_t src = pre ? i : d.p_hi + (i - d.p_lo), dst = pre ? i : i + kept;
+        if (dst < 0 || dst >= a.dst_cap) {
+            atomicOr((int*)&d.dwords[kIdError], 8);
+            continue;
+        }
+        a.dst.key[dst] = a.delta.key[src];
+        a.dst.lt[dst] = a.delta.lt[src];
+        a.dst.ver[dst] = a.delta.ver[src];
+    }
+}
+
+void launch_import_delta_bounds(hipStream_t s, const ImportDeltaArgs& d) {
+    fdb_launch(k_impd_bounds, dim3(1), dim3(64), 0, s, d);
+}
+
+void launch_import_delta_merge(hipStream_t s, const ImportDeltaArgs& d, uint64_t* granules) {
+    auto grid = [](int64_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); };
+    const int64_t ndr = d.p_hi - d.p_lo, nbr = d.q_hi - d.q_lo, nv = d.mr + (d.a.has_hi ? 1 : 0);
+    if (ndr > 0) fdb_launch(k_impd_rank<1>, grid(ndr), dim3(kBlock), 0, s, d);
+    if (nv > 0) fdb_launch(k_impd_rank<2>, grid(nv), dim3(kBlock), 0, s, d);
+    if (nbr > 0) fdb_launch(k_impd_rank<0>, grid(nbr), dim3(kBlock), 0, s, d);  // reads d_blt, v_blt
+    ScanState st;
+    st.granules = granules;
+    st.counter = (int*)&d.dwords[kIdScan];
+    st.error = st.counter + 1;
+    const int64_t total = d.R + (d.a.has_hi ? 1 : 0);
+    if (total > 0) launch_scan<2>(s, ImportDeltaFold{d}, (const int64_t*)nullptr, total, st);
+    const int64_t outside = d.a.nd - ndr;
+    if (outside > 0) {
+        const int64_t g = (outside + kBlock - 1) / kBlock;
+        fdb_launch(k_impd_copy, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(kBlock), 0, s, d);
+    }
+}
+
 }  // namespace fdbcs

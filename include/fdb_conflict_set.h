@@ -211,7 +211,44 @@ int fdbcs_history_import(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t 
  * readable. */
 int fdbcs_history_import_pending(fdbcs_conflict_set* dst, fdbcs_conflict_set* src, const uint8_t* lo_key,
                                  int32_t lo_len, const uint8_t* hi_key, int32_t hi_len, int64_t* boundaries_out);
-/* Diagnostics: device time of the last import's kernels and host time of the whole call (ms). */
+/* The same import (same H', same validation, error codes and atomicity: on any error the set is
+ * exactly as before), written into the delta tier only: device work is O(boundaries of the base,
+ * the delta and the import inside [lo, hi) + size of the delta), whatever the base holds.
+ * Inside [lo, hi) the new delta carries H' at every key where H' changes, base boundaries included,
+ * equal neighbours coalesced, so every delta version is still a hole or at least every base version
+ * it covers (no delta entry at an imported version spans a base boundary of a greater one).  With a
+ * lower bound, a delta boundary at lo carries H'(lo); with an upper bound, a delta boundary at hi
+ * carries what the delta held there before (the version of its last boundary <= hi, a hole if
+ * none), unless the delta already has a boundary at hi.  Outside the range the delta is unchanged.
+ * Without a lower bound the set's header becomes max(header, header_version); the delta has no
+ * header of its own.  Kept base and delta boundaries keep their tails; only kept imported keys
+ * longer than 16 bytes append tails to the arena (FDBCS_E_NOMEM at its 32 GiB limit).
+ * When the delta afterwards could pass its bound (delta boundaries + base boundaries in the range +
+ * imported boundaries + 2 over the delta limit) or its capacity cannot grow, the call runs
+ * fdbcs_history_import instead (fdbcs_history_import_info reports path 0): never an error for a
+ * range that call accepts.
+ * *boundaries_out is what fdbcs_history_size returns afterwards: both tiers, an upper bound of the
+ * reference's count as between compactions, not the canonical count (base boundaries in the range
+ * are now also present in the delta, until the next compaction folds them).
+ * A later detect with `now` below the greatest version left in the new delta is FDBCS_E_VERSION (a
+ * great version the range clipped away does not count).  FDBCS_E_STATE with batches in flight.  The
+ * oldest version does not move, no floor is applied, the directory code is kept, and a pending export
+ * of the set is dropped. */
+int fdbcs_history_import_delta(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, /* lo_len < 0: no lower bound */
+                               const uint8_t* hi_key, int32_t hi_len,                       /* hi_len < 0: no upper bound */
+                               int64_t n, const uint8_t* key_bytes, const int64_t* key_offsets,
+                               const int64_t* versions, int64_t header_version, int64_t* boundaries_out);
+/* fdbcs_history_import_delta reading src's pending export, as fdbcs_history_import_pending does. */
+int fdbcs_history_import_delta_pending(fdbcs_conflict_set* dst, fdbcs_conflict_set* src, const uint8_t* lo_key,
+                                       int32_t lo_len, const uint8_t* hi_key, int32_t hi_len,
+                                       int64_t* boundaries_out);
+/* Diagnostics: the last successful import of either kind.  *path: 0 = folded into a new base, 1 =
+ * merged into the delta; *base_boundaries: the base tier afterwards; *delta_before / *delta_after:
+ * the delta tier around it.  All zero before the first import. */
+int fdbcs_history_import_info(fdbcs_conflict_set* cs, int32_t* path, int64_t* base_boundaries,
+                              int64_t* delta_before, int64_t* delta_after);
+/* Diagnostics: device time of the last import's kernels and host time of the whole call (ms), for
+ * the imports of both kinds. */
 int fdbcs_history_import_timing(fdbcs_conflict_set* cs, double* ms_kernels, double* ms_host);
 int fdbcs_get_stats(fdbcs_conflict_set* cs, fdbcs_stats* out);
 int fdbcs_reset_stats(fdbcs_conflict_set* cs);

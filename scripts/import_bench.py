@@ -14,7 +14,13 @@ the merged stream (8 B more to zero it), 32 B plus the tail written per kept bou
 gathers are not counted.  The yardstick is the one the export's bench uses, timed in the same run:
 the engine's own compaction + GC pass over the receiver's tiers, per kernel (timing level 3).
 
-    python3 scripts/import_bench.py [--history N] [--batches B] [--reps R] [--out FILE]
+    python3 scripts/import_bench.py [--history N] [--batches B] [--reps R] [--into base|delta|both] [--out FILE]
+
+--into delta sends the imports through into="delta" (fdbcs_history_import_delta), --into both measures
+every case through the fold and through the delta path on the same receiver in the same run; each
+case then also records the path the engine took (0: fold, 1: delta; the full export passes the delta
+bound and must report 0) and the delta tier's size before and after.  The default, base, is the
+fold alone.
 
 Prints one JSON line per receiver state (and appends them to FILE)."""
 import argparse
@@ -62,7 +68,8 @@ class Receiver:
         return self.cs.history_size()
 
 
-def measure(rcv, snd, lo, hi, pending, warmup, reps):
+def measure(rcv, snd, lo, hi, pending, warmup, reps, into=None):
+    kw = {"into": into} if into else {}
     n, nbytes, hdr = snd.export_history(lo, hi)
     arrays = snd.read_export(n, nbytes)
     if pending:
@@ -72,9 +79,9 @@ def measure(rcv, snd, lo, hi, pending, warmup, reps):
         before = rcv.rebuild()
         t0 = time.perf_counter()
         if pending:
-            after = rcv.cs.merge_pending_export(snd, lo, hi)
+            after = rcv.cs.merge_pending_export(snd, lo, hi, **kw)
         else:
-            after = rcv.cs.merge_history(*arrays, hdr, lo=lo, hi=hi)
+            after = rcv.cs.merge_history(*arrays, hdr, lo=lo, hi=hi, **kw)
         t1 = time.perf_counter()
         k_ms, _ = rcv.cs.import_timing()
         if r >= warmup:
@@ -85,8 +92,13 @@ def measure(rcv, snd, lo, hi, pending, warmup, reps):
     rd = nbytes + 16 * n + 32 * total + 32 * total
     wr = 32 * m + 40 * total + 32 * after
     med = summary(dev)["median"]
+    info = {}
+    if into:
+        i = rcv.cs.import_info()
+        info = {"into": into, "engine_path": i["path"], "base_boundaries": i["base_boundaries"],
+                "delta_before": i["delta_before"], "delta_after": i["delta_after"]}
     return {
-        "path": "pending" if pending else "host_arrays", "range": "full" if lo is None else "1pct",
+        **info, "path": "pending" if pending else "host_arrays", "range": "full" if lo is None else "1pct",
         "imported": int(n), "imported_key_bytes": int(nbytes), "boundaries_before": int(before),
         "boundaries_after": int(after), "bytes_read": int(rd), "bytes_written": int(wr),
         "device_us": summary(dev), "host_call_us": summary(host),
@@ -121,8 +133,10 @@ def main():
     ap.add_argument("--batches", type=int, default=50)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--into", choices=("base", "delta", "both"), default="base")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    intos = {"base": (None,), "delta": ("delta",), "both": ("base", "delta")}[a.into]
     p = W.C2Params(history=a.history)
     start = 10_000_000
     hist = W.c2_history(p, seed=1, start_version=start)
@@ -133,9 +147,10 @@ def main():
         out = {"bench": "import", "history": int(len(hist[2])), "batches": batches, "reps": a.reps, "cases": []}
         for lo, hi in ((None, None), RANGE_1PCT):
             for pending in (False, True):
-                c = measure(rcv, snd, lo, hi, pending, a.warmup, a.reps)
-                print(json.dumps(c), file=sys.stderr, flush=True)
-                out["cases"].append(c)
+                for into in intos:
+                    c = measure(rcv, snd, lo, hi, pending, a.warmup, a.reps, into)
+                    print(json.dumps(c), file=sys.stderr, flush=True)
+                    out["cases"].append(c)
         out["yardstick_us"] = yardstick(rcv)
         out["yardstick_sum_us"] = sum(out["yardstick_us"].values())
         rcv.cs.close()

@@ -6,7 +6,7 @@ read at set creation (directory slot budget, split check, stream layout, submitt
 compaction and GC cadence, and a sequence of batches whose snapshots straddle the oldest version; verdicts and
 conflicting-read reports must match oracle/skiplist_baseline.cpp batch by batch.
 
-    python3 scripts/stress_parity.py [seconds] [first_seed] [--state-every K] [--import-every K]
+    python3 scripts/stress_parity.py [seconds] [first_seed] [--state-every K] [--import-every K] [--import-into delta]
 
 --state-every K (default off) also feeds the semantic oracle and compares the engine's exported
 history (ConflictSet.dump_history at floor = oldest version) with the canonical form of the oracle's
@@ -18,6 +18,10 @@ random key range of a second set's history into the engine (ConflictSet.merge_hi
 time merge_pending_export), compares the exported state with merge_max over the canonical forms
 (tests/import_helpers.py) and reloads both oracles with it, so the batches that follow check the
 verdicts the merged history gives.
+
+--import-into delta sends those merges through into="delta" (fdbcs_history_import_delta, which falls
+back to the fold when the delta could pass its bound); the final line counts the merges that took
+the delta path.
 
 Exit status 1 and the failing seed on the first mismatch."""
 import os
@@ -45,7 +49,10 @@ KNOBS = {
 }
 
 
-def merge_round(rng, e, o, so, key, hdr, now, pending):
+PATHS = [0, 0]  # merges that folded into a new base / went into the delta (import_info)
+
+
+def merge_round(rng, e, o, so, key, hdr, now, pending, into="base"):
     """Merge a random range of a second set's random history (versions up to `now`) into the engine
     and reload the oracles with merge_max; returns (error, the first set's header afterwards)."""
     ks = sorted({key(True) for _ in range(int(rng.integers(0, 3000)))})
@@ -62,13 +69,14 @@ def merge_round(rng, e, o, so, key, hdr, now, pending):
     want = canon(merged[1], merged[2], merged[0], oldest)
     if pending:
         e2.export_history(lo, hi, C.NO_FLOOR)
-        e.cs.merge_pending_export(e2, lo, hi)
+        e.cs.merge_pending_export(e2, lo, hi, into=into)
     else:
-        e.cs.merge_history(*dump, lo=lo, hi=hi)
+        e.cs.merge_history(*dump, lo=lo, hi=hi, into=into)
+    PATHS[e.cs.import_info()["path"]] += 1
     e2.close()
     got = split_dump(e.cs.dump_history())
     if got != want:
-        return f"merged state [{lo!r}, {hi!r}) pending={pending}: {len(got[1])} boundaries, merge_max {len(want[1])}", hdr
+        return f"merged state [{lo!r}, {hi!r}) pending={pending} into={into}: {len(got[1])} boundaries, merge_max {len(want[1])}", hdr
     kb, ko, vv, h = pack(want)
     for x in (o, so):
         if len(vv):
@@ -79,7 +87,7 @@ def merge_round(rng, e, o, so, key, hdr, now, pending):
     return None, h
 
 
-def one(seed, state_every=0, import_every=0):
+def one(seed, state_every=0, import_every=0, import_into="base"):
     rng = np.random.default_rng(seed)
     for k, vals in KNOBS.items():
         os.environ[k] = vals[int(rng.integers(0, len(vals)))]
@@ -151,7 +159,7 @@ def one(seed, state_every=0, import_every=0):
                 if got != want:
                     return f"exported state batch {i}: {len(got[1])} boundaries, oracle {len(want[1])}"
             if import_every and (i + 1) % import_every == 0:
-                err, hdr = merge_round(rng, e, o, so, key, hdr, now, merges & 1)
+                err, hdr = merge_round(rng, e, o, so, key, hdr, now, merges & 1, import_into)
                 merges += 1
                 if err:
                     return f"batch {i}: {err}"
@@ -172,13 +180,18 @@ def main():
         import_every = int(args[k + 1])
         del args[k:k + 2]
         state_every = state_every or 1
+    import_into = "base"
+    if "--import-into" in args:
+        k = args.index("--import-into")
+        import_into = args[k + 1]
+        del args[k:k + 2]
     budget = float(args[0]) if len(args) > 0 else 120.0
     seed = int(args[1]) if len(args) > 1 else 1
     oracle.build()
     t0 = time.time()
     n = 0
     while time.time() - t0 < budget:
-        err = one(seed, state_every, import_every)
+        err = one(seed, state_every, import_every, import_into)
         knobs = {k: os.environ[k] for k in KNOBS}
         if err:
             print(f"MISMATCH seed {seed} knobs {knobs}: {err}", flush=True)
@@ -188,6 +201,8 @@ def main():
             print(f"{n} rounds ok ({time.time() - t0:.0f} s), last seed {seed}", flush=True)
         seed += 1
     print(f"stress: {n} random rounds, every batch exact ({time.time() - t0:.0f} s)")
+    if import_every:
+        print(f"stress: {PATHS[1]} merges into the delta, {PATHS[0]} folded into a new base")
 
 
 if __name__ == "__main__":
