@@ -415,8 +415,9 @@ struct fdbcs_conflict_set {
     int64_t x_hdr = 0;                            // the pending result's header version
     // fdbcs_history_import: device copies of the imported arrays (host-array form), the bounds' bytes,
     // the overlay stream (keys, lt, versions, tails), the merged stream (value, key, lt) and the import
-    // words + scan granules; all allocated by the first import and freed with the set.
+    // words; all allocated by the first import and freed with the set.
     DBuf i_bytes, i_off, i_ver, i_bnd, i_okey, i_olt, i_over, i_otail, i_mval, i_mkey, i_mlt, i_dblt, i_vblt, i_state;
+    DBuf i_gran;                                  // the fold's scan granules
     hipEvent_t i_ev[6] = {};                      // around the import's three groups of kernels
     double i_ms_kernels = 0, i_ms_host = 0;       // of the last import (fdbcs_history_import_timing)
     // fdbcs_history_import_delta: its words + scan granules (allocated by the first delta import), and
@@ -1426,7 +1427,8 @@ void fdbcs_destroy_conflict_set(fdbcs_conflict_set* cs) {
     if (cs->x_ev0) (void)hipEventDestroy(cs->x_ev0);
     if (cs->x_ev1) (void)hipEventDestroy(cs->x_ev1);
     for (DBuf* x : {&cs->i_bytes, &cs->i_off, &cs->i_ver, &cs->i_bnd, &cs->i_okey, &cs->i_olt, &cs->i_over, &cs->i_otail,
-                    &cs->i_mval, &cs->i_mkey, &cs->i_mlt, &cs->i_dblt, &cs->i_vblt, &cs->i_state, &cs->i_dstate})
+                    &cs->i_mval, &cs->i_mkey, &cs->i_mlt, &cs->i_dblt, &cs->i_vblt, &cs->i_state,
+                    &cs->i_gran, &cs->i_dstate})
         x->release();
     for (hipEvent_t e : cs->i_ev)
         if (e) (void)hipEventDestroy(e);
@@ -1693,46 +1695,81 @@ static void import_note(fdbcs_conflict_set* cs, int32_t path, int64_t base, int6
     cs->i_info_after = delta_after;
 }
 
-// The import proper, on device arrays (both entry points end here).  The set is idle, its streams
-// drained; d_bytes is 8-byte aligned with >= 16 readable bytes past nbytes.  The host does no
-// per-boundary work: it sizes buffers from n and nbytes, reads the import words back after the
-// validation and after the fold and, on success, switches to the base buffer and tail arena the
-// kernels filled.
-static int import_device(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key,
+// What phase 1 of an import leaves for its continuation.
+struct ImportPlan {
+    Scalars sc;            // the set's scalars before the import
+    int64_t m;             // overlay boundaries
+    int64_t u_end;         // 8-byte units of the overlay's tail arena
+    ImportDeltaArgs d;     // d.a: the arguments both imports share; the rest is the delta import's
+    int64_t dw[kIdWords];  // what k_impd_bounds found (to_delta only)
+};
+
+// The tier pointers of an import's arguments (again after a capacity change: the buffers may have
+// moved).  The fold writes the non-current base buffer and arena, the delta import the non-current
+// delta buffer and the current arena.
+static void import_tiers(fdbcs_conflict_set* cs, ImportArgs& a, bool to_delta) {
+    a.base = hist_of(cs, cs->cur);
+    a.delta = delta_of(cs, cs->dcur);
+    a.htail = (const uint8_t*)cs->htail[cs->tcur].p;
+    a.dst = to_delta ? delta_of(cs, cs->dcur ^ 1) : hist_of(cs, cs->cur ^ 1);
+    a.tdst = (uint8_t*)cs->htail[to_delta ? cs->tcur : cs->tcur ^ 1].p;
+    a.dst_cap = to_delta ? cs->delta_cap : cs->hist_cap;
+    a.tdst_units = cs->tail_cap / 8;
+}
+
+// The merged arrays of phase 2, for `total` positions.
+static int import_merged(fdbcs_conflict_set* cs, ImportArgs& a, int64_t total) {
+    int rc;
+    if ((rc = cs->i_mval.ensure(8 * (size_t)total))) return rc;
+    if ((rc = cs->i_mkey.ensure(16 * (size_t)total))) return rc;
+    if ((rc = cs->i_mlt.ensure(8 * (size_t)total))) return rc;
+    if ((rc = cs->i_dblt.ensure(8 * (size_t)(a.nd + 1)))) return rc;
+    a.m_val = (int64_t*)cs->i_mval.p;
+    a.m_key = (ulonglong2*)cs->i_mkey.p;
+    a.m_lt = (uint2*)cs->i_mlt.p;
+    a.d_blt = (int64_t*)cs->i_dblt.p;
+    return FDBCS_OK;
+}
+
+// Phase 1 of both imports, on device arrays.  The set is idle, its streams drained; d_bytes is
+// 8-byte aligned with >= 16 readable bytes past nbytes.  The host does no per-boundary work: it
+// sizes the overlay from n and nbytes, launches the validation and the overlay's build (to_delta:
+// and the search that places lo and hi in both tiers) and reads the words back once.  *done: the
+// import is over (an empty range: validated, nothing to do).
+static int import_phase1(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key,
                          int32_t hi_len, int64_t n, const uint8_t* d_bytes, int64_t nbytes, const int64_t* d_off,
-                         const int64_t* d_ver, int64_t ihdr, int64_t* boundaries_out) {
-    Scalars sc;
+                         const int64_t* d_ver, int64_t ihdr, int64_t* boundaries_out, bool to_delta, ImportPlan& pl,
+                         bool* done) {
+    *done = false;
+    Scalars& sc = pl.sc;
     HIPOK(hipMemcpy(&sc, cs->scal.p, sizeof(sc), hipMemcpyDeviceToHost));
     const int64_t nb = sc.n, nd = sc.ndb[cs->dcur];
-    const int64_t total_ub = nb + nd + n + 2;
-    if (total_ub >= ((int64_t)1 << 31)) return FDBCS_E_NOMEM;  // the fold's 32-bit scan components
+    if (nb + nd + n + 2 >= ((int64_t)1 << 31)) return FDBCS_E_NOMEM;  // the fold's 32-bit scan components
     const bool has_lo = lo_len >= 0, has_hi = hi_len >= 0;
     const int64_t ll = has_lo ? lo_len : 0, hl = has_hi ? hi_len : 0;
     // overlay tails, in 8-byte units: imported boundary j at (offset_j >> 3) + j, then lo's and hi's
     const int64_t u_lo = ((nbytes + 7) >> 3) + n + 1, u_hi = u_lo + ((ll + 7) >> 3) + 1, u_end = u_hi + ((hl + 7) >> 3) + 1;
-    const int64_t tail_need = sc.tail_used + 8 * u_end;
+    // the fold packs at most that many units behind the arena's bytes, the delta import appends
+    // them from the next whole unit on
+    const int64_t tail_base = (sc.tail_used + 7) >> 3;
+    const int64_t tail_need = to_delta ? 8 * (tail_base + u_end) : sc.tail_used + 8 * u_end;
     if (tail_need + 1 >= kTailLimit) return FDBCS_E_NOMEM;
     int rc;
-    if ((rc = ensure_history(cs, total_ub + 1, tail_need + 1))) return rc;
     const int64_t bnd_hi = (ll + 7) / 8 * 8 + 16;
-    const int64_t gran = scan_granules(total_ub, 2);
     if ((rc = cs->i_bnd.ensure((size_t)(bnd_hi + hl + 64)))) return rc;
     if ((rc = cs->i_okey.ensure(16 * (size_t)(n + 2)))) return rc;
     if ((rc = cs->i_olt.ensure(8 * (size_t)(n + 2)))) return rc;
     if ((rc = cs->i_over.ensure(8 * (size_t)(n + 2)))) return rc;
     if ((rc = cs->i_otail.ensure(8 * (size_t)u_end + kTailSlack))) return rc;
-    if ((rc = cs->i_mval.ensure(8 * (size_t)total_ub))) return rc;
-    if ((rc = cs->i_mkey.ensure(16 * (size_t)total_ub))) return rc;
-    if ((rc = cs->i_mlt.ensure(8 * (size_t)total_ub))) return rc;
-    if ((rc = cs->i_dblt.ensure(8 * (size_t)(nd + 1)))) return rc;
     if ((rc = cs->i_vblt.ensure(8 * (size_t)(n + 2)))) return rc;
-    if ((rc = cs->i_state.ensure(8 * (size_t)(kIwWords + gran)))) return rc;
+    if ((rc = cs->i_state.ensure(8 * (size_t)kIwWords))) return rc;
+    if (to_delta && (rc = cs->i_dstate.ensure(8 * (size_t)kIdWords))) return rc;
     for (hipEvent_t& e : cs->i_ev)
         if (!e) HIPOK(hipEventCreate(&e));
-    ImportArgs a{};
-    a.base = hist_of(cs, cs->cur);
-    a.delta = delta_of(cs, cs->dcur);
-    a.htail = (const uint8_t*)cs->htail[cs->tcur].p;
+    pl.u_end = u_end;
+    pl.d = ImportDeltaArgs{};
+    ImportArgs& a = pl.d.a;
+    import_tiers(cs, a, to_delta);
     a.nb = nb;
     a.nd = nd;
     a.hdr = cs->header_version;
@@ -1756,44 +1793,88 @@ static int import_device(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t 
     a.otail_hi = u_hi;
     a.ovhdr = has_lo ? kHole : ihdr;
     a.words = (int64_t*)cs->i_state.p;
-    a.m_val = (int64_t*)cs->i_mval.p;
-    a.m_key = (ulonglong2*)cs->i_mkey.p;
-    a.m_lt = (uint2*)cs->i_mlt.p;
-    a.d_blt = (int64_t*)cs->i_dblt.p;
     a.v_blt = (int64_t*)cs->i_vblt.p;
-    a.dst = hist_of(cs, cs->cur ^ 1);
-    a.tdst = (uint8_t*)cs->htail[cs->tcur ^ 1].p;
-    a.dst_cap = cs->hist_cap;
-    a.tdst_units = cs->tail_cap / 8;
     a.new_hdr = has_lo ? cs->header_version : std::max(cs->header_version, ihdr);
+    pl.d.dwords = (int64_t*)cs->i_dstate.p;
+    pl.d.tail_base = tail_base;
     hipStream_t s = cs->stream;
     if (ll) HIPOK(hipMemcpyAsync(cs->i_bnd.p, lo_key, (size_t)ll, hipMemcpyHostToDevice, s));
     if (hl) HIPOK(hipMemcpyAsync((uint8_t*)cs->i_bnd.p + bnd_hi, hi_key, (size_t)hl, hipMemcpyHostToDevice, s));
-    HIPOK(hipMemsetAsync(cs->i_state.p, 0, 8 * (size_t)(kIwWords + gran), s));
+    HIPOK(hipMemsetAsync(cs->i_state.p, 0, 8 * (size_t)kIwWords, s));
+    if (to_delta) HIPOK(hipMemsetAsync(cs->i_dstate.p, 0, 8 * (size_t)kIdWords, s));
     const int64_t none = kHole;
     HIPOK(hipMemcpyAsync(&a.words[kIwMaxVer], &none, 8, hipMemcpyHostToDevice, s));
     int64_t words[kIwWords];
     HIPOK(hipEventRecord(cs->i_ev[0], s));
     launch_import_overlay(s, a);
+    if (to_delta) launch_import_delta_bounds(s, pl.d);
     HIPOK(take_launch_error());
     HIPOK(hipEventRecord(cs->i_ev[1], s));
     HIPOK(hipMemcpyAsync(words, cs->i_state.p, sizeof(words), hipMemcpyDeviceToHost, s));
+    if (to_delta) HIPOK(hipMemcpyAsync(pl.dw, cs->i_dstate.p, sizeof(pl.dw), hipMemcpyDeviceToHost, s));
     HIPOK(hipStreamSynchronize(s));
     cs->i_ms_kernels = ev_ms(cs->i_ev[0], cs->i_ev[1]);
     if ((int32_t)words[kIwError] & 1) return FDBCS_E_INVALID;
     if (words[kIwError]) return FDBCS_E_DEVICE;
-    if (has_lo && has_hi && cmp_bytes(lo_key, lo_len, hi_key, hi_len) == 0) {  // an empty range: validated, nothing to do
+    if (has_lo && has_hi && cmp_bytes(lo_key, lo_len, hi_key, hi_len) == 0) {
         *boundaries_out = nb + nd;
-        import_note(cs, 0, nb, nd, nd);
+        import_note(cs, to_delta ? 1 : 0, nb, nd, nd);
+        *done = true;
         return FDBCS_OK;
     }
-    const int64_t m = words[kIwM];
-    if (m < 0 || m > n + 2) return FDBCS_E_DEVICE;
+    pl.m = words[kIwM];
+    if (pl.m < (has_lo ? 1 : 0) + (has_hi ? 1 : 0) || pl.m > n + 2) return FDBCS_E_DEVICE;
+    return FDBCS_OK;
+}
+
+// The end both imports share, once the device scalars hold the new sizes: rebuild the range-max
+// levels of the tier that changed (n_new boundaries), read its greatest version off their top and
+// raise the set's header and greatest written version.
+static int import_finish(fdbcs_conflict_set* cs, const ImportArgs& a, bool delta_tier, int64_t n_new) {
+    hipStream_t s = cs->stream;
+    Scalars* dsc = (Scalars*)cs->scal.p;
+    const MaxLevels lv = delta_tier ? dlevels_of(cs, cs->dcur) : levels_of(cs, cs->cur);
+    const int64_t lvl3_n = delta_tier ? cs->dlvl3_n : cs->lvl3_n, lvl2_n = delta_tier ? cs->dlvl2_n : cs->lvl2_n;
+    HIPOK(hipEventRecord(cs->i_ev[4], s));
+    launch_rangemax(s, lv, dsc, delta_tier ? &dsc->ndb[cs->dcur] : &dsc->n, lvl3_n, lvl2_n,
+                    std::max<int64_t>(n_new, 1));
+    // the top of the rebuilt levels (holes are INT64_MIN), never a pass over the elements
+    launch_import_max(s, lv, lvl3_n, &a.words[kIwMaxVer]);
+    HIPOK(take_launch_error());
+    HIPOK(hipEventRecord(cs->i_ev[5], s));
+    int64_t max_ver;
+    HIPOK(hipMemcpyAsync(&max_ver, &a.words[kIwMaxVer], 8, hipMemcpyDeviceToHost, s));
+    HIPOK(hipStreamSynchronize(s));
+    cs->i_ms_kernels += ev_ms(cs->i_ev[4], cs->i_ev[5]);
+    cs->header_version = a.new_hdr;
+    cs->max_written = std::max({cs->max_written, a.new_hdr, max_ver});
+    cs->ddir_epoch[0] = cs->ddir_epoch[1] = 0;  // the delta's directory: not trusted until an epilogue refills it
+    cs->prev_segs = false;
+    return FDBCS_OK;
+}
+
+// Phase 2 of the fold, from a finished phase 1 of either import: merges the three streams into the
+// non-current base buffer and tail arena and, on success, switches to them with an empty delta.
+static int import_fold(fdbcs_conflict_set* cs, ImportPlan& pl, int64_t* boundaries_out) {
+    ImportArgs& a = pl.d.a;
+    const int64_t nb = a.nb, nd = a.nd, m = pl.m;
+    const int64_t total_ub = nb + nd + a.n + 2;
+    const int64_t tail_need = pl.sc.tail_used + 8 * pl.u_end;
+    int rc;
+    if ((rc = ensure_history(cs, total_ub + 1, tail_need + 1))) return rc;
+    if ((rc = import_merged(cs, a, total_ub))) return rc;
+    // the scan's granules have a buffer of their own: the words of phase 1 stay where they are
+    const size_t gran = 8 * (size_t)scan_granules(total_ub, 2);
+    if ((rc = cs->i_gran.ensure(gran))) return rc;
+    import_tiers(cs, a, false);
+    hipStream_t s = cs->stream;
+    HIPOK(hipMemsetAsync(cs->i_gran.p, 0, gran, s));
     HIPOK(hipEventRecord(cs->i_ev[2], s));
     HIPOK(hipMemsetAsync(cs->i_mlt.p, 0, 8 * (size_t)(nb + nd + m), s));
-    launch_import_fold(s, a, m, (uint64_t*)cs->i_state.p + kIwWords);
+    launch_import_fold(s, a, m, (uint64_t*)cs->i_gran.p);
     HIPOK(take_launch_error());
     HIPOK(hipEventRecord(cs->i_ev[3], s));
+    int64_t words[kIwWords];
     HIPOK(hipMemcpyAsync(words, cs->i_state.p, sizeof(words), hipMemcpyDeviceToHost, s));
     HIPOK(hipStreamSynchronize(s));
     cs->i_ms_kernels += ev_ms(cs->i_ev[2], cs->i_ev[3]);
@@ -1807,20 +1888,7 @@ static int import_device(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t 
     ns.n = kept;
     ns.tail_used = tail_used;
     HIPOK(hipMemcpyAsync(cs->scal.p, &ns, sizeof(ns), hipMemcpyHostToDevice, s));
-    HIPOK(hipEventRecord(cs->i_ev[4], s));
-    launch_rangemax(s, levels_of(cs, cs->cur), (Scalars*)cs->scal.p, &((Scalars*)cs->scal.p)->n, cs->lvl3_n, cs->lvl2_n,
-                    std::max<int64_t>(kept, 1));
-    // the greatest version the import left in the history: the top of the rebuilt range-max levels
-    launch_import_max(s, levels_of(cs, cs->cur), cs->lvl3_n, &a.words[kIwMaxVer]);
-    HIPOK(take_launch_error());
-    HIPOK(hipEventRecord(cs->i_ev[5], s));
-    HIPOK(hipMemcpyAsync(&words[kIwMaxVer], &a.words[kIwMaxVer], 8, hipMemcpyDeviceToHost, s));
-    HIPOK(hipStreamSynchronize(s));
-    cs->i_ms_kernels += ev_ms(cs->i_ev[4], cs->i_ev[5]);
-    cs->header_version = a.new_hdr;
-    cs->max_written = std::max({cs->max_written, a.new_hdr, words[kIwMaxVer]});
-    cs->ddir_epoch[0] = cs->ddir_epoch[1] = 0;  // the delta is empty: no directory entry of it is trusted
-    cs->prev_segs = false;
+    if ((rc = import_finish(cs, a, false, kept))) return rc;
     cs->n_ub = kept;
     cs->nd_ub = 0;
     cs->tail_ub = tail_used;
@@ -1829,112 +1897,46 @@ static int import_device(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t 
     return FDBCS_OK;
 }
 
-// The import into the delta tier, on device arrays (same contract as import_device).  Phase 1
-// validates the arrays, builds the overlay and places lo and hi in both tiers; the host then knows
-// an upper bound of the delta afterwards and either goes on (phase 2 writes the non-current delta
-// buffer and arena bytes past tail_used, and the host switches to them after reading the result
-// words) or hands the whole import to the fold, which leaves an empty delta.
+// The import that folds into a new base (both of its entry points end here).
+static int import_device(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key,
+                         int32_t hi_len, int64_t n, const uint8_t* d_bytes, int64_t nbytes, const int64_t* d_off,
+                         const int64_t* d_ver, int64_t ihdr, int64_t* boundaries_out) {
+    ImportPlan pl;
+    bool done;
+    const int rc = import_phase1(cs, lo_key, lo_len, hi_key, hi_len, n, d_bytes, nbytes, d_off, d_ver, ihdr,
+                                 boundaries_out, false, pl, &done);
+    return rc || done ? rc : import_fold(cs, pl, boundaries_out);
+}
+
+// The import into the delta tier (same contract).  After phase 1 the host knows an upper bound of
+// the delta afterwards and either goes on (phase 2 writes the non-current delta buffer and arena
+// bytes past tail_used, and the host switches to them after reading the result words) or goes on
+// with the fold's phase 2 on the overlay it has, which leaves an empty delta.
 static int import_delta_device(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key,
                                int32_t hi_len, int64_t n, const uint8_t* d_bytes, int64_t nbytes, const int64_t* d_off,
                                const int64_t* d_ver, int64_t ihdr, int64_t* boundaries_out) {
-    Scalars sc;
-    HIPOK(hipMemcpy(&sc, cs->scal.p, sizeof(sc), hipMemcpyDeviceToHost));
-    const int64_t nb = sc.n, nd = sc.ndb[cs->dcur];
-    if (nb + nd + n + 2 >= ((int64_t)1 << 31)) return FDBCS_E_NOMEM;  // as the fold refuses
-    const bool has_lo = lo_len >= 0, has_hi = hi_len >= 0;
-    const int64_t ll = has_lo ? lo_len : 0, hl = has_hi ? hi_len : 0;
-    // overlay tails as in import_device; at most that many units are appended to the arena
-    const int64_t u_lo = ((nbytes + 7) >> 3) + n + 1, u_hi = u_lo + ((ll + 7) >> 3) + 1, u_end = u_hi + ((hl + 7) >> 3) + 1;
-    const int64_t tail_base = (sc.tail_used + 7) >> 3;
-    const int64_t tail_need = 8 * (tail_base + u_end);
-    if (tail_need + 1 >= kTailLimit) return FDBCS_E_NOMEM;
-    int rc;
-    const int64_t bnd_hi = (ll + 7) / 8 * 8 + 16;
-    if ((rc = cs->i_bnd.ensure((size_t)(bnd_hi + hl + 64)))) return rc;
-    if ((rc = cs->i_okey.ensure(16 * (size_t)(n + 2)))) return rc;
-    if ((rc = cs->i_olt.ensure(8 * (size_t)(n + 2)))) return rc;
-    if ((rc = cs->i_over.ensure(8 * (size_t)(n + 2)))) return rc;
-    if ((rc = cs->i_otail.ensure(8 * (size_t)u_end + kTailSlack))) return rc;
-    if ((rc = cs->i_vblt.ensure(8 * (size_t)(n + 2)))) return rc;
-    if ((rc = cs->i_state.ensure(8 * (size_t)kIwWords))) return rc;
-    if ((rc = cs->i_dstate.ensure(8 * (size_t)kIdWords))) return rc;
-    for (hipEvent_t& e : cs->i_ev)
-        if (!e) HIPOK(hipEventCreate(&e));
-    ImportDeltaArgs d{};
+    ImportPlan pl;
+    bool done;
+    int rc = import_phase1(cs, lo_key, lo_len, hi_key, hi_len, n, d_bytes, nbytes, d_off, d_ver, ihdr, boundaries_out,
+                           true, pl, &done);
+    if (rc || done) return rc;
+    ImportDeltaArgs& d = pl.d;
     ImportArgs& a = d.a;
-    auto tiers = [&] {  // (again after a capacity change: the buffers may have moved)
-        a.base = hist_of(cs, cs->cur);
-        a.delta = delta_of(cs, cs->dcur);
-        a.htail = (const uint8_t*)cs->htail[cs->tcur].p;
-        a.dst = delta_of(cs, cs->dcur ^ 1);
-        a.tdst = (uint8_t*)cs->htail[cs->tcur].p;
-        a.dst_cap = cs->delta_cap;
-        a.tdst_units = cs->tail_cap / 8;
-    };
-    tiers();
-    a.nb = nb;
-    a.nd = nd;
-    a.hdr = cs->header_version;
-    a.n = n;
-    a.bytes = d_bytes;
-    a.nbytes = nbytes;
-    a.offsets = d_off;
-    a.versions = d_ver;
-    a.ihdr = ihdr;
-    a.has_lo = has_lo;
-    a.has_hi = has_hi;
-    a.lo_len = (int32_t)ll;
-    a.hi_len = (int32_t)hl;
-    a.bnd = (const uint8_t*)cs->i_bnd.p;
-    a.bnd_hi = bnd_hi;
-    a.ov.key = (ulonglong2*)cs->i_okey.p;
-    a.ov.lt = (uint2*)cs->i_olt.p;
-    a.ov.ver = (int64_t*)cs->i_over.p;
-    a.otail = (uint8_t*)cs->i_otail.p;
-    a.otail_lo = u_lo;
-    a.otail_hi = u_hi;
-    a.ovhdr = has_lo ? kHole : ihdr;
-    a.words = (int64_t*)cs->i_state.p;
-    a.v_blt = (int64_t*)cs->i_vblt.p;
-    a.new_hdr = has_lo ? cs->header_version : std::max(cs->header_version, ihdr);
-    d.dwords = (int64_t*)cs->i_dstate.p;
-    d.tail_base = tail_base;
-    hipStream_t s = cs->stream;
-    if (ll) HIPOK(hipMemcpyAsync(cs->i_bnd.p, lo_key, (size_t)ll, hipMemcpyHostToDevice, s));
-    if (hl) HIPOK(hipMemcpyAsync((uint8_t*)cs->i_bnd.p + bnd_hi, hi_key, (size_t)hl, hipMemcpyHostToDevice, s));
-    HIPOK(hipMemsetAsync(cs->i_state.p, 0, 8 * (size_t)kIwWords, s));
-    HIPOK(hipMemsetAsync(cs->i_dstate.p, 0, 8 * (size_t)kIdWords, s));
-    const int64_t none = kHole;
-    HIPOK(hipMemcpyAsync(&a.words[kIwMaxVer], &none, 8, hipMemcpyHostToDevice, s));
-    int64_t words[kIwWords], dw[kIdWords];
-    HIPOK(hipEventRecord(cs->i_ev[0], s));
-    launch_import_overlay(s, a);
-    launch_import_delta_bounds(s, d);
-    HIPOK(take_launch_error());
-    HIPOK(hipEventRecord(cs->i_ev[1], s));
-    HIPOK(hipMemcpyAsync(words, cs->i_state.p, sizeof(words), hipMemcpyDeviceToHost, s));
-    HIPOK(hipMemcpyAsync(dw, cs->i_dstate.p, sizeof(dw), hipMemcpyDeviceToHost, s));
-    HIPOK(hipStreamSynchronize(s));
-    cs->i_ms_kernels = ev_ms(cs->i_ev[0], cs->i_ev[1]);
-    if ((int32_t)words[kIwError] & 1) return FDBCS_E_INVALID;
-    if (words[kIwError]) return FDBCS_E_DEVICE;
-    if (has_lo && has_hi && cmp_bytes(lo_key, lo_len, hi_key, hi_len) == 0) {  // an empty range: validated, nothing to do
-        *boundaries_out = nb + nd;
-        import_note(cs, 1, nb, nd, nd);
-        return FDBCS_OK;
-    }
-    const int64_t m = words[kIwM];
-    if (m < (has_lo ? 1 : 0) + (has_hi ? 1 : 0) || m > n + 2) return FDBCS_E_DEVICE;
-    d.p_lo = dw[kIdPlo];
-    d.p_hi = dw[kIdPhi];
-    d.q_lo = dw[kIdQlo];
-    d.q_hi = dw[kIdQhi];
-    d.e_ver = dw[kIdEver];
+    ImportWindow& w = d.w;
+    Scalars& sc = pl.sc;
+    const int64_t nb = a.nb, nd = a.nd, m = pl.m;
+    const int64_t* dw = pl.dw;
+    w.p_lo = dw[kIdPlo];
+    w.p_hi = dw[kIdPhi];
+    w.q_lo = dw[kIdQlo];
+    w.q_hi = dw[kIdQhi];
+    w.e_ver = dw[kIdEver];
     d.e_skip = dw[kIdEskip] ? 1 : 0;
-    if (d.p_lo < 0 || d.p_lo > d.p_hi || d.p_hi > nd || d.q_lo < 0 || d.q_lo > d.q_hi || d.q_hi > nb) return FDBCS_E_DEVICE;
-    const int64_t ndr = d.p_hi - d.p_lo, nbr = d.q_hi - d.q_lo;
-    d.mr = m - (has_hi ? 1 : 0);
-    d.R = ndr + nbr + d.mr;
+    if (w.p_lo < 0 || w.p_lo > w.p_hi || w.p_hi > nd || w.q_lo < 0 || w.q_lo > w.q_hi || w.q_hi > nb) return FDBCS_E_DEVICE;
+    const int64_t nbr = w.q_hi - w.q_lo;
+    w.closing = a.has_hi ? 1 : 0;
+    w.mr = m - w.closing;
+    w.R = (w.p_hi - w.p_lo) + nbr + w.mr;
     // the delta afterwards holds at most its boundaries outside the range, the range's and the closing one
     const int64_t nd_bound = nd + nbr + m + 2;
     bool fold = nd_bound > delta_limit_for(cs, cs->n_ub);
@@ -1945,62 +1947,38 @@ static int import_delta_device(fdbcs_conflict_set* cs, const uint8_t* lo_key, in
         else if (rc)
             return rc;
     }
-    if (fold) {  // the existing path takes every range this one cannot hold: exact, with an empty delta
-        const double ms = cs->i_ms_kernels;
-        rc = import_device(cs, lo_key, lo_len, hi_key, hi_len, n, d_bytes, nbytes, d_off, d_ver, ihdr, boundaries_out);
-        cs->i_ms_kernels += ms;
-        return rc;
-    }
-    if ((rc = ensure_history(cs, cs->hist_cap, tail_need + 1))) return rc;
-    const int64_t total = d.R + (has_hi ? 1 : 0);
+    // the fold takes every range the delta cannot hold: exact, with an empty delta
+    if (fold) return import_fold(cs, pl, boundaries_out);
+    if ((rc = ensure_history(cs, cs->hist_cap, 8 * (d.tail_base + pl.u_end) + 1))) return rc;
+    const int64_t total = w.R + w.closing;
     const int64_t gran = scan_granules(total, 2);
-    if ((rc = cs->i_mval.ensure(8 * (size_t)(total + 1)))) return rc;
-    if ((rc = cs->i_mkey.ensure(16 * (size_t)(total + 1)))) return rc;
-    if ((rc = cs->i_mlt.ensure(8 * (size_t)(total + 1)))) return rc;
-    if ((rc = cs->i_dblt.ensure(8 * (size_t)(nd + 1)))) return rc;
+    if ((rc = import_merged(cs, a, total + 1))) return rc;
     if ((rc = cs->i_dstate.ensure(8 * (size_t)(kIdWords + gran)))) return rc;
-    tiers();
-    a.m_val = (int64_t*)cs->i_mval.p;
-    a.m_key = (ulonglong2*)cs->i_mkey.p;
-    a.m_lt = (uint2*)cs->i_mlt.p;
-    a.d_blt = (int64_t*)cs->i_dblt.p;
+    import_tiers(cs, a, true);
     d.dwords = (int64_t*)cs->i_dstate.p;
+    hipStream_t s = cs->stream;
     HIPOK(hipMemsetAsync(cs->i_dstate.p, 0, 8 * (size_t)(kIdWords + gran), s));
     HIPOK(hipEventRecord(cs->i_ev[2], s));
     HIPOK(hipMemsetAsync(cs->i_mlt.p, 0, 8 * (size_t)(total + 1), s));
     launch_import_delta_merge(s, d, (uint64_t*)cs->i_dstate.p + kIdWords);
     HIPOK(take_launch_error());
     HIPOK(hipEventRecord(cs->i_ev[3], s));
-    HIPOK(hipMemcpyAsync(dw, cs->i_dstate.p, sizeof(dw), hipMemcpyDeviceToHost, s));
+    HIPOK(hipMemcpyAsync(pl.dw, cs->i_dstate.p, sizeof(pl.dw), hipMemcpyDeviceToHost, s));
     HIPOK(hipStreamSynchronize(s));
     cs->i_ms_kernels += ev_ms(cs->i_ev[2], cs->i_ev[3]);
     if ((int32_t)dw[kIdError] & 8) return FDBCS_E_NOMEM;
     if (dw[kIdError] || ((const int32_t*)&dw[kIdScan])[1]) return FDBCS_E_DEVICE;
     const int64_t kept = dw[kIdKept], units = dw[kIdTailUnits];
-    const int64_t nd_new = d.p_lo + kept + (nd - d.p_hi);
-    if (kept < 0 || kept > total || nd_new > cs->delta_cap || units < 0 || units > u_end) return FDBCS_E_DEVICE;
+    const int64_t nd_new = w.p_lo + kept + (nd - w.p_hi);
+    if (kept < 0 || kept > total || nd_new > cs->delta_cap || units < 0 || units > pl.u_end) return FDBCS_E_DEVICE;
     // success: the delta buffer the kernels filled becomes current, the appended tails count
-    const int64_t tail_used = units ? 8 * (tail_base + units) : sc.tail_used;
+    const int64_t tail_used = units ? 8 * (d.tail_base + units) : sc.tail_used;
     cs->dcur ^= 1;
     sc.nd = nd_new;
     sc.ndb[cs->dcur] = nd_new;
     sc.tail_used = tail_used;
     HIPOK(hipMemcpyAsync(cs->scal.p, &sc, sizeof(sc), hipMemcpyHostToDevice, s));
-    cs->ddir_epoch[0] = cs->ddir_epoch[1] = 0;  // the delta's directory is not trusted until an epilogue refills it
-    cs->prev_segs = false;
-    HIPOK(hipEventRecord(cs->i_ev[4], s));
-    // levels and sample index of the new delta buffer, as ensure_delta rebuilds them after a regrow
-    launch_rangemax(s, dlevels_of(cs, cs->dcur), (Scalars*)cs->scal.p, &((Scalars*)cs->scal.p)->ndb[cs->dcur],
-                    cs->dlvl3_n, cs->dlvl2_n, std::max<int64_t>(nd_new, 1));
-    // the greatest version left in the new delta: the top of its rebuilt levels (holes are INT64_MIN)
-    launch_import_max(s, dlevels_of(cs, cs->dcur), cs->dlvl3_n, &a.words[kIwMaxVer]);
-    HIPOK(take_launch_error());
-    HIPOK(hipEventRecord(cs->i_ev[5], s));
-    HIPOK(hipMemcpyAsync(&words[kIwMaxVer], &a.words[kIwMaxVer], 8, hipMemcpyDeviceToHost, s));
-    HIPOK(hipStreamSynchronize(s));
-    cs->i_ms_kernels += ev_ms(cs->i_ev[4], cs->i_ev[5]);
-    cs->header_version = a.new_hdr;
-    cs->max_written = std::max({cs->max_written, a.new_hdr, words[kIwMaxVer]});
+    if ((rc = import_finish(cs, a, true, nd_new))) return rc;
     cs->nd_ub = nd_new;  // exact: the next batch's compaction trigger counts the import
     cs->tail_ub = tail_used;
     *boundaries_out = nb + nd_new;

@@ -581,10 +581,23 @@ struct ImportArgs {
     int64_t dst_cap, tdst_units;
     int64_t new_hdr;       // the set's header after the import
 };
-// Validate the imported arrays, place lo / hi in them and normalize the overlay (phase 1); the host
-// reads the words (error, overlay size) before phase 2.
+// What k_import_rank<S> merges: a window of each stream, by value.  Counts and values are taken over
+// the whole streams, positions in the merged arrays from the windows' start.
+struct ImportWindow {
+    int64_t p_lo, p_hi;    // the delta's boundaries: [p_lo, p_hi)
+    int64_t q_lo, q_hi;    // the base's: [q_lo, q_hi)
+    int64_t mr;            // the overlay's: [0, mr)
+    int64_t R;             // boundaries of the three windows: the merged positions are [0, R)
+    int64_t e_ver;         // with a closing boundary: its version
+    int32_t closing;       // overlay boundary mr closes the range: it takes position R as it is
+    int* error;            // the word that gets bit 4 for a merged position out of range
+};
+// Validate the imported arrays, place lo / hi in them and normalize the overlay (phase 1 of both
+// imports: k_import_check, k_import_bounds, k_import_normalize); the host reads the words (error,
+// overlay size) before phase 2.
 void launch_import_overlay(hipStream_t s, const ImportArgs& a);
-// Merge the three streams and write the new base (phase 2).  m: the overlay size phase 1 reported.
+// Merge the three streams and write the new base (phase 2: k_import_rank<1>, <2>, <0> over the whole
+// streams, then k_scan<ImportFold>).  m: the overlay size phase 1 reported.
 void launch_import_fold(hipStream_t s, const ImportArgs& a, int64_t m, uint64_t* granules);
 // The greatest version of the tier whose levels `m` were just rebuilt, into *out (device, atomicMax).
 void launch_import_max(hipStream_t s, const MaxLevels& m, int64_t lvl3_n, int64_t* out);
@@ -611,21 +624,19 @@ struct ImportDeltaArgs {
     // non-current delta buffer (dst_cap its capacity), tdst the current arena (tdst_units its capacity)
     ImportArgs a;
     int64_t* dwords;       // [kIdWords] ImportDeltaWord
-    // what k_impd_bounds found, read back by the host and passed to the later launches by value
-    int64_t p_lo, p_hi;    // the delta's boundaries in the range: [p_lo, p_hi)
-    int64_t q_lo, q_hi;    // the base's: [q_lo, q_hi)
-    int64_t mr;            // overlay boundaries in the range: [0, mr) (all but the closing one)
-    int64_t R;             // boundaries of the three in the range; with an upper bound the closing
-                           // boundary takes position R of the merged arrays
-    int64_t e_ver;         // its version (kIdEver)
+    // what k_impd_bounds found, read back by the host and passed to the later launches by value:
+    // the boundaries inside the range (mr: all of the overlay's but the closing one, which stands
+    // with an upper bound and carries kIdEver); w.error is the launcher's to set
+    ImportWindow w;
     int32_t e_skip;        // kIdEskip
     int64_t tail_base;     // first free unit of the arena (tail_used / 8)
 };
-// Positions of lo and hi in both tiers and the delta's value at hi; after launch_import_overlay, in
-// phase 1 (the host reads both word blocks in one go).
+// Positions of lo and hi in both tiers and the delta's value at hi (k_impd_bounds); after
+// launch_import_overlay, in phase 1 (the host reads both word blocks in one go).
 void launch_import_delta_bounds(hipStream_t s, const ImportDeltaArgs& d);
-// Rank the three streams' boundaries inside the range, fold them into the non-current delta buffer at
-// p_lo and copy the delta's prefix and suffix around them (phase 2).
+// Rank the three streams' boundaries inside the range (k_import_rank<1>, <2>, <0> over d.w), fold
+// them into the non-current delta buffer at p_lo (k_scan<ImportDeltaFold>) and copy the delta's
+// prefix and suffix around them (k_impd_copy) (phase 2).
 void launch_import_delta_merge(hipStream_t s, const ImportDeltaArgs& d, uint64_t* granules);
 
 }  // namespace fdbcs

@@ -4766,13 +4766,17 @@ void launch_export(hipStream_t s, const ExportArgs& a, const MaxLevels& basem, u
 //                       export_put_key; source keys start at any byte).  Tail units need no scan:
 //                       imported boundary j owns unit (offsets[j] >> 3) + j, which never overlaps
 //                       its neighbours' and wastes at most 15 bytes per key of scratch.
-//   k_import_rank<S>    one lane per element of stream S: its lower bounds in the other two give
-//                       its position in the merged order (on equal keys delta, overlay, base) and
-//                       all three streams' values at its key, hence H'.  Later elements of a tie
-//                       repeat their predecessor's value, so no case is special.  The element's
-//                       prefix words, (len, tail unit) and H' go to its merged position.  Base
-//                       boundaries (S = 0, launched last) search no keys: their ranks follow from
-//                       the lower bounds the other two streams' elements found in the base.
+//   k_import_rank<S>    one lane per element of stream S inside an ImportWindow (this import: the
+//                       whole streams, no closing boundary): its lower bounds in the other two's
+//                       windows give its position in the merged order (on equal keys delta,
+//                       overlay, base) and all three streams' values at its key, hence H'.  Values
+//                       come from the whole tiers (the boundary covering a window's first key may
+//                       lie before it); the searches are plain binary searches over the windows.
+//                       Later elements of a tie repeat their predecessor's value, so no case is
+//                       special.  The element's prefix words, (len, tail unit) and H' go to its
+//                       merged position.  Base boundaries (S = 0, launched last) search no keys:
+//                       their ranks follow from the lower bounds the other two streams' elements
+//                       found in the base.
 //   k_scan<ImportFold>  flags value changes along the merged stream, scans (kept, tail units) with
 //                       the look-back and writes the kept boundaries into the non-current base
 //                       buffer, their tails packed into the non-current arena; every read of the
@@ -4905,12 +4909,32 @@ __global__ __launch_bounds__(kBlock) void k_import_normalize(ImportArgs a) {
     }
 }
 
-// Boundaries of a tier below q, and whether the next one equals it.
-__device__ __forceinline__ int64_t import_lower(const Hist& h, int64_t n, const uint8_t* arena, const DKey& q,
-                                                const uint8_t* qtail, bool& exact) {
-    const int64_t lb = export_bound(h, n, arena, q, qtail, false);
-    exact = lb < n && hist_cmp(h, lb, arena, q, qtail) == 0;
-    return lb;
+// Boundary i of a stream as a search key; its tail starts at qtail.
+__device__ __forceinline__ void impd_key(const Hist& h, int64_t i, const uint8_t* arena, DKey& q,
+                                         const uint8_t*& qtail) {
+    const ulonglong2 k = h.key[i];
+    const uint2 lt = h.lt[i];
+    q.hi = k.x;
+    q.lo = k.y;
+    q.len = lt.x;
+    q.tail = 0;  // the query's tail starts at qtail
+    qtail = hist_tail(arena, lt.x > 16u ? lt.y : 0u);
+}
+
+// Boundaries of h[lo, hi) below q counted from 0 (the answer lies in [lo, hi]), and whether the
+// next one equals it.
+__device__ __forceinline__ int64_t impd_lower(const Hist& h, int64_t lo, int64_t hi, const uint8_t* arena,
+                                              const DKey& q, const uint8_t* qtail, bool& exact) {
+    const int64_t end = hi;
+    while (lo < hi) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (hist_cmp(h, mid, arena, q, qtail) < 0)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    exact = lo < end && hist_cmp(h, lo, arena, q, qtail) == 0;
+    return lo;
 }
 
 // Entries of the ascending array x[0..n) that are <= v.
@@ -4928,56 +4952,61 @@ __device__ __forceinline__ int64_t import_count_le(const int64_t* x, int64_t n, 
 
 constexpr uint32_t kImportOvTail = 1u << 31;  // ImportArgs::m_lt len bit: the tail is in the overlay's arena
 
-// S: the stream of this launch's elements (0 base, 1 delta, 2 overlay), one lane each.
+// S: the stream of this launch's elements (0 base, 1 delta, 2 overlay), one lane per boundary inside
+// the window; with a closing boundary the overlay's launch has one more lane for it.
 template <int S>
-__global__ __launch_bounds__(kBlock) void k_import_rank(ImportArgs a, int64_t m) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t total = a.nb + a.nd + m;
-    if (i >= (S == 0 ? a.nb : S == 1 ? a.nd : m)) return;
-    ulonglong2 k;
-    uint2 lt;
-    const uint8_t* arena = S == 2 ? a.otail : a.htail;
-    if constexpr (S == 0) k = a.base.key[i], lt = a.base.lt[i];
-    if constexpr (S == 1) k = a.delta.key[i], lt = a.delta.lt[i];
-    if constexpr (S == 2) k = a.ov.key[i], lt = a.ov.lt[i];
+__global__ __launch_bounds__(kBlock) void k_import_rank(ImportArgs a, ImportWindow w) {
+    const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t ndr = w.p_hi - w.p_lo, nbr = w.q_hi - w.q_lo;
+    if (i0 >= (S == 0 ? nbr : S == 1 ? ndr : w.mr + w.closing)) return;
+    if (S == 2 && i0 == w.mr) {  // the closing boundary: hi's key, the delta's old value there
+        const uint2 lt = a.ov.lt[i0];
+        a.m_val[w.R] = w.e_ver;
+        a.m_key[w.R] = a.ov.key[i0];
+        a.m_lt[w.R] = make_uint2(lt.x | kImportOvTail, lt.x > 16u ? lt.y : 0u);
+        return;
+    }
+    const int64_t i = i0 + (S == 0 ? w.q_lo : S == 1 ? w.p_lo : 0);
+    const Hist& h = S == 0 ? a.base : S == 1 ? a.delta : a.ov;
+    const ulonglong2 k = h.key[i];
+    const uint2 lt = h.lt[i];
     DKey q;
-    q.hi = k.x;
-    q.lo = k.y;
-    q.len = lt.x;
-    q.tail = 0;  // the query's tail starts at qtail
-    const uint8_t* qtail = hist_tail(arena, lt.x > 16u ? lt.y : 0u);
-    // boundaries below the key (lt) and at or below it (le) in each stream
+    const uint8_t* qtail;
+    impd_key(h, i, S == 2 ? a.otail : a.htail, q, qtail);
+    // boundaries below the key (lt) and at or below it (le) in each stream, counted over the whole stream
     int64_t b_lt = i, b_le = i + 1, d_lt = i, d_le = i + 1, v_lt = i, v_le = i + 1;
     [[maybe_unused]] bool ex;
     if constexpr (S == 0) {
         // a base boundary's ranks in the other two streams follow from their elements' lower bounds
-        // in the base (k_import_rank<1>, <2> ran first): the delta boundaries at or below base key i
-        // are those with at most i base boundaries below them.  A search over a dense ascending
-        // array of integers, no key compares.
-        d_le = import_count_le(a.d_blt, a.nd, i);
-        v_le = import_count_le(a.v_blt, m, i);
+        // in the base (k_import_rank<1>, <2> ran first): the in-window delta boundaries at or below
+        // base key i are those with at most i base boundaries below them.  A search over a dense
+        // ascending array of integers, no key compares.
+        d_le = w.p_lo + import_count_le(a.d_blt + w.p_lo, ndr, i);
+        v_le = import_count_le(a.v_blt, w.mr, i);
     } else {
-        b_lt = import_lower(a.base, a.nb, a.htail, q, qtail, ex);
+        b_lt = impd_lower(a.base, w.q_lo, w.q_hi, a.htail, q, qtail, ex);
         b_le = b_lt + (ex ? 1 : 0);
         (S == 1 ? a.d_blt : a.v_blt)[i] = b_lt;
     }
     if constexpr (S == 2) {
-        d_lt = import_lower(a.delta, a.nd, a.htail, q, qtail, ex);
+        d_lt = impd_lower(a.delta, w.p_lo, w.p_hi, a.htail, q, qtail, ex);
         d_le = d_lt + (ex ? 1 : 0);
     }
     if constexpr (S == 1) {
-        v_lt = import_lower(a.ov, m, a.otail, q, qtail, ex);
+        v_lt = impd_lower(a.ov, 0, w.mr, a.otail, q, qtail, ex);
         v_le = v_lt + (ex ? 1 : 0);
     }
-    // on equal keys: delta, then overlay, then base
-    const int64_t pos = S == 1 ? d_lt + v_lt + b_lt : S == 2 ? v_lt + d_le + b_lt : b_lt + d_le + v_le;
+    // on equal keys: delta, then overlay, then base; positions count from the window's start
+    const int64_t pos = S == 1   ? (d_lt - w.p_lo) + v_lt + (b_lt - w.q_lo)
+                        : S == 2 ? v_lt + (d_le - w.p_lo) + (b_lt - w.q_lo)
+                                 : (b_lt - w.q_lo) + (d_le - w.p_lo) + v_le;
     const int64_t dv = d_le > 0 ? a.delta.ver[d_le - 1] : kHole;
     const int64_t bv = b_le > 0 ? a.base.ver[b_le - 1] : a.hdr;
     const int64_t ov = v_le > 0 ? a.ov.ver[v_le - 1] : a.ovhdr;
     int64_t v = dv != kHole ? dv : bv;
     if (ov != kHole && ov > v) v = ov;
-    if (pos < 0 || pos >= total) {  // streams out of order: never index past the merged arrays
-        atomicOr((int*)&a.words[kIwError], 4);
+    if (pos < 0 || pos >= w.R) {  // streams out of order: never index past the merged arrays
+        atomicOr(w.error, 4);
         return;
     }
     a.m_val[pos] = v;
@@ -5049,11 +5078,23 @@ void launch_import_overlay(hipStream_t s, const ImportArgs& a) {
     fdb_launch(k_import_normalize, dim3((unsigned)((a.n + 2 + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, a);
 }
 
-void launch_import_fold(hipStream_t s, const ImportArgs& a, int64_t m, uint64_t* granules) {
+// The rank launches of either import: delta, overlay, then base (it reads d_blt, v_blt).
+static void launch_import_rank(hipStream_t s, const ImportArgs& a, const ImportWindow& w) {
     auto grid = [](int64_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); };
-    if (a.nd > 0) fdb_launch(k_import_rank<1>, grid(a.nd), dim3(kBlock), 0, s, a, m);
-    if (m > 0) fdb_launch(k_import_rank<2>, grid(m), dim3(kBlock), 0, s, a, m);
-    if (a.nb > 0) fdb_launch(k_import_rank<0>, grid(a.nb), dim3(kBlock), 0, s, a, m);  // reads d_blt, v_blt
+    const int64_t ndr = w.p_hi - w.p_lo, nv = w.mr + w.closing, nbr = w.q_hi - w.q_lo;
+    if (ndr > 0) fdb_launch(k_import_rank<1>, grid(ndr), dim3(kBlock), 0, s, a, w);
+    if (nv > 0) fdb_launch(k_import_rank<2>, grid(nv), dim3(kBlock), 0, s, a, w);
+    if (nbr > 0) fdb_launch(k_import_rank<0>, grid(nbr), dim3(kBlock), 0, s, a, w);
+}
+
+void launch_import_fold(hipStream_t s, const ImportArgs& a, int64_t m, uint64_t* granules) {
+    ImportWindow w{};  // the whole streams, no closing boundary
+    w.p_hi = a.nd;
+    w.q_hi = a.nb;
+    w.mr = m;
+    w.R = a.nb + a.nd + m;
+    w.error = (int*)&a.words[kIwError];
+    launch_import_rank(s, a, w);
     ScanState st;
     st.granules = granules;
     st.counter = (int*)&a.words[kIwScan];
@@ -5073,13 +5114,11 @@ void launch_import_fold(hipStream_t s, const ImportArgs& a, int64_t m, uint64_t*
 // hi.  Outside the range the delta is copied as it is.
 //   k_impd_bounds     positions of lo and hi in the base and in the delta (plain binary searches,
 //                     full key compare), the delta's value at hi
-//   k_impd_rank<S>    k_import_rank<S> over the sub-ranges only: one lane per boundary of stream S
-//                     inside the range, its place among the three in-range streams (on equal keys
-//                     delta, overlay, base) and H' at its key.  Values come from the whole tiers
-//                     (the boundary covering lo may lie before the range); the searches are plain
-//                     binary searches over the sub-ranges, log2(range) steps instead of log2(tier)
+//   k_import_rank<S>  the fold's kernel over the windows k_impd_bounds found: one lane per boundary of
+//                     stream S inside the range, log2(range) search steps instead of log2(tier)
 //                     (the base's directory, lane_lower_bound, is not used: an in-range search is
-//                     already short, and the base boundaries again search only integer arrays).
+//                     already short).  The overlay's launch has one more lane, which puts the
+//                     closing boundary at position R.
 //   k_scan<ImportDeltaFold>  flags value changes along the in-range stream, scans (kept, tail units
 //                     of kept overlay keys) on granules of the import's own and writes the kept
 //                     boundaries into the non-current delta buffer from p_lo on, one lane each.
@@ -5088,33 +5127,6 @@ void launch_import_fold(hipStream_t s, const ImportArgs& a, int64_t m, uint64_t*
 //   k_impd_copy       the delta's prefix [0, p_lo) as it is and its suffix [p_hi, nd) shifted behind
 //                     the kept boundaries, grid-stride.
 // The greatest version is read off the rebuilt delta's top level (k_import_max), never per element.
-
-__device__ __forceinline__ void impd_key(const Hist& h, int64_t i, const uint8_t* arena, DKey& q,
-                                         const uint8_t*& qtail) {
-    const ulonglong2 k = h.key[i];
-    const uint2 lt = h.lt[i];
-    q.hi = k.x;
-    q.lo = k.y;
-    q.len = lt.x;
-    q.tail = 0;  // the query's tail starts at qtail
-    qtail = hist_tail(arena, lt.x > 16u ? lt.y : 0u);
-}
-
-// Boundaries of h[lo, hi) below q counted from 0 (the answer lies in [lo, hi]), and whether the
-// next one equals it.
-__device__ __forceinline__ int64_t impd_lower(const Hist& h, int64_t lo, int64_t hi, const uint8_t* arena,
-                                              const DKey& q, const uint8_t* qtail, bool& exact) {
-    const int64_t end = hi;
-    while (lo < hi) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (hist_cmp(h, mid, arena, q, qtail) < 0)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    exact = lo < end && hist_cmp(h, lo, arena, q, qtail) == 0;
-    return lo;
-}
 
 __global__ __launch_bounds__(64) void k_impd_bounds(ImportDeltaArgs d) {
     const ImportArgs& a = d.a;
@@ -5153,72 +5165,11 @@ __global__ __launch_bounds__(64) void k_impd_bounds(ImportDeltaArgs d) {
     d.dwords[kIdEskip] = skip;
 }
 
-// S: the stream of this launch's elements (0 base, 1 delta, 2 overlay), one lane per boundary inside
-// the range; the overlay's launch has one more lane for the closing boundary.
-template <int S>
-__global__ __launch_bounds__(kBlock) void k_impd_rank(ImportDeltaArgs d) {
-    const ImportArgs& a = d.a;
-    const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t ndr = d.p_hi - d.p_lo, nbr = d.q_hi - d.q_lo;
-    if (i0 >= (S == 0 ? nbr : S == 1 ? ndr : d.mr + (a.has_hi ? 1 : 0))) return;
-    if (S == 2 && i0 == d.mr) {  // the closing boundary: hi's key, the delta's old value there
-        const uint2 lt = a.ov.lt[i0];
-        a.m_val[d.R] = d.e_ver;
-        a.m_key[d.R] = a.ov.key[i0];
-        a.m_lt[d.R] = make_uint2(lt.x | kImportOvTail, lt.x > 16u ? lt.y : 0u);
-        return;
-    }
-    const int64_t i = i0 + (S == 0 ? d.q_lo : S == 1 ? d.p_lo : 0);
-    const Hist& h = S == 0 ? a.base : S == 1 ? a.delta : a.ov;
-    const ulonglong2 k = h.key[i];
-    const uint2 lt = h.lt[i];
-    DKey q;
-    const uint8_t* qtail;
-    impd_key(h, i, S == 2 ? a.otail : a.htail, q, qtail);
-    // boundaries below the key (lt) and at or below it (le) in each stream, counted over the whole stream
-    int64_t b_lt = i, b_le = i + 1, d_lt = i, d_le = i + 1, v_lt = i, v_le = i + 1;
-    [[maybe_unused]] bool ex;
-    if constexpr (S == 0) {
-        // as k_import_rank<0>: the in-range delta / overlay boundaries at or below base key i are
-        // those with at most i base boundaries below them (k_impd_rank<1>, <2> ran first)
-        d_le = d.p_lo + import_count_le(a.d_blt + d.p_lo, ndr, i);
-        v_le = import_count_le(a.v_blt, d.mr, i);
-    } else {
-        b_lt = impd_lower(a.base, d.q_lo, d.q_hi, a.htail, q, qtail, ex);
-        b_le = b_lt + (ex ? 1 : 0);
-        (S == 1 ? a.d_blt : a.v_blt)[i] = b_lt;
-    }
-    if constexpr (S == 2) {
-        d_lt = impd_lower(a.delta, d.p_lo, d.p_hi, a.htail, q, qtail, ex);
-        d_le = d_lt + (ex ? 1 : 0);
-    }
-    if constexpr (S == 1) {
-        v_lt = impd_lower(a.ov, 0, d.mr, a.otail, q, qtail, ex);
-        v_le = v_lt + (ex ? 1 : 0);
-    }
-    // on equal keys: delta, then overlay, then base; positions count from the range's start
-    const int64_t pos = S == 1   ? (d_lt - d.p_lo) + v_lt + (b_lt - d.q_lo)
-                        : S == 2 ? v_lt + (d_le - d.p_lo) + (b_lt - d.q_lo)
-                                 : (b_lt - d.q_lo) + (d_le - d.p_lo) + v_le;
-    const int64_t dv = d_le > 0 ? a.delta.ver[d_le - 1] : kHole;
-    const int64_t bv = b_le > 0 ? a.base.ver[b_le - 1] : a.hdr;
-    const int64_t ov = v_le > 0 ? a.ov.ver[v_le - 1] : a.ovhdr;
-    int64_t v = dv != kHole ? dv : bv;
-    if (ov != kHole && ov > v) v = ov;
-    if (pos < 0 || pos >= d.R) {  // streams out of order: never index past the merged arrays
-        atomicOr((int*)&d.dwords[kIdError], 4);
-        return;
-    }
-    a.m_val[pos] = v;
-    a.m_key[pos] = k;
-    a.m_lt[pos] = make_uint2(lt.x | (S == 2 ? kImportOvTail : 0u), lt.x > 16u ? lt.y : 0u);
-}
-
 struct ImportDeltaFold {
     ImportDeltaArgs d;
     __device__ bool keep(int64_t p) const {
         const ImportArgs& a = d.a;
-        if (p == d.R && d.e_skip) return false;  // the delta's own boundary at hi follows
+        if (p == d.w.R && d.e_skip) return false;  // the delta's own boundary at hi follows
         // the boundary at lo always stands; without a lower bound the delta's implicit header is a hole
         if (p == 0) return a.has_lo || a.m_val[0] != kHole;
         return a.m_val[p] != a.m_val[p - 1];
@@ -5236,7 +5187,7 @@ struct ImportDeltaFold {
         uint2 lt = a.m_lt[p];
         const bool ovt = (lt.x & kImportOvTail) != 0;
         lt.x &= ~kImportOvTail;
-        const int64_t o = d.p_lo + (int64_t)ex[0];
+        const int64_t o = d.w.p_lo + (int64_t)ex[0];
         const uint32_t nu = ovt ? tail_units(lt.x) : 0u;
         const int64_t unit = d.tail_base + (int64_t)ex[1];
         if (o >= a.dst_cap || unit + nu > a.tdst_units) {  // never past the buffers the host sized
@@ -5262,10 +5213,10 @@ struct ImportDeltaFold {
 __global__ __launch_bounds__(kBlock) void k_impd_copy(ImportDeltaArgs d) {
     const ImportArgs& a = d.a;
     const int64_t kept = d.dwords[kIdKept];
-    const int64_t n = a.nd - (d.p_hi - d.p_lo);  // boundaries outside the range
+    const int64_t n = a.nd - (d.w.p_hi - d.w.p_lo);  // boundaries outside the range
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const bool pre = i < d.p_lo;
-        const int64_t src = pre ? i : d.p_hi + (i - d.p_lo), dst = pre ? i : i + kept;
+        const bool pre = i < d.w.p_lo;
+        const int64_t src = pre ? i : d.w.p_hi + (i - d.w.p_lo), dst = pre ? i : i + kept;
         if (dst < 0 || dst >= a.dst_cap) {
             atomicOr((int*)&d.dwords[kIdError], 8);
             continue;
@@ -5281,18 +5232,16 @@ void launch_import_delta_bounds(hipStream_t s, const ImportDeltaArgs& d) {
 }
 
 void launch_import_delta_merge(hipStream_t s, const ImportDeltaArgs& d, uint64_t* granules) {
-    auto grid = [](int64_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); };
-    const int64_t ndr = d.p_hi - d.p_lo, nbr = d.q_hi - d.q_lo, nv = d.mr + (d.a.has_hi ? 1 : 0);
-    if (ndr > 0) fdb_launch(k_impd_rank<1>, grid(ndr), dim3(kBlock), 0, s, d);
-    if (nv > 0) fdb_launch(k_impd_rank<2>, grid(nv), dim3(kBlock), 0, s, d);
-    if (nbr > 0) fdb_launch(k_impd_rank<0>, grid(nbr), dim3(kBlock), 0, s, d);  // reads d_blt, v_blt
+    ImportWindow w = d.w;
+    w.error = (int*)&d.dwords[kIdError];
+    launch_import_rank(s, d.a, w);
     ScanState st;
     st.granules = granules;
     st.counter = (int*)&d.dwords[kIdScan];
     st.error = st.counter + 1;
-    const int64_t total = d.R + (d.a.has_hi ? 1 : 0);
+    const int64_t total = w.R + w.closing;
     if (total > 0) launch_scan<2>(s, ImportDeltaFold{d}, (const int64_t*)nullptr, total, st);
-    const int64_t outside = d.a.nd - ndr;
+    const int64_t outside = d.a.nd - (w.p_hi - w.p_lo);
     if (outside > 0) {
         const int64_t g = (outside + kBlock - 1) / kBlock;
         fdb_launch(k_impd_copy, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(kBlock), 0, s, d);

@@ -304,6 +304,46 @@ def test_fallback_under_a_set_delta_limit(engine, oracle_mod):
     merge_checked(r, (0, keys[:5], [400, 401, 402, 403, 404]), keys[0], keys[4], what="under the limit")
 
 
+def test_fallback_with_overlay_tails_grows_the_arena(engine, oracle_mod):
+    """A fallback whose overlay holds tails, on a set whose tail arena must grow for the fold: the
+    fold goes on from the overlay the delta import's first phase built, after the receiver's
+    buffers moved.  No call reports the arena's capacity, so the count relies on a new set's arena
+    of 1.5 * 64 KiB: 2400 keys of 40 bytes take 8 * (12 000 + 2400) bytes of overlay tails, which
+    the fold may all have to pack behind the receiver's own."""
+    r = Pair(engine, oracle_mod, gc_interval=0, delta_limit=64)
+    for pb, now, no in prefix_sequence(13)[:4]:
+        r.detect(pb, now, no)
+    assert any(len(k) > 16 for k in r.reference()[1])  # tails of its own, which move with the arena
+    # 24-byte tails behind 240 prefix words: the first and the last tail word decide among ten each
+    tails = [bytes([t // 4]) * 8 + b"\x01" * 8 + b"\x00" * 7 + bytes([t]) for t in range(10)]
+    keys = [P14 + bytes([x, y]) + t for x in (0, 1, 2, 3, 128, 255) for y in range(40) for t in tails]
+    assert keys == sorted(set(keys)) and all(len(k) == 40 for k in keys)
+    imp = (0, keys, [90 + (i * 7) % 41 for i in range(len(keys))])  # below and above the receiver's versions
+    kb, ko, vv, hdr = pack(imp)
+    assert 8 * ((len(kb) + 7) // 8 + len(keys)) > 3 * (1 << 16) // 2
+    lo, hi = keys[37], keys[-40][:-1] + b"\xfe"  # one of the keys, and one between two of them
+    assert len(lo) == len(hi) == 40 and keys[0] < lo < hi < keys[-1] and hi not in keys
+    want = expected(r, imp, lo, hi)
+    n = r.cs.merge_history(kb, ko, vv, hdr, lo=lo, hi=hi, into="delta")
+    info = r.cs.import_info()
+    assert info["path"] == 0 and info["delta_after"] == 0 and info["base_boundaries"] == n == r.cs.history_size()
+    assert dumped(r.cs) == want
+    adopt(r, want)
+    pb, _, no = prefix_sequence(13)[4]
+    r.detect(pb, 300, no)
+    r.check(what="after the fallback")
+    # the same import with invalid arrays: refused by the shared first phase, the set as it was
+    before, info = r.cs.dump_history(), r.cs.import_info()
+    bad = ko.copy()
+    bad[len(keys) // 2] = ko[len(keys) // 2 - 1] - 1  # the key before it has length -1
+    swapped = list(keys)
+    swapped[1000], swapped[1001] = swapped[1001], swapped[1000]
+    for arrays in ((kb, bad, vv, hdr), pack((0, swapped, imp[2]))):
+        raises(engine, engine.FDBCS_E_INVALID, r.cs.merge_history, *arrays, lo=lo, hi=hi, into="delta")
+        assert all(np.array_equal(x, y) for x, y in zip(r.cs.dump_history(), before)) and r.cs.import_info() == info
+    r.check(what="after the refused imports")
+
+
 # ---- 7
 
 def test_atomicity_and_state_rules(engine, oracle_mod):
