@@ -130,9 +130,8 @@ struct HSpan {
     char kind;
     int64_t t0, t1;
 };
-inline int64_t mono_ns() {
-    return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch())
-        .count();
+inline int64_t mono_ns(std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now()) {
+    return std::chrono::duration_cast<std::chrono::nanoseconds>(t.time_since_epoch()).count();
 }
 
 // Host threads for addTransaction of whole batches (fdbcs_batch_add_packed): the endpoint keys'
@@ -309,7 +308,7 @@ struct fdbcs_conflict_set {
     DBuf route_btail;                  // device routing: tails of this resolver's key-range bounds
     std::vector<uint8_t> route_bounds; // the bounds route_btail holds (lo | hi bytes), to skip re-uploads
     // batch workspaces (rotating)
-    DBuf ws[kNumWork][56];  // [0, kWsScanSlot): TAKE slots of ensure_workspace
+    DBuf ws[kNumWork][56];  // [0, kWsTileSlot): TAKE slots of ensure_workspace
     DBuf wbtail[kNumWork];  // Work::btail of each workspace (ensure_btail)
     int64_t ws_T = -1, ws_R = -1, ws_W = -1;
     Work work[kNumWork]{};
@@ -2982,15 +2981,77 @@ int fdbcs_batch_upload(fdbcs_batch* b) {
     return do_upload(b, b->cs->ustream);
 }
 
+// ---- the detect call, step by step ("The detect call's steps")
 
-int fdbcs_batch_detect_async(fdbcs_batch* b, int64_t now, int64_t new_oldest_version) {
-    if (!b) return FDBCS_E_INVALID;
-    if (!b->cs) return FDBCS_E_STATE;
-    if (b->state > 1) return FDBCS_E_STATE;
-    fdbcs_conflict_set* cs = b->cs;
-    const auto t_begin = std::chrono::steady_clock::now();
+// What one detect call decides before it records anything and that more than one of its steps
+// reads.  Every step below takes the set, the batch and this plan, and reads no other step's
+// locals.  Fields are set by plan_layout unless another step is named.
+struct DetectPlan {
+    fdbcs_conflict_set* const cs;
+    fdbcs_batch* const b;
+    const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
+    const int64_t now, oldest_arg;  // the call's `now` and new_oldest_version
+    // sizes and layout (detect_admit, detect_bind_results)
+    int64_t T = 0, R = 0, W = 0, tail_add = 0;
+    ResultLayout RL{};
+    // the batch's resources
+    BatchSlot* const sl;
+    const int wp;  // the workspace (cs->wpar as the call found it) and its Work
+    Work& w;
+    // streams: batch order (X), stage A, half Y, the upload
+    hipStream_t s = nullptr, sa = nullptr, ys = nullptr, us = nullptr;
+    // layout flags
+    int timing = 0;
+    bool sampled = false, kprof = false, split = false, threaded = false, pipe = false, use_prev = false;
+    bool own_upload = false, was_uploaded = false, long_keys = false;
+    bool ws_busy = false;  // (record_stage_a: its event query stays where the waits are recorded)
+    // tier views (plan_views): what the merge reads (delta) and what the check reads (cdelta, ps)
+    Tier base, delta, cdelta;
+    PrevSegs ps{};
+    uint8_t* htail = nullptr;
+    Scalars* sc = nullptr;
+    int bsrc = 0, dsrc = 0, dchk = 0;
+    // what the sort leaves for the epilogue to re-zero of its scratch (record_stage_a)
+    int sort_nb = 0, sort_samples = 0;
+    // the Y decisions (decide_y).  The launch arguments that read the state it rolls forward are
+    // taken before it moves: the GC's (gc_oldest before gc_applied, gc_htail before tcur) and the
+    // merge's view of the delta buffer it writes (merge_dlv, before that buffer's directory epoch)
+    int dnew = 0, final_base = 0;
+    int64_t nd_after = 0, new_oldest = 0, base_hint = 0, gc_oldest = 0;
+    bool compact = false, gc = false;
+    uint8_t* gc_htail = nullptr;
+    MaxLevels merge_dlv;
+
+    DetectPlan(fdbcs_conflict_set* cs_, fdbcs_batch* b_, int64_t now_, int64_t oldest_)
+        : cs(cs_), b(b_), now(now_), oldest_arg(oldest_), sl(b_->slot), wp(cs_->wpar), w(cs_->work[cs_->wpar]) {}
+
+    // phase events: level 2 records every phase, level 1 only the hot kernels (roofline)
+    // level 3 (per-kernel profile) records only the events around every kernel
+    // level 1 with a timed kernel (fdbcs_set_timed_kernel) records only that kernel's events
+    hipEvent_t rec(int ph, int level) const {
+        if (timing == 3 || timing < level || (level == 1 && (!sampled || cs->timed_func))) return nullptr;
+        b->recorded |= 1u << ph;
+        return sl->ev[ph];
+    }
+    void mark(int ph) const {
+        if (hipEvent_t e = rec(ph, 2)) fdb_event(LaunchList::kTimingRecord, e, s);
+    }
+};
+
+// Redirects this thread's fdb_launch / fdb_event into `l` for as long as it lives, so that no
+// return of a recording step, early or late, leaves t_record set (every later direct launch on the
+// thread would be appended to a dead list instead of being issued).
+struct RecordInto {
+    explicit RecordInto(LaunchList& l) { t_record = &l; }
+    ~RecordInto() { t_record = nullptr; }
+    RecordInto(const RecordInto&) = delete;
+    RecordInto& operator=(const RecordInto&) = delete;
+};
+
+// Step 1: may this batch be detected now, and is there room for it?
+static int detect_admit(fdbcs_conflict_set* cs, fdbcs_batch* b, DetectPlan& p) {
     HIPOK(hipSetDevice(cs->device));
-    if (now < cs->max_written) return FDBCS_E_VERSION;
+    if (p.now < cs->max_written) return FDBCS_E_VERSION;
     if (int rc0 = finish_route(b)) return rc0;  // a routed batch's sizes (its route ran ahead)
     if (b->routed && b->rep_dev && b->rep_n != b->r_global_R) {
         // report bytes for every read of the shares, no more and no fewer (like the conflict
@@ -3005,14 +3066,14 @@ int fdbcs_batch_detect_async(fdbcs_batch* b, int64_t now, int64_t new_oldest_ver
     // tail offsets are 32-bit: refuse a batch that could overflow the arena (GC repacks it long before)
     // history tail bytes this batch can append (each inserted tail padded to 8 bytes)
     // only write endpoints ever enter the history (merge inserts segment begins and ends)
-    const int64_t tail_add = b->wtail;
-    if (cs->tail_ub + tail_add + 1 >= kTailLimit) return FDBCS_E_NOMEM;
-    const int64_t T = b->T(), R = b->R(), W = b->W();
+    p.tail_add = b->wtail;
+    if (cs->tail_ub + p.tail_add + 1 >= kTailLimit) return FDBCS_E_NOMEM;
+    p.T = b->T(), p.R = b->R(), p.W = b->W();
     int rc;
-    if ((rc = ensure_workspace(cs, T, R, W))) return rc;
+    if ((rc = ensure_workspace(cs, p.T, p.R, p.W))) return rc;
     if ((rc = ensure_btail(cs, (int64_t)b->tail_size()))) return rc;
-    if ((rc = ensure_delta(cs, cs->nd_ub + 2 * W + 1))) return rc;
-    if ((rc = ensure_history(cs, cs->n_ub + cs->nd_ub + 2 * W + 1, cs->tail_ub + tail_add + 1)))
+    if ((rc = ensure_delta(cs, cs->nd_ub + 2 * p.W + 1))) return rc;
+    if ((rc = ensure_history(cs, cs->n_ub + cs->nd_ub + 2 * p.W + 1, cs->tail_ub + p.tail_add + 1)))
         return rc;
     if ((rc = ensure_events(b))) return rc;
     if (cs->ddir_counter == UINT32_MAX && cs->edir[0].p) {
@@ -3023,20 +3084,26 @@ int fdbcs_batch_detect_async(fdbcs_batch* b, int64_t now, int64_t new_oldest_ver
         HIPOK(hipStreamSynchronize(cs->stream));
         cs->ddir_counter = 0;
     }
-    // results (host-mapped; verdicts written by k_resolve, scalars and flag by the epilogue):
-    // verdicts | scalars | completion flag, then the
-    // report copies rconf | hist | first_conf
-    const ResultLayout RL = result_layout(T, R);
-    const size_t o_sc = RL.sc, o_fl = RL.fl, o_rc = RL.rc, o_hc = RL.hc, o_fc = RL.fc, out_bytes = RL.total;
-    BatchSlot* sl = b->slot;
-    if ((rc = sl->pin_out.ensure(out_bytes, true))) return rc;
+    return FDBCS_OK;
+}
+
+// Step 2: where the batch's results go, and its sequence number.
+// results (host-mapped; verdicts written by k_resolve, scalars and flag by the epilogue):
+// verdicts | scalars | completion flag, then the
+// report copies rconf | hist | first_conf
+static int detect_bind_results(fdbcs_conflict_set* cs, fdbcs_batch* b, DetectPlan& p) {
+    const int64_t T = p.T;
+    const ResultLayout& RL = p.RL = result_layout(T, p.R);
+    BatchSlot* sl = p.sl;
+    int rc;
+    if ((rc = sl->pin_out.ensure(RL.total, true))) return rc;
     char* ho = (char*)sl->pin_out.p;
     b->h_verdict = (uint8_t*)ho;
-    b->h_scal = (Scalars*)(ho + o_sc);
-    b->h_flag = (volatile uint32_t*)(ho + o_fl);
-    b->h_rconf = (uint8_t*)(ho + o_rc);
-    b->h_hist = (uint8_t*)(ho + o_hc);
-    b->h_first = (int32_t*)(ho + o_fc);
+    b->h_scal = (Scalars*)(ho + RL.sc);
+    b->h_flag = (volatile uint32_t*)(ho + RL.fl);
+    b->h_rconf = (uint8_t*)(ho + RL.rc);
+    b->h_hist = (uint8_t*)(ho + RL.hc);
+    b->h_first = (int32_t*)(ho + RL.fc);
     b->h_roff = b->routed ? (const int32_t*)(ho + RL.ro) : b->roff.data();
     b->h_flags = b->routed ? (const uint8_t*)(ho + RL.fg) : b->flags.data();
     if ((rc = sl->dverdict.ensure(T + 64))) return rc;
@@ -3056,138 +3123,139 @@ int fdbcs_batch_detect_async(fdbcs_batch* b, int64_t now, int64_t new_oldest_ver
     if (b->seq == 0) b->seq = ++cs->seq;  // 0 means "not done"
     *b->h_flag = 0;
     b->recorded = 0;
+    return FDBCS_OK;
+}
 
-    hipStream_t s = cs->stream;
-    const int timing = cs->timing;
+// Step 3: the stream layout and its flags, the batch's workspace, the empty stage lists and the
+// tier views.  Nothing here can fail, and nothing is issued or recorded.
+static void plan_layout(fdbcs_conflict_set* cs, fdbcs_batch* b, DetectPlan& p) {
+    hipStream_t s = p.s = cs->stream;
+    const int timing = p.timing = cs->timing;
     // Stage A (sort, positions, candidate edges) depends only on this batch: it runs on its own
     // stream and overlaps stage B of the previous batch.  Phase timing (level 2) runs both stages on
     // one stream so the phases are measured one after another.
-    hipStream_t sa = (timing == 2 || cs->serial) ? s : cs->astream;  // level 3 keeps the timed layout
-    const int wp = cs->wpar;
-    cs->wpar = (wp + 1) % kNumWork;
-    b->wp = wp;
-    Work& w = cs->work[wp];
+    p.sa = (timing == 2 || cs->serial) ? s : cs->astream;  // level 3 keeps the timed layout
+    cs->wpar = (p.wp + 1) % kNumWork;
+    b->wp = p.wp;
+    Work& w = p.w;
     // write groups need the group minima in the resolver's LDS beside the status bytes
-    w.groups = cs->write_groups && W > 0 && W <= kMaxGroupWrites && T <= kMaxTxnLds ? 1 : 0;
-    // phase events: level 2 records every phase, level 1 only the hot kernels (roofline)
+    w.groups = cs->write_groups && p.W > 0 && p.W <= kMaxGroupWrites && p.T <= kMaxTxnLds ? 1 : 0;
     // level-1 (roofline) events on one batch in timing_every: each event record is a runtime call
     // on the submitting thread, and the per-launch averages need only a sample of the batches
-    const bool sampled = timing >= 2 || b->seq % (uint32_t)kTimingEvery == 0;
-    // level 3 (per-kernel profile) records only the events around every kernel
-    // level 1 with a timed kernel (fdbcs_set_timed_kernel) records only that kernel's events
-    auto rec = [&](int ph, int level) -> hipEvent_t {
-        if (timing == 3 || timing < level || (level == 1 && (!sampled || cs->timed_func))) return nullptr;
-        b->recorded |= 1u << ph;
-        return sl->ev[ph];
-    };
-    auto mark = [&](int ph) -> int {
-        if (hipEvent_t e = rec(ph, 2)) fdb_event(LaunchList::kTimingRecord, e, s);
-        return FDBCS_OK;
-    };
-    const bool was_uploaded = b->state == 1;
-    LaunchList& la = cs->rec_a;
-    LaunchList& lb = cs->rec_b;
-    LaunchList& lc = cs->rec_c;
-    LaunchList& ly = cs->rec_y;
-    la.clear();
-    lb.clear();
-    lc.clear();
-    ly.clear();
+    p.sampled = timing >= 2 || b->seq % (uint32_t)kTimingEvery == 0;
+    p.was_uploaded = b->state == 1;
     // per-kernel events: every kernel at level 3, the kernel fdbcs_set_timed_kernel named at level 1
     // (sampled batches)
-    sl->prof_next = 0;
-    sl->prof_spans.clear();
-    const bool kprof = timing == 3 || (timing == 1 && sampled && cs->timed_func);
-    for (LaunchList* L : {&la, &lb, &lc, &ly}) {
-        L->prof = kprof ? &sl->prof : nullptr;
+    p.sl->prof_next = 0;
+    p.sl->prof_spans.clear();
+    p.kprof = timing == 3 || (timing == 1 && p.sampled && cs->timed_func);
+    for (LaunchList* L : {&cs->rec_a, &cs->rec_b, &cs->rec_c, &cs->rec_y}) {
+        L->clear();
+        L->prof = p.kprof ? &p.sl->prof : nullptr;
         L->timed_func = timing == 3 ? nullptr : cs->timed_func;
     }
     // Split read check: the base tier changes only at compactions, so unless one is still pending
     // on the stream its half of D.CheckRead runs beside stage A on its own stream; stage B keeps the
     // delta half.
-    const bool split = (cs->split_check == 1 || (cs->split_check == 2 && cs->n_ub >= kSplitCheckMinBase)) &&
-                       !cs->serial && timing != 2;
+    p.split = (cs->split_check == 1 || (cs->split_check == 2 && cs->n_ub >= kSplitCheckMinBase)) && !cs->serial &&
+              timing != 2;
     // two submitting threads: this batch's stage A and check go out from the helper, stage B on the
     // next call.  The previous batch's stage B is recorded but maybe not issued yet, so an event it
     // records cannot be queried here: waits on its events are kept unconditionally.
-    const bool threaded = cs->submit_thread && timing < 2 && !cs->trace && sa != s;
-    cs->stats.host_ms_prepare += host_ms_since(t_begin);
-    const auto t_rec = std::chrono::steady_clock::now();
-    // ---- upload (issued now) and record stage A: D.Sort and the candidate edges of D.CheckIntraBatch
+    p.threaded = cs->submit_thread && timing < 2 && !cs->trace && p.sa != s;
     // The upload runs on its own stream unless the phases are timed one after another (then on
     // stage A's stream, bracketed by the upload phase's events).
-    const bool own_upload = timing != 2 && !cs->serial;
-    if (hipEvent_t e = rec(kPhStart, 2)) HIPOK(hipEventRecord(e, sa));
-    if (b->state == 0 && (rc = do_upload(b, own_upload ? cs->ustream : sa))) return rc;
-    if (hipEvent_t e = rec(kPhUpload, 2)) HIPOK(hipEventRecord(e, sa));
-    t_record = &la;
+    p.own_upload = timing != 2 && !cs->serial;
+    p.us = p.own_upload ? cs->ustream : p.sa;
+    // long-key probes pay off once tails run past a word (a 17-byte end key k\0 of a 16-byte key
+    // ties on the prefix with k only, and the length decides)
+    p.long_keys = b->max_len > 24;
+    p.sc = (Scalars*)cs->scal.p;
+    p.bsrc = cs->cur, p.dsrc = cs->dcur;
+    // Stage B in two halves (fdbcs_conflict_set::ystream): X = check, resolution, D.Combine on
+    // `stream`; Y = merge, compaction / GC, epilogue on `ystream`.  Unless the previous batch
+    // compacted, this batch's check reads the delta before the previous batch's merge (buffer
+    // dsrc ^ 1, complete once the batch before it finished Y) plus the previous batch's union
+    // segments at its `now` (PrevSegs): the same history, so the check need not wait for that merge.
+    p.pipe = !(timing == 2 || cs->serial);
+    p.ys = p.pipe ? cs->ystream : s;
+    p.use_prev = p.pipe && cs->prev_segs;
+    p.dchk = p.use_prev ? p.dsrc ^ 1 : p.dsrc;
+    w.trace = cs->trace ? (unsigned long long*)cs->trace_buf.p : nullptr;
+    w.no_prepass = cs->no_prepass ? 1 : 0;
+}
+
+// Step 3, second part: the tier views.  Apart from plan_layout only because the views are built
+// under the record span of the host-time stats (host_ms_record), as they always were.
+static void plan_views(fdbcs_conflict_set* cs, DetectPlan& p) {
+    Scalars* sc = p.sc;
+    const int bsrc = p.bsrc, dsrc = p.dsrc, dchk = p.dchk;
+    p.base = Tier{hist_of(cs, bsrc), levels_of(cs, bsrc), &sc->n, cs->header_version};
+    p.delta = Tier{delta_of(cs, dsrc), dlevels_of(cs, dsrc), &sc->ndb[dsrc], kHole};
+    p.cdelta = Tier{delta_of(cs, dchk), dlevels_of(cs, dchk), &sc->ndb[dchk], kHole};  // what the check reads
+    if (p.use_prev) {
+        const Work& pw = cs->work[cs->prev_wp];
+        p.ps = PrevSegs{pw.segk, pw.btail, &pw.bsc->n_segments, cs->prev_now};
+    }
+    p.htail = (uint8_t*)cs->htail[cs->tcur].p;
+}
+
+// FDBCS_TRACE: the device timestamps start over with every batch (the pipeline is drained first).
+static int reset_trace(fdbcs_conflict_set* cs, const Work& w) {
+    HIPOK(hipStreamSynchronize(cs->astream));
+    HIPOK(hipStreamSynchronize(cs->stream));
+    unsigned long long init[kTrSlots];
+    for (int i = 0; i < kTrSlots; i++)
+        init[i] = (i == kTrSampleBegin || i == kTrCheckBegin || i == kTrEpiBegin || i == kTrResBegin || i == kTrResW0min ||
+                   i == kTrPartBegin || i == kTrBktBegin)
+                      ? ~0ull
+                      : 0ull;
+    HIPOK(hipMemcpy(w.trace, init, sizeof(init), hipMemcpyHostToDevice));
+    return FDBCS_OK;
+}
+
+// Step 4: the upload (issued now) and the record of stage A: D.Sort and the candidate edges of
+// D.CheckIntraBatch.
+static int record_stage_a(fdbcs_conflict_set* cs, fdbcs_batch* b, DetectPlan& p) {
+    hipStream_t s = p.s, sa = p.sa;
+    const int wp = p.wp;
+    Work& w = p.w;
+    BatchSlot* sl = p.sl;
+    int rc;
+    if (hipEvent_t e = p.rec(kPhStart, 2)) HIPOK(hipEventRecord(e, sa));
+    if (b->state == 0 && (rc = do_upload(b, p.us))) return rc;
+    if (hipEvent_t e = p.rec(kPhUpload, 2)) HIPOK(hipEventRecord(e, sa));
+    RecordInto recording(cs->rec_a);
     // workspace wp was last used by the batch before the previous one: its epilogue re-zeroed it.
     // ev_b[wp] is recorded by every batch's stage B, whatever its stream layout, so the query is
     // never answered by a stale or never-recorded event (a timing-level change with batches in
     // flight included).
-    const bool ws_busy = cs->wused[wp] && (threaded || !stage_b_done(cs, wp));
-    if (ws_busy && (sa != s || cs->y_async[wp])) fdb_event(LaunchList::kSyncWait, cs->ev_b[wp], sa);
+    p.ws_busy = cs->wused[wp] && (p.threaded || !stage_b_done(cs, wp));
+    if (p.ws_busy && (sa != s || cs->y_async[wp])) fdb_event(LaunchList::kSyncWait, cs->ev_b[wp], sa);
     // and the check after that batch may still read its union segments and their tails
-    if (cs->xfree_rec[wp] && sa != s && (threaded || !batch_done(cs->xfree_user[wp])))
+    if (cs->xfree_rec[wp] && sa != s && (p.threaded || !batch_done(cs->xfree_user[wp])))
         fdb_event(LaunchList::kSyncWait, cs->xfree_ev[wp], sa);
     cs->xfree_rec[wp] = false;
     cs->wused[wp] = true;
     cs->ws_user[wp] = b;
     // stage A reads the batch: wait for the upload stream
-    if (own_upload || (was_uploaded && hipEventQuery(sl->ev_up) != hipSuccess))
+    if (p.own_upload || (p.was_uploaded && hipEventQuery(sl->ev_up) != hipSuccess))
         fdb_event(LaunchList::kSyncWait, sl->ev_up, sa);
     const BatchDev& bd = b->bd;
     // a routed batch's TooOld test (SkipList.cpp:770) against the oldest version every earlier
     // detect left (its routing may have run before the previous batch's detect): stage A, ahead
     // of every kernel that reads the flags (stage B)
     if (b->routed) launch_route_too_old(sa, bd, cs->oldest);
-    // long-key probes pay off once tails run past a word (a 17-byte end key k\0 of a 16-byte key
-    // ties on the prefix with k only, and the length decides)
-    const bool long_keys = b->max_len > 24;
-    Scalars* sc = (Scalars*)cs->scal.p;
-    const int bsrc = cs->cur, dsrc = cs->dcur;
-    // Stage B in two halves (fdbcs_conflict_set::ystream): X = check, resolution, D.Combine on
-    // `stream`; Y = merge, compaction / GC, epilogue on `ystream`.  Unless the previous batch
-    // compacted, this batch's check reads the delta before the previous batch's merge (buffer
-    // dsrc ^ 1, complete once the batch before it finished Y) plus the previous batch's union
-    // segments at its `now` (PrevSegs): the same history, so the check need not wait for that merge.
-    const bool pipe = !(timing == 2 || cs->serial);
-    hipStream_t ys = pipe ? cs->ystream : s;
-    const bool use_prev = pipe && cs->prev_segs;
-    const int dchk = use_prev ? dsrc ^ 1 : dsrc;
-    const Tier base{hist_of(cs, bsrc), levels_of(cs, bsrc), &sc->n, cs->header_version};
-    const Tier delta{delta_of(cs, dsrc), dlevels_of(cs, dsrc), &sc->ndb[dsrc], kHole};
-    const Tier cdelta{delta_of(cs, dchk), dlevels_of(cs, dchk), &sc->ndb[dchk], kHole};  // what the check reads
-    PrevSegs ps{};
-    if (use_prev) {
-        const Work& pw = cs->work[cs->prev_wp];
-        ps = PrevSegs{pw.segk, pw.btail, &pw.bsc->n_segments, cs->prev_now};
-    }
-    uint8_t* htail = (uint8_t*)cs->htail[cs->tcur].p;
-
-    w.trace = cs->trace ? (unsigned long long*)cs->trace_buf.p : nullptr;
-    w.no_prepass = cs->no_prepass ? 1 : 0;
-    if (w.trace) {
-        HIPOK(hipStreamSynchronize(cs->astream));
-        HIPOK(hipStreamSynchronize(s));
-        unsigned long long init[kTrSlots];
-        for (int i = 0; i < kTrSlots; i++)
-            init[i] = (i == kTrSampleBegin || i == kTrCheckBegin || i == kTrEpiBegin || i == kTrResBegin || i == kTrResW0min ||
-                       i == kTrPartBegin || i == kTrBktBegin)
-                          ? ~0ull
-                          : 0ull;
-        HIPOK(hipMemcpy(w.trace, init, sizeof(init), hipMemcpyHostToDevice));
-    }
+    if (w.trace && (rc = reset_trace(cs, w))) return rc;
     // D.Sort and the sorted positions.  Splitters: the quantiles the last batch of >= kQuantMinE
     // endpoints left (stage A runs in batch order on one stream), or this batch's ranked samples
     // when there are none yet (cold start)
-    int sort_nb = 0, sort_samples = 0;  // what the epilogue re-zeroes of the sort's scratch
     {
-        const int64_t E = 2 * (R + W);
+        const int64_t E = 2 * (p.R + p.W);
         const int nbk = sort_bucket_count(E, cs->bucket_target, w.slab_buckets);
         const bool cold = nbk > 1 && (cs->sort_cold || !cs->quant_valid);
-        sort_nb = E > 0 ? nbk : 0;
-        sort_samples = E > 0 && cold ? sort_cold_samples(E, nbk) : 0;
+        p.sort_nb = E > 0 ? nbk : 0;
+        p.sort_samples = E > 0 && cold ? sort_cold_samples(E, nbk) : 0;
         const bool write_quant = E >= kQuantMinE;
         SplitKey* qt = (SplitKey*)cs->quant.p;
         if (cs->quant_sa && cs->quant_sa != sa) {
@@ -3199,70 +3267,85 @@ int fdbcs_batch_detect_async(fdbcs_batch* b, int64_t now, int64_t new_oldest_ver
         }
         cs->quant_sa = sa;
         launch_sort(sa, bd, w, qt + cs->qcur * kQuant, write_quant ? qt + (cs->qcur ^ 1) * kQuant : nullptr, cold,
-                    cs->bucket_target, b->max_len > (int32_t)kSortNxLen, cs->validate, rec(kPhSortBegin, 1),
-                    rec(kPhSortEnd, 1));
+                    cs->bucket_target, b->max_len > (int32_t)kSortNxLen, cs->validate, p.rec(kPhSortBegin, 1),
+                    p.rec(kPhSortEnd, 1));
         if (write_quant) {
             cs->qcur ^= 1;
             cs->quant_valid = true;
         }
     }
-    mark(kPhSort);
+    p.mark(kPhSort);
     if (cs->validate) launch_validate_sort(sa, bd, w);
     w.hseq = b->seq;  // (Work is passed by value: the edge scan's finish tags its host word)
     launch_edges(sa, bd, w);
     if (sa != s) fdb_event(LaunchList::kSyncRecord, cs->ev_a[wp], sa);
-    mark(kPhEdges);
-    if (split) {  // ---- record the base-tier check (its own stream)
-        t_record = &lc;
-        hipStream_t sc_ = cs->cstream;
-        fdb_event(LaunchList::kSyncWait, sl->ev_up, sc_);
-        if (ws_busy) fdb_event(LaunchList::kSyncWait, cs->ev_b[wp], sc_);
-        if (cs->cmp_recorded && (threaded || hipEventQuery(cs->ev_cmp) != hipSuccess))
-            fdb_event(LaunchList::kSyncWait, cs->ev_cmp, sc_);
-        fdb_event(LaunchList::kTimingRecord, rec(kPhCheckBegin, 1), sc_);
-        launch_check_tier(sc_, bd, w, base, true, htail, long_keys, PrevSegs{});
-        fdb_event(LaunchList::kTimingRecord, rec(kPhCheckEnd, 1), sc_);
-        fdb_event(LaunchList::kSyncRecord, cs->ev_c[wp], sc_);
-    }
-    // ---- record stage B, half X: D.CheckRead, then batch order
-    t_record = &lb;
-    if (sa == s || !was_uploaded || hipEventQuery(sl->ev_up) != hipSuccess) fdb_event(LaunchList::kSyncWait, sl->ev_up, s);
+    p.mark(kPhEdges);
+    return FDBCS_OK;
+}
+
+// Step 5 (split check only): the record of the base-tier check, on its own stream.
+static void record_base_check(fdbcs_conflict_set* cs, fdbcs_batch* b, DetectPlan& p) {
+    RecordInto recording(cs->rec_c);
+    const int wp = p.wp;
+    hipStream_t sc_ = cs->cstream;
+    fdb_event(LaunchList::kSyncWait, p.sl->ev_up, sc_);
+    if (p.ws_busy) fdb_event(LaunchList::kSyncWait, cs->ev_b[wp], sc_);
+    if (cs->cmp_recorded && (p.threaded || hipEventQuery(cs->ev_cmp) != hipSuccess))
+        fdb_event(LaunchList::kSyncWait, cs->ev_cmp, sc_);
+    fdb_event(LaunchList::kTimingRecord, p.rec(kPhCheckBegin, 1), sc_);
+    launch_check_tier(sc_, b->bd, p.w, p.base, true, p.htail, p.long_keys, PrevSegs{});
+    fdb_event(LaunchList::kTimingRecord, p.rec(kPhCheckEnd, 1), sc_);
+    fdb_event(LaunchList::kSyncRecord, cs->ev_c[wp], sc_);
+}
+
+// Step 6: the record of stage B, half X: D.CheckRead, then batch order (resolution, D.Combine, the
+// conflict output and the report copies), ended by ev_res.
+static void record_half_x(fdbcs_conflict_set* cs, fdbcs_batch* b, DetectPlan& p) {
+    RecordInto recording(cs->rec_b);
+    hipStream_t s = p.s, sa = p.sa;
+    const int wp = p.wp;
+    const int64_t T = p.T, R = p.R;
+    Work& w = p.w;
+    BatchSlot* sl = p.sl;
+    const BatchDev& bd = b->bd;
+    const ResultLayout& RL = p.RL;
+    if (sa == s || !p.was_uploaded || hipEventQuery(sl->ev_up) != hipSuccess) fdb_event(LaunchList::kSyncWait, sl->ev_up, s);
     {
         // the delta the check reads is complete: Y of the batch before the previous one (with the
         // previous batch's segments), or of the previous batch (it compacted, or nothing pending).
         // Only a Y on ystream needs the event (a timing-level change may switch layouts mid-flight).
-        const int wy = use_prev ? cs->prev2_wp : cs->last_wp;
-        if (wy >= 0 && cs->y_async[wy] && (threaded || !stage_b_done(cs, wy)))
+        const int wy = p.use_prev ? cs->prev2_wp : cs->last_wp;
+        if (wy >= 0 && cs->y_async[wy] && (p.threaded || !stage_b_done(cs, wy)))
             fdb_event(LaunchList::kSyncWait, cs->ev_b[wy], s);
     }
-    if (split) {
+    if (p.split) {
         b->check_hist = cs->n_ub;  // the timed (base-tier) check
-        launch_check_tier(s, bd, w, cdelta, false, htail, long_keys, ps);
+        launch_check_tier(s, bd, w, p.cdelta, false, p.htail, p.long_keys, p.ps);
     } else {
         b->check_hist = cs->n_ub + cs->nd_ub;
-        fdb_event(LaunchList::kTimingRecord, rec(kPhCheckBegin, 1), s);
-        launch_check(s, bd, w, base, cdelta, htail, long_keys, ps);
-        fdb_event(LaunchList::kTimingRecord, rec(kPhCheckEnd, 1), s);
+        fdb_event(LaunchList::kTimingRecord, p.rec(kPhCheckBegin, 1), s);
+        launch_check(s, bd, w, p.base, p.cdelta, p.htail, p.long_keys, p.ps);
+        fdb_event(LaunchList::kTimingRecord, p.rec(kPhCheckEnd, 1), s);
     }
-    if (use_prev) {  // the previous batch's workspace may be reused once this check is done with it
+    if (p.use_prev) {  // the previous batch's workspace may be reused once this check is done with it
         cs->xfree_ev[cs->prev_wp] = cs->ev_res[wp];  // recorded at the end of this half X
         cs->xfree_user[cs->prev_wp] = b;
         cs->xfree_rec[cs->prev_wp] = true;
     }
-    mark(kPhCheck);
+    p.mark(kPhCheck);
     if (sa != s) fdb_event(LaunchList::kSyncWait, cs->ev_a[wp], s);
-    if (split) fdb_event(LaunchList::kSyncWait, cs->ev_c[wp], s);
+    if (p.split) fdb_event(LaunchList::kSyncWait, cs->ev_c[wp], s);
     w.vdev = (uint8_t*)sl->dverdict.p;  // (Work by value: the resolution's launches carry it)
-    launch_resolve(s, bd, w, b->any_report, (uint8_t*)sl->pin_out.dp, sc);
+    launch_resolve(s, bd, w, b->any_report, (uint8_t*)sl->pin_out.dp, p.sc);
     w.vdev = nullptr;
     if (b->out_dev && b->out_n > 0)  // multi-resolver combine input, final before the completion flag
         launch_conflict_output(s, bd, w, b->routed ? (const int32_t*)sl->rt_inv.p : (const int32_t*)sl->pin_inv.dp,
                                b->out_n, b->out_dev);
     if (b->any_report) {  // before the epilogue re-zeroes hist_conf (into the host-mapped results)
         char* hdv = (char*)sl->pin_out.dp;
-        if (R) launch_copy_bytes(s, hdv + o_rc, w.rconf, R);
-        launch_copy_bytes(s, hdv + o_hc, w.hist_conf, T);
-        launch_copy_bytes(s, hdv + o_fc, w.first_conf, 4 * T);
+        if (R) launch_copy_bytes(s, hdv + RL.rc, w.rconf, R);
+        launch_copy_bytes(s, hdv + RL.hc, w.hist_conf, T);
+        launch_copy_bytes(s, hdv + RL.fc, w.first_conf, 4 * T);
         if (b->routed) {  // the report loop's roff and flags (TooOld included: stage A is done)
             launch_copy_bytes(s, hdv + RL.ro, bd.roff, 4 * (T + 1));
             launch_copy_bytes(s, hdv + RL.fg, bd.flags, T);
@@ -3272,34 +3355,27 @@ int fdbcs_batch_detect_async(fdbcs_batch* b, int64_t now, int64_t new_oldest_ver
     // are reported without candidate edges too, so outside the resolution's skip group
     if (b->routed && b->rep_dev && b->rep_n > 0)
         launch_report_bytes(s, bd, w, (const int32_t*)sl->rt_gids.p, b->rep_n, b->rep_dev);
-    mark(kPhIntra);
-    mark(kPhCombine);
-    // ---- half Y: D.MergeWrite, compaction / GC, epilogue, after X
+    p.mark(kPhIntra);
+    p.mark(kPhCombine);
     fdb_event(LaunchList::kSyncRecord, cs->ev_res[wp], s);
-    t_record = &ly;
-    if (ys != s) fdb_event(LaunchList::kSyncWait, cs->ev_res[wp], ys);
-    const int dnew = dsrc ^ 1;
-    const int64_t nd_after = cs->nd_ub + 2 * W;
-    const int64_t new_oldest = std::max(cs->oldest, new_oldest_version);
+}
+
+// Step 7: what half Y will do: compaction, the GC turn, the delta directory's epoch.  Host state
+// only: nothing is recorded and nothing can fail, so the policy reads (and changes) in one place.
+static void decide_y(fdbcs_conflict_set* cs, fdbcs_batch* b, DetectPlan& p) {
+    const int dnew = p.dnew = p.dsrc ^ 1;
+    p.nd_after = cs->nd_ub + 2 * p.W;
+    p.new_oldest = std::max(cs->oldest, p.oldest_arg);
     // Compaction when the delta may outgrow its bound (or on the forced cadence); removeBefore
     // (SkipList.cpp:880-889) runs with it whenever the oldest version moved.
-    bool compact = nd_after > delta_limit_for(cs, cs->n_ub);
+    bool compact = p.nd_after > delta_limit_for(cs, cs->n_ub);
     if (cs->gc_interval > 0 && ++cs->batches_since_compact >= cs->gc_interval) compact = true;
     if (cs->tail_ub > cs->tail_reclaim) compact = true;
-    // D.MergeWrite into the delta tier
-    char* hd = (char*)sl->pin_out.dp;
-    launch_merge(ys, bd, w, delta.h, delta.m, delta_of(cs, dnew), dlevels_of(cs, dnew), &sc->ndb[dsrc], htail, sc, now,
-                 cs->dlvl3_n, cs->dlvl2_n, cs->nd_ub + 1, rec(kPhCopyBegin, 1), rec(kPhCopyEnd, 1), long_keys);
-    mark(kPhMerge);
     bool gc = false;
-    int final_base = bsrc;
-    const int64_t base_hint = cs->n_ub + nd_after + 1;
+    p.final_base = p.bsrc;
+    p.base_hint = cs->n_ub + p.nd_after + 1;
     if (compact) {
-        launch_compact(ys, w, base.h, base.m, delta_of(cs, dnew), hist_of(cs, bsrc ^ 1), htail, sc,
-                       cs->header_version, cs->lvl3_n, cs->lvl2_n, nd_after + 1, cs->n_ub + 1, rec(kPhCompBegin, 1),
-                       rec(kPhCompEnd, 1), long_keys ? 2 : 1, cs->n_ub <= (16 << 20) ? 1024 : 4096,
-                       cs->n_ub > (16 << 20));
-        final_base = bsrc ^ 1;
+        p.final_base = p.bsrc ^ 1;
         cs->batches_since_compact = 0;
         // Size-triggered compactions (gc_interval 0) run removeBefore on every kGcEveryCompactions-th
         // one: a full pass over the base costs ~10x the compaction copy at C2 while one
@@ -3308,32 +3384,60 @@ int fdbcs_batch_detect_async(fdbcs_batch* b, int64_t now, int64_t new_oldest_ver
         // either way; a forced cadence (gc_interval > 0) keeps GC at every compaction.  Past the
         // tail-reclaim threshold the GC also repacks the tail arena.
         const bool gc_turn = cs->gc_interval > 0 || ++cs->compactions_since_gc >= kGcEveryCompactions;
-        gc = (new_oldest > cs->gc_applied && gc_turn) || cs->tail_ub > cs->tail_reclaim;
+        gc = (p.new_oldest > cs->gc_applied && gc_turn) || cs->tail_ub > cs->tail_reclaim;
         if (gc) cs->compactions_since_gc = 0;
     }
-    mark(kPhCompact);
-    if (gc) {
-        launch_gc(ys, w, hist_of(cs, final_base), hist_of(cs, final_base ^ 1), htail,
-                  (uint8_t*)cs->htail[cs->tcur ^ 1].p, sc, std::max(new_oldest, cs->gc_applied), cs->header_version,
-                  base_hint);
+    if (gc) {  // from the compaction's output into the other base buffer and the other tail arena
+        p.gc_htail = (uint8_t*)cs->htail[cs->tcur ^ 1].p;
+        p.gc_oldest = std::max(p.new_oldest, cs->gc_applied);
         cs->tcur ^= 1;
-        final_base ^= 1;
-        cs->gc_applied = new_oldest;
+        p.final_base ^= 1;
+        cs->gc_applied = p.new_oldest;
     }
-    mark(kPhGc);
-    b->gc_ran = gc;
-    b->compacted = compact;
+    p.compact = b->compacted = compact;
+    p.gc = b->gc_ran = gc;
     // the epilogue that rebuilds the delta tier's index also fills its directory under a new epoch
     // (a compaction leaves none).  The epoch tag is 32 bits: before it wraps, every entry is
-    // cleared (ensure_delta_directory), so a slot an old fill left behind is never trusted.
+    // cleared (detect_admit), so a slot an old fill left behind is never trusted.
+    p.merge_dlv = dlevels_of(cs, dnew);  // (the merge's launches carry the epoch the buffer had)
     if (compact || !cs->edir[dnew].p) {
         cs->ddir_epoch[dnew] = 0;
     } else {
         cs->ddir_epoch[dnew] = ++cs->ddir_counter;
     }
-    launch_epilogue(ys, bd, w, compact ? levels_of(cs, final_base) : dlevels_of(cs, dnew), sc, compact ? 1 : 0,
-                    gc ? 1 : 0, (uint8_t*)hd, (uint32_t*)(hd + o_fl), b->seq,
-                    compact ? base_hint : nd_after + 1, &sc->ndb[dnew], sort_nb, sort_samples);
+}
+
+// Step 8: the record of stage B, half Y, after X (ev_res): D.MergeWrite, compaction / GC and the
+// epilogue, ended by ev_b (and ev_cmp when the base was rewritten).
+static void record_half_y(fdbcs_conflict_set* cs, fdbcs_batch* b, DetectPlan& p) {
+    RecordInto recording(cs->rec_y);
+    hipStream_t s = p.s, ys = p.ys;
+    const int wp = p.wp, bsrc = p.bsrc, dsrc = p.dsrc, dnew = p.dnew;
+    const int64_t nd_after = p.nd_after;
+    const bool compact = p.compact, gc = p.gc, long_keys = p.long_keys;
+    Work& w = p.w;
+    const BatchDev& bd = b->bd;
+    Scalars* sc = p.sc;
+    uint8_t* htail = p.htail;
+    if (ys != s) fdb_event(LaunchList::kSyncWait, cs->ev_res[wp], ys);
+    // D.MergeWrite into the delta tier
+    char* hd = (char*)p.sl->pin_out.dp;
+    launch_merge(ys, bd, w, p.delta.h, p.delta.m, delta_of(cs, dnew), p.merge_dlv, &sc->ndb[dsrc], htail, sc,
+                 p.now, cs->dlvl3_n, cs->dlvl2_n, cs->nd_ub + 1, p.rec(kPhCopyBegin, 1), p.rec(kPhCopyEnd, 1), long_keys);
+    p.mark(kPhMerge);
+    if (compact)
+        launch_compact(ys, w, p.base.h, p.base.m, delta_of(cs, dnew), hist_of(cs, bsrc ^ 1), htail, sc,
+                       cs->header_version, cs->lvl3_n, cs->lvl2_n, nd_after + 1, cs->n_ub + 1, p.rec(kPhCompBegin, 1),
+                       p.rec(kPhCompEnd, 1), long_keys ? 2 : 1, cs->n_ub <= (16 << 20) ? 1024 : 4096,
+                       cs->n_ub > (16 << 20));
+    p.mark(kPhCompact);
+    if (gc)  // (final_base already names the buffer the GC writes)
+        launch_gc(ys, w, hist_of(cs, p.final_base ^ 1), hist_of(cs, p.final_base), htail, p.gc_htail, sc, p.gc_oldest,
+                  cs->header_version, p.base_hint);
+    p.mark(kPhGc);
+    launch_epilogue(ys, bd, w, compact ? levels_of(cs, p.final_base) : dlevels_of(cs, dnew), sc, compact ? 1 : 0,
+                    gc ? 1 : 0, (uint8_t*)hd, (uint32_t*)(hd + p.RL.fl), b->seq,
+                    compact ? p.base_hint : nd_after + 1, &sc->ndb[dnew], p.sort_nb, p.sort_samples);
     fdb_event(LaunchList::kSyncRecord, cs->ev_b[wp], ys);
     // (no event marks the slot free: a slot returns to the pool only from fdbcs_batch_destroy,
     // after the batch's completion flag was seen or its streams were synchronized; every kernel
@@ -3342,13 +3446,16 @@ int fdbcs_batch_detect_async(fdbcs_batch* b, int64_t now, int64_t new_oldest_ver
         fdb_event(LaunchList::kSyncRecord, cs->ev_cmp, ys);
         cs->cmp_recorded = true;
     }
-    mark(kPhEpilogue);
-    mark(kPhEnd);
-    t_record = nullptr;
-    cs->stats.host_ms_record += host_ms_since(t_rec);
-    const auto t_sub = std::chrono::steady_clock::now();
-    // ---- submit
-    if (threaded) {
+    p.mark(kPhEpilogue);
+    p.mark(kPhEnd);
+}
+
+// Step 9: hand the lists to the helper thread, or issue them now.
+static int submit_lists(fdbcs_conflict_set* cs, fdbcs_batch* b, DetectPlan& p) {
+    LaunchList &la = cs->rec_a, &lb = cs->rec_b, &lc = cs->rec_c, &ly = cs->rec_y;
+    hipStream_t s = p.s, sa = p.sa, ys = p.ys;
+    int rc;
+    if (p.threaded) {
         // the helper issues this batch's stage A and check while this thread issues the
         // previous batch's stage B; this batch's stage B waits for the next call (or a flush)
         if ((rc = worker_wait(cs))) return rc;
@@ -3385,37 +3492,268 @@ int fdbcs_batch_detect_async(fdbcs_batch* b, int64_t now, int64_t new_oldest_ver
         return FDBCS_E_DEVICE;
     } else {
         HIPOK(la.replay(sa));
-        if (split) HIPOK(lc.replay(cs->cstream));
+        if (p.split) HIPOK(lc.replay(cs->cstream));
         HIPOK(lb.replay(s));
         HIPOK(ly.replay(ys));
     }
     HIPOK(take_launch_error());
-    cs->stats.host_ms_submit += host_ms_since(t_sub);
-    cs->cur = final_base;
-    cs->dcur = dnew;
+    return FDBCS_OK;
+}
+
+// Step 10: the batch is on its way: roll the set's cross-batch state forward.
+static void commit_batch(fdbcs_conflict_set* cs, fdbcs_batch* b, const DetectPlan& p) {
+    const int wp = p.wp;
+    cs->cur = p.final_base;
+    cs->dcur = p.dnew;
     // the next batch's check: this batch's segments stand in for its merge unless it compacted
-    cs->prev_segs = pipe && !compact;
+    cs->prev_segs = p.pipe && !p.compact;
     cs->prev2_wp = cs->last_wp;
     cs->last_wp = wp;
-    cs->y_async[wp] = ys != s;
+    cs->y_async[wp] = p.ys != p.s;
     cs->prev_wp = wp;
-    cs->prev_now = now;
-    cs->oldest = new_oldest;  // SkipList.cpp:880-882
-    if (W) cs->max_written = std::max(cs->max_written, now);
-    if (compact) {
-        cs->n_ub += nd_after;
+    cs->prev_now = p.now;
+    cs->oldest = p.new_oldest;  // SkipList.cpp:880-882
+    if (p.W) cs->max_written = std::max(cs->max_written, p.now);
+    if (p.compact) {
+        cs->n_ub += p.nd_after;
         cs->nd_ub = 0;
     } else {
-        cs->nd_ub = nd_after;
+        cs->nd_ub = p.nd_after;
     }
-    cs->tail_ub += tail_add;
+    cs->tail_ub += p.tail_add;
     cs->inflight++;
     cs->x_valid = false;
     b->state = 2;
-    if (cs->htrace)
-        cs->htr[0].push_back({b->seq, 'D',
-                              (int64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(t_begin.time_since_epoch()).count(),
-                              mono_ns()});
+    if (cs->htrace) cs->htr[0].push_back({b->seq, 'D', mono_ns(p.t_begin), mono_ns()});
+}
+
+int fdbcs_batch_detect_async(fdbcs_batch* b, int64_t now, int64_t new_oldest_version) {
+    if (!b) return FDBCS_E_INVALID;
+    if (!b->cs) return FDBCS_E_STATE;
+    if (b->state > 1) return FDBCS_E_STATE;
+    fdbcs_conflict_set* cs = b->cs;
+    DetectPlan p(cs, b, now, new_oldest_version);
+    int rc;
+    if ((rc = detect_admit(cs, b, p))) return rc;
+    if ((rc = detect_bind_results(cs, b, p))) return rc;
+    plan_layout(cs, b, p);
+    cs->stats.host_ms_prepare += host_ms_since(p.t_begin);
+    const auto t_rec = std::chrono::steady_clock::now();
+    plan_views(cs, p);
+    if ((rc = record_stage_a(cs, b, p))) return rc;
+    if (p.split) record_base_check(cs, b, p);
+    record_half_x(cs, b, p);
+    decide_y(cs, b, p);
+    record_half_y(cs, b, p);
+    cs->stats.host_ms_record += host_ms_since(t_rec);
+    const auto t_sub = std::chrono::steady_clock::now();
+    if ((rc = submit_lists(cs, b, p))) return rc;
+    cs->stats.host_ms_submit += host_ms_since(t_sub);
+    commit_batch(cs, b, p);
+    return FDBCS_OK;
+}
+
+// ---- the wait for a detected batch, step by step
+
+// Until the batch's completion flag is seen: its stage B issued if it still waits for the next
+// detect or for the helper, then the spin.
+static int wait_flag(fdbcs_conflict_set* cs, fdbcs_batch* b) {
+    const int64_t tw0 = cs->htrace ? mono_ns() : 0;
+    HIPOK(hipSetDevice(cs->device));
+    if (cs->pending_batch == b)  // its stage B still waits for the next detect: launch it now
+        if (int rc = flush_pending(cs)) return rc;
+    if (cs->work_y_batch == b)  // its Y is with the helper: issued (events and all) before reading them
+        if (int rc = worker_wait(cs)) return rc;
+    // the epilogue publishes b->seq; poll it, checking the streams for errors only every ~2 ms:
+    // hipStreamQuery takes runtime locks the helper thread's launches need, so querying at
+    // the spin rate slows the submission of the batches behind this one
+    auto t_q = std::chrono::steady_clock::now();
+    for (uint64_t spin = 0; *b->h_flag != b->seq; spin++) {
+        __builtin_ia32_pause();
+        if ((spin & 4095) != 4095) continue;
+        if (std::chrono::steady_clock::now() - t_q < std::chrono::milliseconds(cs->wait_query_ms)) continue;
+        t_q = std::chrono::steady_clock::now();
+        // the flag comes from the epilogue (stage B's Y half): done or failing once both
+        // halves are idle
+        hipError_t e = hipStreamQuery(cs->astream);
+        if (e == hipSuccess || e == hipErrorNotReady) e = hipStreamQuery(cs->stream);
+        if (e == hipSuccess) e = hipStreamQuery(cs->ystream);
+        if (e != hipSuccess && e != hipErrorNotReady) {
+            fprintf(stderr, "fdbcs: stream error while waiting: %s\n", hipGetErrorString(e));
+            return FDBCS_E_DEVICE;
+        }
+        if (e == hipSuccess && *b->h_flag != b->seq) {
+            fprintf(stderr, "fdbcs: stream idle but batch %u not completed\n", b->seq);
+            return FDBCS_E_DEVICE;
+        }
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    if (cs->htrace) cs->htr[0].push_back({b->seq, 'W', tw0, mono_ns()});
+    return FDBCS_OK;
+}
+
+// FDBCS_TRACE=1: the device timestamps of the batch's kernel sections, printed.
+static int print_trace(fdbcs_conflict_set* cs, const fdbcs_batch* b) {
+    if (int rc = sync_all(cs)) return rc;
+    unsigned long long tr[kTrSlots];
+    HIPOK(hipMemcpy(tr, cs->trace_buf.p, sizeof(tr), hipMemcpyDeviceToHost));
+    auto us = [&](int a, int z) { return (double)((long long)(tr[z] - tr[a])) / 100.0; };  // 100 MHz
+    fprintf(stderr,
+            "fdbcs trace: sample %.2f us, check %.2f us (check starts %+.2f us after sample); epilogue "
+            "levels %.2f, zero %.2f, host %.2f, fence %.2f us\n",
+            us(kTrSampleBegin, kTrSampleEnd), us(kTrCheckBegin, kTrCheckEnd), us(kTrSampleBegin, kTrCheckBegin),
+            us(kTrEpiBegin, kTrEpiLevels), us(kTrEpiLevels, kTrEpiZero), us(kTrEpiZero, kTrEpiHost),
+            us(kTrEpiHost, kTrEpiFence));
+    fprintf(stderr,
+            "fdbcs trace: sort partition fill %.2f, search %.2f, end %.2f us; bucket prologue %.2f, "
+            "sorted %.2f, ties %.2f, end %.2f us (partition start to bucket start %.2f us)\n",
+            us(kTrPartBegin, kTrPartFill), us(kTrPartBegin, kTrPartSearch), us(kTrPartBegin, kTrPartEnd),
+            us(kTrBktBegin, kTrBktPrologue), us(kTrBktBegin, kTrBktSorted), us(kTrBktBegin, kTrBktTies),
+            us(kTrBktBegin, kTrBktEnd), us(kTrPartBegin, kTrBktBegin));
+    const double nw = tr[kTrBktWaves] ? (double)tr[kTrBktWaves] : 1.0;
+    fprintf(stderr,
+            "fdbcs trace: bucket tie runs: %llu lanes in runs, %llu ranked in registers, %llu serially, "
+            "longest run %llu\n",
+            tr[kTrBktRuns], tr[kTrBktSimple], tr[kTrBktSlow], tr[kTrBktMaxRun]);
+    fprintf(stderr, "fdbcs trace: bucket per wave (%llu waves): load %.2f, sort %.2f, ties %.2f, put %.2f us\n",
+            tr[kTrBktWaves], tr[kTrBktSumLoad] / nw / 100.0, tr[kTrBktSumSort] / nw / 100.0,
+            tr[kTrBktSumTies] / nw / 100.0, tr[kTrBktSumPut] / nw / 100.0);
+    const double np = tr[kTrPartWaves] ? (double)tr[kTrPartWaves] : 1.0;
+    fprintf(stderr,
+            "fdbcs trace: partition per wave (%llu waves): fill %.2f, tail copy %.2f, search %.2f, "
+            "place %.2f us\n",
+            tr[kTrPartWaves], tr[kTrPartSumFill] / np / 100.0, tr[kTrPartSumCopy] / np / 100.0,
+            tr[kTrPartSumSearch] / np / 100.0, tr[kTrPartSumPlace] / np / 100.0);
+    fprintf(stderr,
+            "fdbcs trace: resolve pre-pass %.2f us, wait %.2f us, rounds %.2f us (setup %.2f, first round "
+            "%.2f of which minima %.2f, %d rounds), finish %.2f us; waves start %.2f..%.2f us before the first kernarg use\n",
+            us(kTrResBegin, kTrResPre), us(kTrResPre, kTrResWait), us(kTrResWait, kTrResRounds),
+            us(kTrResWait, kTrResSetup), us(kTrResSetup, kTrResRound1), us(kTrResSetup, kTrResMin1),
+            (int)b->h_scal->intra_rounds, us(kTrResRounds, kTrResEnd), us(kTrResW0min, kTrResWait),
+            us(kTrResW0max, kTrResWait));
+    fprintf(stderr, "fdbcs trace: combine chunk 0: loads %.2f, scan1 %.2f, scan2 %.2f, stores %.2f us\n",
+            us(kTrResRounds, kTrCmbLoad), us(kTrCmbLoad, kTrCmbScan1), us(kTrCmbScan1, kTrCmbScan2),
+            us(kTrCmbScan2, kTrCmbStore));
+    return FDBCS_OK;
+}
+
+// conflictingKeyRangeMap: every conflicting read for history conflicts (SkipList.cpp:641-645),
+// the first for intra-batch conflicts (SkipList.cpp:821-828).
+static void rebuild_conflicting_reads(fdbcs_batch* b) {
+    const int32_t T = b->T();
+    b->conf_off.assign(T + 1, 0);
+    b->conf_idx.clear();
+    if (!b->any_report) return;
+    // (a routed batch: the sub-transaction's own indexInTx, as the resolver's map holds it)
+    const int32_t* roff = b->h_roff;
+    const uint8_t* flags = b->h_flags;
+    for (int32_t t = 0; t < T; t++) {
+        if ((flags[t] & kFlagReport) && b->h_verdict[t] == FDBCS_TRANSACTION_CONFLICT) {
+            if (b->h_hist[t]) {
+                for (int32_t r = roff[t]; r < roff[t + 1]; r++)
+                    if (b->h_rconf[r]) b->conf_idx.push_back(r - roff[t]);
+            } else if (b->h_first[t] != INT_MAX) {
+                b->conf_idx.push_back(b->h_first[t]);
+            }
+        }
+        b->conf_off[t + 1] = (int32_t)b->conf_idx.size();
+    }
+}
+
+// The finished batch's share of the set's stats: counts, the phase and roofline times of the
+// events it recorded (synchronized first) and the per-kernel profile.
+static int account_stats(fdbcs_conflict_set* cs, fdbcs_batch* b) {
+    fdbcs_stats& st = cs->stats;
+    st.batches++;
+    st.transactions += b->T();
+    st.read_ranges += b->R();
+    st.write_ranges += b->W();
+    // timing events may trail the completion flag: wait for the last one recorded
+    for (int e : {(int)kPhEnd, (int)kPhCompEnd, (int)kPhCopyEnd, (int)kPhCheckEnd})
+        if ((b->recorded >> e) & 1u) {
+            HIPOK(hipEventSynchronize(b->slot->ev[e]));
+            break;
+        }
+    for (const auto& sp : b->slot->prof_spans) {  // per-kernel events (levels 3 and 1)
+        HIPOK(hipEventSynchronize(sp.second.second));
+        const double ms = ev_ms(sp.second.first, sp.second.second);
+        auto it = std::find_if(cs->kprof.begin(), cs->kprof.end(), [&](const auto& k) { return k.func == sp.first; });
+        if (it == cs->kprof.end()) {
+            cs->kprof.push_back({sp.first, 0, 0.0});
+            it = cs->kprof.end() - 1;
+        }
+        it->launches += 1;
+        it->ms += ms;
+    }
+    b->slot->prof_spans.clear();
+    auto ph = [&](int a, int z) {
+        return ((b->recorded >> a) & (b->recorded >> z) & 1u) ? ev_ms(b->slot->ev[a], b->slot->ev[z]) : 0.0;
+    };
+    st.ms_upload += ph(kPhStart, kPhUpload);
+    st.ms_sort += ph(kPhUpload, kPhSort);
+    st.ms_intra += ph(kPhSort, kPhEdges) + ph(kPhCheck, kPhIntra);
+    st.ms_check_read += ph(kPhEdges, kPhCheck);
+    st.ms_combine += ph(kPhIntra, kPhCombine);
+    st.ms_merge += ph(kPhCombine, kPhMerge);
+    st.ms_compact += ph(kPhMerge, kPhCompact);
+    st.ms_gc += ph(kPhCompact, kPhGc);
+    st.ms_epilogue += ph(kPhGc, kPhEpilogue);
+    st.ms_total += ph(kPhUpload, kPhEnd);
+    // roofline inputs: a kernel's launches, bytes and device time are counted together, on the
+    // batches whose events were recorded (timing level 1 samples 1 batch in timing_every)
+    if (b->h_scal->intra_edges < 0) {
+        st.intra_fallbacks += 1;
+    } else {
+        st.intra_edges += b->h_scal->intra_edges;
+        st.intra_rounds += b->h_scal->intra_rounds;
+    }
+    // algorithmic bytes of the copy kernels (roofline.py): read every kept old boundary and
+    // every inserted one (its key from the batch), write every boundary of the result, 32 B
+    // each (16 B key, 8 B length/tail, 8 B version); kept + inserted = the result's size
+    {
+        const int64_t kept = b->h_scal->d_before - b->h_scal->d_rem, out = b->h_scal->nd_next;
+        const int64_t bytes = 32 * (kept + (out - kept) + out);
+        st.merge_bytes_all += bytes;
+        st.delta_sum += b->h_scal->d_before;
+        st.base_sum += b->h_scal->n;
+        st.segments_sum += b->h_scal->n_segments;
+        if ((b->recorded >> kPhCopyEnd) & 1u) {
+            st.ms_merge_kernel += ph(kPhCopyBegin, kPhCopyEnd);
+            st.merge_launches += 1;
+            st.merge_bytes += bytes;
+        }
+    }
+    if ((b->recorded >> kPhCheckEnd) & 1u) {
+        st.ms_check_kernel += ph(kPhCheckBegin, kPhCheckEnd);
+        st.check_launches += b->R() > 0;
+        st.check_reads += b->R();
+        st.check_history += b->R() > 0 ? b->check_hist : 0;
+    }
+    if ((b->recorded >> kPhSortEnd) & 1u) {
+        st.ms_sort_kernel += ph(kPhSortBegin, kPhSortEnd);
+        st.sort_launches += 1;
+        st.sort_items += 2 * (int64_t)(b->R() + b->W());
+    }
+    st.gc_runs += b->gc_ran ? 1 : 0;
+    st.sort_big_buckets += b->h_scal->sort_big;
+    if (b->routed && b->slot->rt_timed) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, b->slot->ev_rt0, b->slot->ev_rt1) == hipSuccess) st.ms_route_kernels += ms;
+        st.routed_batches += 1;
+        b->slot->rt_timed = false;
+    }
+    if (b->compacted) {
+        st.compactions += 1;
+        // kept base boundaries read, delta boundaries inserted read, result written
+        const int64_t kept = b->h_scal->c_before - b->h_scal->c_rem;
+        const int64_t bytes = 32 * (kept + (b->h_scal->n_next - kept) + b->h_scal->n_next);
+        st.compact_bytes_all += bytes;
+        if ((b->recorded >> kPhCompEnd) & 1u) {
+            st.ms_compact_kernel += ph(kPhCompBegin, kPhCompEnd);
+            st.compact_launches += 1;
+            st.compact_bytes += bytes;
+        }
+    }
     return FDBCS_OK;
 }
 
@@ -3424,84 +3762,9 @@ int fdbcs_batch_wait(fdbcs_batch* b, uint8_t* verdicts, int32_t* n_committed, in
     if (b->state == 2 && !b->cs) return FDBCS_E_STATE;
     fdbcs_conflict_set* cs = b->cs;
     if (b->state == 2) {
-        const int64_t tw0 = cs->htrace ? mono_ns() : 0;
-        HIPOK(hipSetDevice(cs->device));
-        if (cs->pending_batch == b)  // its stage B still waits for the next detect: launch it now
-            if (int rc = flush_pending(cs)) return rc;
-        if (cs->work_y_batch == b)  // its Y is with the helper: issued (events and all) before reading them
-            if (int rc = worker_wait(cs)) return rc;
-        // the epilogue publishes b->seq; poll it, checking the streams for errors only every ~2 ms:
-        // hipStreamQuery takes runtime locks the helper thread's launches need, so querying at
-        // the spin rate slows the submission of the batches behind this one
-        auto t_q = std::chrono::steady_clock::now();
-        for (uint64_t spin = 0; *b->h_flag != b->seq; spin++) {
-            __builtin_ia32_pause();
-            if ((spin & 4095) != 4095) continue;
-            if (std::chrono::steady_clock::now() - t_q < std::chrono::milliseconds(cs->wait_query_ms)) continue;
-            t_q = std::chrono::steady_clock::now();
-            {
-                // the flag comes from the epilogue (stage B's Y half): done or failing once both
-                // halves are idle
-                hipError_t e = hipStreamQuery(cs->astream);
-                if (e == hipSuccess || e == hipErrorNotReady) e = hipStreamQuery(cs->stream);
-                if (e == hipSuccess) e = hipStreamQuery(cs->ystream);
-                if (e != hipSuccess && e != hipErrorNotReady) {
-                    fprintf(stderr, "fdbcs: stream error while waiting: %s\n", hipGetErrorString(e));
-                    return FDBCS_E_DEVICE;
-                }
-                if (e == hipSuccess && *b->h_flag != b->seq) {
-                    fprintf(stderr, "fdbcs: stream idle but batch %u not completed\n", b->seq);
-                    return FDBCS_E_DEVICE;
-                }
-            }
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-        if (cs->htrace) cs->htr[0].push_back({b->seq, 'W', tw0, mono_ns()});
-        if (cs->trace && cs->inflight == 1) {
-            if (int rc = sync_all(cs)) return rc;
-            unsigned long long tr[kTrSlots];
-            HIPOK(hipMemcpy(tr, cs->trace_buf.p, sizeof(tr), hipMemcpyDeviceToHost));
-            auto us = [&](int a, int z) { return (double)((long long)(tr[z] - tr[a])) / 100.0; };  // 100 MHz
-            fprintf(stderr,
-                    "fdbcs trace: sample %.2f us, check %.2f us (check starts %+.2f us after sample); epilogue "
-                    "levels %.2f, zero %.2f, host %.2f, fence %.2f us\n",
-                    us(kTrSampleBegin, kTrSampleEnd), us(kTrCheckBegin, kTrCheckEnd), us(kTrSampleBegin, kTrCheckBegin),
-                    us(kTrEpiBegin, kTrEpiLevels), us(kTrEpiLevels, kTrEpiZero), us(kTrEpiZero, kTrEpiHost),
-                    us(kTrEpiHost, kTrEpiFence));
-            fprintf(stderr,
-                    "fdbcs trace: sort partition fill %.2f, search %.2f, end %.2f us; bucket prologue %.2f, "
-                    "sorted %.2f, ties %.2f, end %.2f us (partition start to bucket start %.2f us)\n",
-                    us(kTrPartBegin, kTrPartFill), us(kTrPartBegin, kTrPartSearch), us(kTrPartBegin, kTrPartEnd),
-                    us(kTrBktBegin, kTrBktPrologue), us(kTrBktBegin, kTrBktSorted), us(kTrBktBegin, kTrBktTies),
-                    us(kTrBktBegin, kTrBktEnd),
-                    us(kTrPartBegin, kTrBktBegin));
-            {
-                const double nw = tr[kTrBktWaves] ? (double)tr[kTrBktWaves] : 1.0;
-                fprintf(stderr, "fdbcs trace: bucket tie runs: %llu lanes in runs, %llu ranked in registers, %llu serially, "
-                        "longest run %llu\n", tr[kTrBktRuns], tr[kTrBktSimple], tr[kTrBktSlow], tr[kTrBktMaxRun]);
-                fprintf(stderr,
-                        "fdbcs trace: bucket per wave (%llu waves): load %.2f, sort %.2f, ties %.2f, put %.2f us\n",
-                        tr[kTrBktWaves], tr[kTrBktSumLoad] / nw / 100.0, tr[kTrBktSumSort] / nw / 100.0,
-                        tr[kTrBktSumTies] / nw / 100.0, tr[kTrBktSumPut] / nw / 100.0);
-                const double np = tr[kTrPartWaves] ? (double)tr[kTrPartWaves] : 1.0;
-                fprintf(stderr,
-                        "fdbcs trace: partition per wave (%llu waves): fill %.2f, tail copy %.2f, search %.2f, "
-                        "place %.2f us\n",
-                        tr[kTrPartWaves], tr[kTrPartSumFill] / np / 100.0, tr[kTrPartSumCopy] / np / 100.0,
-                        tr[kTrPartSumSearch] / np / 100.0, tr[kTrPartSumPlace] / np / 100.0);
-            }
-            fprintf(stderr, "fdbcs trace: resolve pre-pass %.2f us, wait %.2f us, rounds %.2f us (setup %.2f, first round "
-                    "%.2f of which minima %.2f, %d rounds), finish %.2f us; waves start %.2f..%.2f us before the first kernarg use\n",
-                    us(kTrResBegin, kTrResPre), us(kTrResPre, kTrResWait), us(kTrResWait, kTrResRounds),
-                    us(kTrResWait, kTrResSetup), us(kTrResSetup, kTrResRound1), us(kTrResSetup, kTrResMin1),
-                    (int)b->h_scal->intra_rounds,
-                    us(kTrResRounds, kTrResEnd), us(kTrResW0min, kTrResWait), us(kTrResW0max, kTrResWait));
-            fprintf(stderr, "fdbcs trace: combine chunk 0: loads %.2f, scan1 %.2f, scan2 %.2f, stores %.2f us\n",
-                    us(kTrResRounds, kTrCmbLoad), us(kTrCmbLoad, kTrCmbScan1), us(kTrCmbScan1, kTrCmbScan2),
-                    us(kTrCmbScan2, kTrCmbStore));
-
-
-        }
+        int rc;
+        if ((rc = wait_flag(cs, b))) return rc;
+        if (cs->trace && cs->inflight == 1 && (rc = print_trace(cs, b))) return rc;
         if (b->h_scal->debug_error) {
             fprintf(stderr, "fdbcs: device invariant check failed (debug_error=%d)\n", b->h_scal->debug_error);
             cs->inflight--;
@@ -3516,118 +3779,8 @@ int fdbcs_batch_wait(fdbcs_batch* b, uint8_t* verdicts, int32_t* n_committed, in
         }
         b->n_committed = nc;
         b->n_too_old = nt;
-        // conflictingKeyRangeMap: every conflicting read for history conflicts (SkipList.cpp:641-645),
-        // the first for intra-batch conflicts (SkipList.cpp:821-828).
-        b->conf_off.assign(T + 1, 0);
-        b->conf_idx.clear();
-        if (b->any_report) {
-            // (a routed batch: the sub-transaction's own indexInTx, as the resolver's map holds it)
-            const int32_t* roff = b->h_roff;
-            const uint8_t* flags = b->h_flags;
-            for (int32_t t = 0; t < T; t++) {
-                if ((flags[t] & kFlagReport) && b->h_verdict[t] == FDBCS_TRANSACTION_CONFLICT) {
-                    if (b->h_hist[t]) {
-                        for (int32_t r = roff[t]; r < roff[t + 1]; r++)
-                            if (b->h_rconf[r]) b->conf_idx.push_back(r - roff[t]);
-                    } else if (b->h_first[t] != INT_MAX) {
-                        b->conf_idx.push_back(b->h_first[t]);
-                    }
-                }
-                b->conf_off[t + 1] = (int32_t)b->conf_idx.size();
-            }
-        }
-        // stats
-        fdbcs_stats& st = cs->stats;
-        st.batches++;
-        st.transactions += T;
-        st.read_ranges += b->R();
-        st.write_ranges += b->W();
-        // timing events may trail the completion flag: wait for the last one recorded
-        for (int e : {(int)kPhEnd, (int)kPhCompEnd, (int)kPhCopyEnd, (int)kPhCheckEnd})
-            if ((b->recorded >> e) & 1u) {
-                HIPOK(hipEventSynchronize(b->slot->ev[e]));
-                break;
-            }
-        for (const auto& sp : b->slot->prof_spans) {  // per-kernel events (levels 3 and 1)
-            HIPOK(hipEventSynchronize(sp.second.second));
-            const double ms = ev_ms(sp.second.first, sp.second.second);
-            auto it = std::find_if(cs->kprof.begin(), cs->kprof.end(), [&](const auto& k) { return k.func == sp.first; });
-            if (it == cs->kprof.end()) {
-                cs->kprof.push_back({sp.first, 0, 0.0});
-                it = cs->kprof.end() - 1;
-            }
-            it->launches += 1;
-            it->ms += ms;
-        }
-        b->slot->prof_spans.clear();
-        auto ph = [&](int a, int z) {
-            return ((b->recorded >> a) & (b->recorded >> z) & 1u) ? ev_ms(b->slot->ev[a], b->slot->ev[z]) : 0.0;
-        };
-        st.ms_upload += ph(kPhStart, kPhUpload);
-        st.ms_sort += ph(kPhUpload, kPhSort);
-        st.ms_intra += ph(kPhSort, kPhEdges) + ph(kPhCheck, kPhIntra);
-        st.ms_check_read += ph(kPhEdges, kPhCheck);
-        st.ms_combine += ph(kPhIntra, kPhCombine);
-        st.ms_merge += ph(kPhCombine, kPhMerge);
-        st.ms_compact += ph(kPhMerge, kPhCompact);
-        st.ms_gc += ph(kPhCompact, kPhGc);
-        st.ms_epilogue += ph(kPhGc, kPhEpilogue);
-        st.ms_total += ph(kPhUpload, kPhEnd);
-        // roofline inputs: a kernel's launches, bytes and device time are counted together, on the
-        // batches whose events were recorded (timing level 1 samples 1 batch in timing_every)
-        if (b->h_scal->intra_edges < 0) {
-            st.intra_fallbacks += 1;
-        } else {
-            st.intra_edges += b->h_scal->intra_edges;
-            st.intra_rounds += b->h_scal->intra_rounds;
-        }
-        // algorithmic bytes of the copy kernels (roofline.py): read every kept old boundary and
-        // every inserted one (its key from the batch), write every boundary of the result, 32 B
-        // each (16 B key, 8 B length/tail, 8 B version); kept + inserted = the result's size
-        {
-            const int64_t kept = b->h_scal->d_before - b->h_scal->d_rem, out = b->h_scal->nd_next;
-            const int64_t bytes = 32 * (kept + (out - kept) + out);
-            st.merge_bytes_all += bytes;
-            st.delta_sum += b->h_scal->d_before;
-            st.base_sum += b->h_scal->n;
-            st.segments_sum += b->h_scal->n_segments;
-            if ((b->recorded >> kPhCopyEnd) & 1u) {
-                st.ms_merge_kernel += ph(kPhCopyBegin, kPhCopyEnd);
-                st.merge_launches += 1;
-                st.merge_bytes += bytes;
-            }
-        }
-        if ((b->recorded >> kPhCheckEnd) & 1u) {
-            st.ms_check_kernel += ph(kPhCheckBegin, kPhCheckEnd);
-            st.check_launches += b->R() > 0;
-            st.check_reads += b->R();
-            st.check_history += b->R() > 0 ? b->check_hist : 0;
-        }
-        if ((b->recorded >> kPhSortEnd) & 1u) {
-            st.ms_sort_kernel += ph(kPhSortBegin, kPhSortEnd);
-            st.sort_launches += 1;
-            st.sort_items += 2 * (int64_t)(b->R() + b->W());
-        }
-        st.gc_runs += b->gc_ran ? 1 : 0;
-        st.sort_big_buckets += b->h_scal->sort_big;
-        if (b->routed && b->slot->rt_timed) {
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, b->slot->ev_rt0, b->slot->ev_rt1) == hipSuccess) st.ms_route_kernels += ms;
-            st.routed_batches += 1;
-            b->slot->rt_timed = false;
-        }
-        if (b->compacted) {
-            st.compactions += 1;
-            // kept base boundaries read, delta boundaries inserted read, result written
-            const int64_t kept = b->h_scal->c_before - b->h_scal->c_rem;
-            const int64_t bytes = 32 * (kept + (b->h_scal->n_next - kept) + b->h_scal->n_next);
-            st.compact_bytes_all += bytes;
-            if ((b->recorded >> kPhCompEnd) & 1u) {
-                st.ms_compact_kernel += ph(kPhCompBegin, kPhCompEnd);
-                st.compact_launches += 1;
-                st.compact_bytes += bytes;
-            }
-        }
+        rebuild_conflicting_reads(b);
+        if ((rc = account_stats(cs, b))) return rc;
         cs->inflight--;
         if (cs->inflight == 0) {
             cs->n_ub = b->h_scal->n;
