@@ -12,7 +12,13 @@ of universe key i sees.  Every endpoint a test sends is a universe key, so the m
 The stored state is the run-length encoding of `ver` (clamped at the floor, as
 tests/export_helpers.canon describes the canonical form).  Range maxima come from a sparse table so
 that reads over a million entries stay cheap; `check_table` compares it with plain slices.
+
+The batch-order half (TxnBatch, resolve, batch_facts, below): multi-range transactions walked in
+batch order over a bool array `dirty[U]` marked by the writes of the transactions that committed
+earlier in the batch, and the facts about the batch's candidate edges that key geometry alone gives.
 """
+from types import SimpleNamespace
+
 import numpy as np
 
 from foundationdb_amd.packing import PackedBatch
@@ -390,3 +396,175 @@ def interleaved_step(seed, model, now, oldest, n=300):
             want.append(CONFLICT if m is None else v)
     model._tab = None
     return model.batch(is_write, aa, bb, snap), np.array(want, np.uint8)
+
+
+# ---- the batch-order model: multi-range transactions walked in batch order over a dirty map of the
+# universe, and the facts about a batch that follow from key geometry alone
+
+
+class TxnBatch:
+    """Multi-range transactions over universe indices, in batch order: per transaction its reads and
+    writes ((a, b) pairs, a <= b; a == b is an empty range), its snapshot and its report flag."""
+
+    def __init__(self):
+        self.reads, self.writes, self.snap, self.report, self.tag = [], [], [], [], []
+
+    def __len__(self):
+        return len(self.snap)
+
+    def add(self, reads=(), writes=(), snap=0, report=False, tag=None):
+        self.reads.append([(int(a), int(b)) for a, b in reads])
+        self.writes.append([(int(a), int(b)) for a, b in writes])
+        self.snap.append(int(snap))
+        self.report.append(bool(report))
+        self.tag.append(tag)
+        return len(self.snap) - 1
+
+    def arrays(self):
+        T = len(self)
+        roff, woff = np.zeros(T + 1, np.int32), np.zeros(T + 1, np.int32)
+        np.cumsum([len(x) for x in self.reads], out=roff[1:])
+        np.cumsum([len(x) for x in self.writes], out=woff[1:])
+        r = np.array([x for tr in self.reads for x in tr], np.int64).reshape(-1, 2)
+        w = np.array([x for tr in self.writes for x in tr], np.int64).reshape(-1, 2)
+        assert (r[:, 0] <= r[:, 1]).all() and (w[:, 0] <= w[:, 1]).all()
+        return SimpleNamespace(T=T, roff=roff, woff=woff, ra=r[:, 0], re=r[:, 1], wa=w[:, 0], we=w[:, 1],
+                               rt=np.repeat(np.arange(T), np.diff(roff)), wt=np.repeat(np.arange(T), np.diff(woff)),
+                               snap=np.array(self.snap, np.int64), report=np.array(self.report, bool))
+
+    def pack(self, model):
+        A = self.arrays()
+        ends = np.concatenate([np.stack([A.ra, A.re], 1).ravel(), np.stack([A.wa, A.we], 1).ravel()])
+        kb, ko = model.pack_keys(ends)
+        return PackedBatch(A.snap, A.report.astype(np.uint8), A.roff, A.woff, kb, ko)
+
+
+def admitted_arrays(A, too_old):
+    """The batch without the ranges of its TooOld transactions, which are never registered (the
+    reference skips them when the transaction is added): what the sorted endpoints, the candidate
+    edges and the counts R and W are made of.  Transactions keep their numbers."""
+    kr, kw = ~too_old[A.rt], ~too_old[A.wt]
+    roff, woff = np.zeros(A.T + 1, np.int32), np.zeros(A.T + 1, np.int32)
+    np.cumsum(np.where(too_old, 0, np.diff(A.roff)), out=roff[1:])
+    np.cumsum(np.where(too_old, 0, np.diff(A.woff)), out=woff[1:])
+    return SimpleNamespace(T=A.T, roff=roff, woff=woff, ra=A.ra[kr], re=A.re[kr], wa=A.wa[kw], we=A.we[kw],
+                           rt=A.rt[kr], wt=A.wt[kw], snap=A.snap, report=A.report)
+
+
+def batch_facts(A, verdicts, dead):
+    """What key geometry alone says about a batch (A: admitted_arrays()), given the verdicts:
+
+    slots[r]      of a non-empty read [ra, re): the writes, empty ones included, that begin strictly
+                  inside it plus the non-empty writes that cover its begin (wa <= ra < we); 0 for an
+                  empty read.  n_slots is their sum.
+    P             the candidate pairs: over every read, the write-begins strictly inside it (non-empty
+                  reads) plus the non-empty writes covering its begin (every read).  P_grouped counts
+                  the covering side once per write group and read-begin instead.
+    cand[r]       the candidate writers of read r, as transactions in write order (None: none): earlier
+                  transactions' non-empty writes that overlap the non-empty read; direct[r] says which
+                  of them begin strictly inside the read (the others cover its begin).
+    dead          history conflict or TooOld: decided before the rounds (a TooOld transaction has no
+                  ranges here, so only a history-conflicted one can be a dead candidate writer).
+    n_live[t]     t's candidate writers that are not dead, over its reads in order; walked[t]: how many
+                  of them abort before the first that commits (all of them if none does); exact[t]: no
+                  read of t has more than one live candidate, so that order is the only one possible.
+    U             transactions that are not dead and have a live candidate.
+    groups        maximal runs of writes, in (begin key, write index) order, that are non-empty and
+                  contain the same non-empty set of read-begins: gorder (the order), gstart[j] (the
+                  position where position j's group starts, -1: in none), giv[j] (the interval of sorted
+                  read-begins position j's write contains)."""
+    T, R, W = A.T, len(A.ra), len(A.wa)
+    ne_r, ne_w = A.ra < A.re, A.wa < A.we
+    wa_s = np.sort(A.wa)
+    inside = np.where(ne_r, np.searchsorted(wa_s, A.re, "left") - np.searchsorted(wa_s, A.ra, "right"), 0)
+    cover = np.searchsorted(np.sort(A.wa[ne_w]), A.ra, "right") - np.searchsorted(np.sort(A.we[ne_w]), A.ra, "right")
+    slots = np.where(ne_r, inside + cover, 0)
+    cand, direct = [None] * R, [None] * R
+    # the non-empty writes by begin key: an overlapping one begins in (ra - longest write, re)
+    by_begin = np.flatnonzero(ne_w)[np.argsort(A.wa[ne_w], kind="stable")]
+    wa_n = A.wa[by_begin]
+    longest = int((A.we - A.wa).max()) if W else 0
+    first = np.searchsorted(wa_n, A.ra - longest, "right")
+    last = np.searchsorted(wa_n, A.re, "left")
+    for r in np.flatnonzero(slots > 0).tolist():
+        x = np.sort(by_begin[first[r]:last[r]])
+        x = x[(A.wt[x] < A.rt[r]) & (A.ra[r] < A.we[x])]
+        if len(x):
+            cand[r], direct[r] = A.wt[x], A.wa[x] > A.ra[r]
+    n_cand, n_live = np.zeros(T, np.int64), np.zeros(T, np.int64)
+    walked, exact = np.zeros(T, np.int64), np.ones(T, bool)
+    for t in np.unique(A.rt[slots > 0]).tolist():
+        live = []
+        for r in range(A.roff[t], A.roff[t + 1]):
+            if cand[r] is None:
+                continue
+            n_cand[t] += len(cand[r])
+            lv = cand[r][~dead[cand[r]]]
+            exact[t] &= len(lv) <= 1
+            live.extend(lv.tolist())
+        n_live[t] = len(live)
+        commits = np.flatnonzero(verdicts[live] == COMMITTED) if live else np.zeros(0, np.int64)
+        walked[t] = commits[0] if len(commits) else len(live)
+        if not dead[t]:  # the model against itself: the dirty map and the candidate writers agree
+            assert (verdicts[t] == CONFLICT) == bool(len(commits)), t
+    # write groups
+    gorder = np.lexsort((np.arange(W), A.wa))
+    rb_s = np.sort(A.ra)
+    lo = np.searchsorted(rb_s, A.wa[gorder], "left")
+    hi = np.where(ne_w[gorder], np.searchsorted(rb_s, A.we[gorder], "left"), lo)
+    member = hi > lo
+    same = np.zeros(W, bool)
+    same[1:] = member[1:] & member[:-1] & (lo[1:] == lo[:-1]) & (hi[1:] == hi[:-1])
+    start = np.where(member & ~same, np.arange(W), -1)
+    gstart = np.where(member, np.maximum.accumulate(start), -1)
+    n_groups = int((member & ~same).sum())
+    P = int(inside.sum() + cover.sum())
+    P_grouped = int(inside.sum() + (hi - lo)[member & ~same].sum())
+    return SimpleNamespace(slots=slots, n_slots=int(slots.sum()), P=P, P_grouped=P_grouped, cand=cand, direct=direct,
+                           dead=dead, n_cand=n_cand, n_live=n_live, walked=walked, exact=exact,
+                           U=int((~dead & (n_live > 0)).sum()), gorder=gorder, gstart=gstart,
+                           giv=np.stack([lo, hi], 1), n_groups=n_groups, rb_sorted=rb_s)
+
+
+def resolve(model, tb, now, oldest, facts=True):
+    """One batch against the model, walked in batch order.  TooOld iff the transaction has reads and
+    snapshot < oldest; a history conflict per read from read_max; an intra-batch conflict iff a
+    non-empty read [a, b) meets dirty[a:b].any(), dirty marked by the non-empty writes of the
+    transactions that committed earlier in the batch (an empty read never conflicts intra-batch, a
+    history-conflicted transaction is not looked at); a committed transaction's writes then stand at
+    `now` in the model.  Returns verdicts, reports (an entry for every reporting, admitted
+    transaction with reads: every history-conflicting read, else the first intra-batch one, else
+    nothing), the arrays, and admitted_arrays with their batch_facts."""
+    A = tb.arrays() if isinstance(tb, TxnBatch) else tb
+    T = A.T
+    has_reads = np.diff(A.roff) > 0
+    too_old = has_reads & (A.snap < oldest)
+    hist_read = model.read_max(A.ra, A.re) > A.snap[A.rt] if len(A.ra) else np.zeros(0, bool)
+    hist = np.zeros(T, bool)
+    hist[A.rt[hist_read]] = True
+    hist &= ~too_old
+    dead = too_old | hist
+    verdicts = np.full(T, COMMITTED, np.uint8)
+    verdicts[too_old], verdicts[hist] = TOO_OLD, CONFLICT
+    dirty = np.zeros(model.U, bool)
+    first_intra = {}
+    ra, re, wa, we, roff, woff = (x.tolist() for x in (A.ra, A.re, A.wa, A.we, A.roff, A.woff))
+    for t in np.flatnonzero(~dead).tolist():
+        for r in range(roff[t], roff[t + 1]):
+            if ra[r] < re[r] and dirty[ra[r]:re[r]].any():
+                verdicts[t], first_intra[t] = CONFLICT, r - roff[t]
+                break
+        else:
+            for w in range(woff[t], woff[t + 1]):
+                dirty[wa[w]:we[w]] = True
+    cw = (verdicts[A.wt] == COMMITTED) & (A.wa < A.we)
+    model.write(A.wa[cw], A.we[cw], now)
+    reports = {}
+    for t in np.flatnonzero(A.report & has_reads & ~too_old).tolist():
+        if hist[t]:
+            reports[t] = [r - roff[t] for r in range(roff[t], roff[t + 1]) if hist_read[r]]
+        else:
+            reports[t] = [first_intra[t]] if t in first_intra else []
+    adm = admitted_arrays(A, too_old)
+    return SimpleNamespace(verdicts=verdicts, reports=reports, arrays=A, admitted=adm, first_intra=first_intra,
+                           facts=batch_facts(adm, verdicts, dead) if facts else None)

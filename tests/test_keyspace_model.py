@@ -98,3 +98,91 @@ def test_plan_sizes_reach_the_upper_levels():
     _, steps = K.build_plan(1, "prefix20", 10 ** 14 + 7, **BIG)
     assert all(steps[i]["reached"][2] >= 20 and steps[i]["reached"][3] >= 20 for i in (0, 6))
     assert all(pb.n_txn <= 49152 for s in steps for pb, _, _, _ in s["batches"])
+
+
+# ---- the batch-order model (K.resolve) against the semantic oracle
+
+
+def random_txn_batch(rng, U, n, now, oldest, old_snap):
+    """Multi-range transactions over a universe of U keys: touching and nested ranges abound on so
+    few keys; empty ranges, transactions that read their own write, snapshots below `oldest`
+    (TooOld) and at `old_snap` (below an earlier batch's writes: history conflicts)."""
+    tb = K.TxnBatch()
+
+    def rng_range():
+        a = int(rng.integers(0, U))
+        if rng.random() < 0.15:
+            return a, a
+        return a, min(U - 1, a + int(rng.integers(1, 4))) if a < U - 1 else a
+
+    for _ in range(n):
+        reads = [rng_range() for _ in range(int(rng.integers(0, 4)))]
+        writes = [rng_range() for _ in range(int(rng.integers(0, 3)))]
+        if reads and rng.random() < 0.2:
+            writes.append(reads[0])  # reads its own write
+        x = rng.random()
+        snap = oldest - 1 - int(rng.integers(0, 3)) if x < 0.07 else (old_snap if x < 0.3 else now - 1)
+        tb.add(reads, writes, snap, rng.random() < 0.6)
+    return tb
+
+
+def check_against_oracle(o, model, tb, now, oldest, header, what):
+    pb = tb.pack(model)
+    res = K.resolve(model, tb, now, oldest)
+    got, conf = o.detect(pb, now, oldest)
+    assert (got == res.verdicts).all(), (what, np.flatnonzero(got != res.verdicts)[:10])
+    assert {t: sorted(x) for t, x in conf.items()} == res.reports, what
+    keys, vers = o.dump_history()
+    assert _rle_lists(model.rle(), model.klen) == canon(keys, vers, header, NO_FLOOR), what
+    return res
+
+
+@pytest.mark.parametrize("shape", K.SHAPES)
+def test_resolve_matches_semantic_oracle_on_random_batches(oracle_built, shape):
+    """A few hundred random multi-range batches over small universes: verdicts, reports (an entry for
+    every reporting admitted transaction with reads) and the state after each batch."""
+    rng = np.random.default_rng(11)
+    seen = {K.CONFLICT: 0, K.TOO_OLD: 0, K.COMMITTED: 0}
+    hist_conflicts = intra = own = 0
+    for trial in range(60):
+        U = int(rng.integers(6, 40))
+        model = K.KeyspaceModel(K.make_universe(rng, U, shape), 600)
+        hist = np.array([1, U // 2])
+        model.load(hist, [700, 800])
+        o = oracle_built.OracleConflictSet()
+        o.load_history(*model.pack_keys(hist), np.array([700, 800]), 600)
+        o.set_oldest_version(1000)
+        now = 2000
+        for i in range(5):
+            tb = random_txn_batch(rng, U, int(rng.integers(3, 60)), now, 1000, 1500)
+            res = check_against_oracle(o, model, tb, now, 1000, 600, (shape, trial, i))
+            for v in seen:
+                seen[v] += int((res.verdicts == v).sum())
+            f = res.facts
+            hist_conflicts += int((f.dead & (res.verdicts == K.CONFLICT)).sum())
+            intra += len(res.first_intra)
+            own += sum(1 for t in range(len(tb)) if res.verdicts[t] == K.COMMITTED
+                       and any(a < b and (a, b) in tb.writes[t] for a, b in tb.reads[t]))
+            now += 10
+    assert min(seen.values()) > 300 and min(hist_conflicts, intra) > 300 and own > 50, (seen, hist_conflicts, intra, own)
+
+
+@pytest.mark.parametrize("kind,shape", [("core", "random16"), ("fill", "prefix20"), ("sizes", "random16")])
+def test_directed_resolution_plan_matches_semantic_oracle(oracle_built, kind, shape):
+    """Every directed batch of tests/resolution_plan.py, at full size (the oracle takes them in
+    milliseconds): building the plan asserts its coverage from the model's facts; then verdicts,
+    reports and the state after every batch against the semantic oracle."""
+    from tests import resolution_plan as RP
+
+    p = RP.build(kind, 1, shape)
+    assert set(p.coverage) == {"core": {"ladders", "groups", "prepass"}, "fill": {"fill"}, "sizes": {"sizes"}}[kind]
+    o = oracle_built.OracleConflictSet()
+    o.load_history(*p.loaded)
+    o.set_oldest_version(RP.OLDEST)
+    for s in p.steps:
+        got, conf = o.detect(s.pb, s.now, s.oldest)
+        assert s.pb.n_txn == s.T <= 49152
+        assert (got == s.want).all(), (s.name, np.flatnonzero(got != s.want)[:10])
+        assert {t: sorted(x) for t, x in conf.items()} == s.reports, s.name
+        keys, vers = o.dump_history()
+        assert _rle_lists(s.state, p.model.klen) == canon(keys, vers, RP.HEADER, NO_FLOOR), s.name
