@@ -13,6 +13,10 @@ The stored state is the run-length encoding of `ver` (clamped at the floor, as
 tests/export_helpers.canon describes the canonical form).  Range maxima come from a sparse table so
 that reads over a million entries stay cheap; `check_table` compares it with plain slices.
 
+The universe is a uint8[U, klen] matrix of keys of one length or, for keys of different lengths, a
+(key_bytes, key_offsets) pair sorted by memcmp and then by length (var_universe; Python's order of
+bytes); everything below works on universe indices and packs keys through pack_keys in either form.
+
 The batch-order half (TxnBatch, resolve, batch_facts, below): multi-range transactions walked in
 batch order over a bool array `dirty[U]` marked by the writes of the transactions that committed
 earlier in the batch, and the facts about the batch's candidate edges that key geometry alone gives.
@@ -44,10 +48,34 @@ def make_universe(rng, n, shape):
     return np.ascontiguousarray(keys)
 
 
+def var_universe(keys):
+    """(key_bytes, key_offsets) of distinct keys of any lengths, sorted by memcmp and then by length
+    (the reference's order of byte strings, which is Python's order of bytes): the variable-length form
+    of a universe, which KeyspaceModel takes in place of a uint8[U, klen] matrix."""
+    keys = sorted(set(keys))
+    ko = np.zeros(len(keys) + 1, np.int64)
+    np.cumsum([len(k) for k in keys], out=ko[1:])
+    return np.frombuffer(b"".join(keys), np.uint8).copy(), ko
+
+
+def split_keys(kb, ko):
+    """The keys of a (key_bytes, key_offsets) pair as a list of bytes."""
+    raw, ko = np.asarray(kb, np.uint8).tobytes(), np.asarray(ko).tolist()
+    return [raw[a:b] for a, b in zip(ko, ko[1:])]
+
+
 class KeyspaceModel:
     def __init__(self, keys, header):
-        self.keys = keys
-        self.U, self.klen = keys.shape
+        """keys: uint8[U, klen], or (key_bytes, key_offsets) for keys of different lengths (klen is
+        None then).  Sorted and distinct either way."""
+        if isinstance(keys, tuple):
+            self.kb, self.ko = np.asarray(keys[0], np.uint8), np.asarray(keys[1], np.int64)
+            self.keys, self.U, self.klen = None, len(self.ko) - 1, None
+            ks = split_keys(self.kb, self.ko)
+            assert all(x < y for x, y in zip(ks, ks[1:]))
+        else:
+            self.keys = keys
+            self.U, self.klen = keys.shape
         self.header = int(header)
         self.ver = np.full(self.U, header, np.int64)
         self._tab = None
@@ -109,10 +137,15 @@ class KeyspaceModel:
     def rle(self):
         """(header, key_bytes, key_offsets, versions): the canonical stored state."""
         s = self.boundaries()
-        return self.header, self.keys[s].ravel(), np.arange(len(s) + 1, dtype=np.int64) * self.klen, self.ver[s]
+        return (self.header, *self.pack_keys(s), self.ver[s])
 
     def pack_keys(self, idx):
         idx = np.asarray(idx, np.int64)
+        if self.klen is None:
+            ln = self.ko[idx + 1] - self.ko[idx]
+            off = np.zeros(len(idx) + 1, np.int64)
+            np.cumsum(ln, out=off[1:])
+            return self.kb[np.repeat(self.ko[idx] - off[:-1], ln) + np.arange(off[-1])], off
         return self.keys[idx].ravel(), np.arange(len(idx) + 1, dtype=np.int64) * self.klen
 
     def batch(self, is_write, a, b, snap):
@@ -139,9 +172,13 @@ def assert_dump_equals(dump, want, what=None):
         return
     n = min(len(vv), len(wvv))
     bad = vv[:n] != wvv[:n]
-    if n and np.array_equal(ko[: n + 1], wko[: n + 1]):
-        klen = int(wko[1])
-        bad |= (kb[: n * klen].reshape(n, klen) != wkb[: n * klen].reshape(n, klen)).any(axis=1)
+    if n:  # keys of either form: a boundary is wrong if its length is, or a byte of it
+        ko, wko = np.asarray(ko, np.int64), np.asarray(wko, np.int64)
+        bad |= np.diff(ko[: n + 1]) != np.diff(wko[: n + 1])
+        same = np.array_equal(ko[: n + 1], wko[: n + 1])
+        m = int(wko[n]) if same else 0  # (after a wrong length the bytes no longer line up)
+        if m:
+            bad |= np.add.reduceat((kb[:m] != wkb[:m]).astype(np.int64), wko[:n].clip(max=m - 1)) * (np.diff(wko[: n + 1]) > 0) > 0
     d = int(np.argmax(bad)) if bad.any() else n
     raise AssertionError((what, "first difference at boundary", d, "of", len(vv), len(wvv),
                           vv[d:d + 3].tolist(), wvv[d:d + 3].tolist()))

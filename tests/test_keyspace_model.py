@@ -11,6 +11,8 @@ from tests.export_helpers import NO_FLOOR, canon
 
 def _rle_lists(state, klen):
     hdr, kb, ko, vv = state
+    if klen is None:  # keys of different lengths: by the offsets
+        return hdr, K.split_keys(kb, ko), vv.tolist()
     raw = kb.tobytes()
     return hdr, [raw[i * klen:(i + 1) * klen] for i in range(len(vv))], vv.tolist()
 
@@ -186,3 +188,143 @@ def test_directed_resolution_plan_matches_semantic_oracle(oracle_built, kind, sh
         assert {t: sorted(x) for t, x in conf.items()} == s.reports, s.name
         keys, vers = o.dump_history()
         assert _rle_lists(s.state, p.model.klen) == canon(keys, vers, RP.HEADER, NO_FLOOR), s.name
+
+
+# ---- keys of different lengths, and the search plan (tests/search_plan.py)
+
+
+def random_var_universe(rng, U):
+    """U keys over two byte values, 0 to 40 bytes long: proper prefixes, \\0 extensions and keys that
+    differ only past 16 and past 24 bytes abound."""
+    keys = {b""}
+    stems = [bytes(rng.integers(0, 2, size=int(n)).astype(np.uint8) * 255) for n in (15, 16, 23, 24, 31)]
+    while len(keys) < U:
+        s = stems[int(rng.integers(0, len(stems)))] if rng.random() < 0.7 else b""
+        keys.add(s + bytes(rng.integers(0, 2, size=int(rng.integers(0, 9))).astype(np.uint8) * 255))
+    return K.var_universe(keys)
+
+
+def test_variable_length_resolve_matches_semantic_oracle(oracle_built):
+    """A few hundred random multi-range batches over small universes of keys of different lengths:
+    verdicts, reports and the state after each batch (pack_keys, rle, TxnBatch.pack on offsets)."""
+    rng = np.random.default_rng(12)
+    seen = {K.CONFLICT: 0, K.TOO_OLD: 0, K.COMMITTED: 0}
+    for trial in range(60):
+        U = int(rng.integers(6, 40))
+        model = K.KeyspaceModel(random_var_universe(rng, U), 600)
+        assert model.klen is None and model.U == U
+        hist = np.array([1, U // 2])
+        model.load(hist, [700, 800])
+        o = oracle_built.OracleConflictSet()
+        o.load_history(*model.pack_keys(hist), np.array([700, 800]), 600)
+        o.set_oldest_version(1000)
+        now = 2000
+        for i in range(5):
+            tb = random_txn_batch(rng, U, int(rng.integers(3, 60)), now, 1000, 1500)
+            res = check_against_oracle(o, model, tb, now, 1000, 600, ("var", trial, i))
+            for v in seen:
+                seen[v] += int((res.verdicts == v).sum())
+            now += 10
+    assert min(seen.values()) > 300, seen
+
+
+def test_variable_length_dump_comparison():
+    """assert_dump_equals on keys of different lengths: equal states pass; a wrong version, a wrong
+    byte and a wrong length are each found at their boundary."""
+    model = K.KeyspaceModel(K.var_universe([b"", b"a", b"a\0", b"ab" * 20, b"b"]), 5)
+    model.load(np.array([0, 2, 3]), [7, 8, 9])
+    hdr, kb, ko, vv = model.rle()
+    assert K.split_keys(kb, ko) == [b"", b"a\0", b"ab" * 20]
+    K.assert_dump_equals((kb, ko, vv, hdr), model.rle())
+    for at, dump in ((1, (kb, ko, np.array([7, 6, 9]), hdr)),
+                     (2, (np.concatenate([kb[:-1], [0]]).astype(np.uint8), ko, vv, hdr)),
+                     (1, (kb, ko + np.array([0, 0, 1, 1]), vv, hdr))):
+        with pytest.raises(AssertionError) as e:
+            K.assert_dump_equals(dump, model.rle())
+        assert e.value.args[0][2] == at, e.value.args
+
+
+@pytest.fixture(scope="module")
+def search_plans():
+    from tests import search_plan as SP
+
+    return [SP.build(0), SP.build(1)]
+
+
+def run_on_oracle(oracle_built, p):
+    from tests import search_plan as SP
+
+    o = oracle_built.OracleConflictSet()
+    o.load_history(*p.loaded)
+    o.set_oldest_version(SP.OLDEST)
+    for s in p.steps:
+        for pb, now, new_oldest, want in s.batches:
+            got, _ = o.detect(pb, now, new_oldest)
+            assert pb.n_txn <= 49152 and not (want == K.TOO_OLD).any()
+            assert (got == want).all(), (s.name, np.flatnonzero(got != want)[:10])
+        if s.state is not None:
+            keys, vers = o.dump_history()
+            assert _rle_lists(s.state, None) == canon(keys, vers, p.header, o.oldest_version), s.name
+            if s.as_stored:
+                assert _rle_lists(s.state, None) == canon(keys, vers, p.header, NO_FLOOR), s.name
+
+
+@pytest.mark.parametrize("polarity", [0, 1])
+def test_search_plan_matches_semantic_oracle(oracle_built, search_plans, polarity):
+    """Every batch of the core search plan against the semantic oracle: verdicts, and the state after
+    every write batch, the compaction and the GC."""
+    run_on_oracle(oracle_built, search_plans[polarity])
+
+
+@pytest.mark.parametrize("kind", ["short", "long", "wide", "path-d"])
+def test_search_riders_match_semantic_oracle(oracle_built, search_plans, kind):
+    """The riders and the previous-batch-segment batches against the semantic oracle; the riders'
+    common reads have the core plan's verdicts (their keys and versions are the same)."""
+    from tests import search_plan as SP
+
+    p = SP.build_path_d(0) if kind == "path-d" else SP.build(0, kind)
+    run_on_oracle(oracle_built, p)
+    if kind == "path-d":
+        assert sorted(p.coverage["path_d"]) == sorted(set(SP.PATH_D_SIZES[:-1]) | {max(p.coverage["path_d"])})
+        assert max(p.coverage["path_d"]) > 4000
+    else:
+        core = search_plans[0]
+        assert [s.name for s in p.steps] == [s.name for s in core.steps]
+        longest = max(int(np.diff(pb.key_offsets).max()) for s in p.steps for pb, _, _, _ in s.batches)
+        assert (longest > 24) == (kind == "long")
+
+
+def test_search_plan_conditions(search_plans):
+    """The plan's own conditions, from the model alone: no read is sent once (K.twice's single share is
+    asserted 0 as each batch is built); over both polarities every directed key has a read that flips
+    one of its two verdicts under each of the four one-segment errors, in the loaded base alone and
+    over the written history; every tail-edge class over 16 bytes is queried at all eight tail
+    residues in every read batch; the run starts stand at ranks 0, 1, 7 mod 8 and 0, 1, 63 mod 64 in
+    the base and, by the predicted delta, in the delta; the crowded directory family and the sparse
+    one; per-family counts of reads decided by one structure alone."""
+    from tests import search_plan as SP
+
+    counts = SP.check_sensitivity(search_plans)
+    assert counts["base"] >= 400 and counts["delta"] == len(search_plans[0].directed) >= 500
+    for p in search_plans:
+        assert p.H > 32768 and all(v >= SP.OLDEST + 1 for v in (p.loaded[2].min(), p.header))
+        assert all(p.align[L] == set(range(8)) for L in SP.TAIL_LENGTHS if L > 16)
+        assert p.coverage["run_starts_base"] == [(0, 0), (1, 1), (7, 63)]
+        d = p.coverage["run_starts_delta"]
+        assert {0, 1, 7} <= {a for a, _ in d} and {0, 1, 63} <= {b for _, b in d}
+        assert p.coverage["directory"]["crowded"] > 4096 and p.coverage["directory"]["sparse"] <= 8
+        for fam, (n, base, delta, prev) in p.coverage["decided"].items():
+            assert n >= 500 and min(base, delta, prev) >= 40, (fam, n, base, delta, prev)
+        lens = {len(k) for k in p.directed}
+        assert {0, 15, 16, 17, 23, 24, 25, 30, 63, 64, 65, 111, 112, 113, 120, 121, 122, 200, 201} <= lens
+        writes = [s for s in p.steps if s.kind == "write"]
+        assert [s.delta_before for s in writes][0] == 0 and writes[-1].delta_before < p.coverage["delta_size"]
+
+
+def test_search_universe_is_sorted_in_the_reference_order(oracle_built, search_plans):
+    """Python's order of bytes is the reference's order of keys (memcmp, then length): every
+    neighbouring pair of the plan's universe through the oracle's point comparison."""
+    u = search_plans[0].ukeys
+    assert u[0] == b"" and len(set(u)) == len(u)
+    for a, b in zip(u, u[1:]):
+        assert oracle_built.point_compare(a, True, False, b, True, False) < 0, (a, b)
