@@ -182,6 +182,53 @@ class TransientStorageMetricSample(StorageMetricSample):
                 self.erase(key)
 
 
+_M64 = (1 << 64) - 1
+
+
+def iops_mix(seed, index) -> np.ndarray:
+    """splitmix64's finalizer over seed + 0x9E3779B97F4A7C15 (index + 1), as uint64: the counter-based
+    generator the device sample rolls with (include/fdb_conflict_set.h, fdbcs_batch_set_iops_sample)."""
+    i = np.asarray(index, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        z = np.uint64(int(seed) & _M64) + np.uint64(0x9E3779B97F4A7C15) * (i + np.uint64(1))
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return z ^ (z >> np.uint64(31))
+
+
+def iops_roll(seed, index, metric, units: int) -> Tuple[np.ndarray, np.ndarray]:
+    """TransientStorageMetricSample::add's decision for entry `index` of a resolver's batch under
+    `seed`, all in integers so that host and device agree bit for bit: (sampled, the value addMetric
+    is given).  A metric at or above `units` always counts, as itself; a smaller one with odds
+    metric / units (u * units < metric << 32, u the top 32 bits of iops_mix), as `units`."""
+    if not 1 <= int(units) <= (1 << 31) - 1:
+        raise ValueError("units must be in [1, 2^31 - 1]")
+    m = np.asarray(metric, dtype=np.uint64)
+    u = iops_mix(seed, index) >> np.uint64(32)
+    big = m >= np.uint64(units)
+    hit = big | (u * np.uint64(units) < (m << np.uint64(32)))
+    return hit, np.where(big, m, np.uint64(units)).astype(np.int64)
+
+
+def iops_sample_of(pb: PackedBatch, units: int, seed: int) -> Tuple[List[bytes], np.ndarray, np.ndarray]:
+    """The iops sample of a resolver's (sub-)batch under the counter-based roll: (keys, metrics,
+    index) of the sampled range begins, entry i being read i for i < R and write i - R after, the
+    order the device sample (ConflictBatch.iops_sample) uses.  The host path's sampler."""
+    n = pb.n_reads + pb.n_writes
+    idx = np.arange(n, dtype=np.int64)
+    offs = pb.key_offsets
+    metric = SAMPLE_OFFSET_PER_KEY + (offs[2 * idx + 1] - offs[2 * idx])
+    hit, val = iops_roll(seed, idx, metric, units)
+    kept = np.nonzero(hit)[0]
+    return [pb.key(2 * int(i)) for i in kept], val[kept].astype(np.int32), kept.astype(np.int32)
+
+
+def seed_of(seed: int, g: int) -> int:
+    """The seed resolver g rolls a batch under when the batch's seed is `seed` (host and device
+    paths alike): resolvers draw from unrelated streams."""
+    return int(iops_mix(seed, g))
+
+
 class ResolverLoad:
     """The resolver side of balancing (Resolver.actor.cpp:58, 178-192, 318-342): the iops sample
     fed by every batch when there is more than one resolver, metrics and split replies."""
@@ -193,9 +240,26 @@ class ResolverLoad:
         self.metrics_requests = 0
         self.split_requests = 0
 
-    def add_batch(self, pb: PackedBatch, now: float) -> None:
+    def add_sampled(self, keys: Sequence[bytes], metrics, now: float) -> None:
+        """Entries already rolled (iops_sample_of, or the device's ConflictBatch.iops_sample): summed
+        into the sample, expiring at now + 1 s.  Every entry of a batch carries the same expiry and
+        addMetric only sums, so their order does not matter."""
+        if self.resolver_count <= 1:
+            return
+        expire = now + SAMPLE_EXPIRATION_TIME
+        for k, m in zip(keys, metrics):
+            m = int(m)
+            if self.sample.add_metric(k, m) == 0:
+                self.sample.erase(k)
+            self.sample.queue.append((expire, k, -m))
+
+    def add_batch(self, pb: PackedBatch, now: float, seed: Optional[int] = None) -> None:
         """:178-192: write then read range begins of every transaction, expiring at now + 1 s.
-        Vectorized roll: a begin key of metric m < 20000 is sampled with probability m/20000."""
+        Vectorized roll: a begin key of metric m < 20000 is sampled with probability m/20000.
+        With a seed the roll is the counter-based one (iops_sample_of) instead of `rng`'s."""
+        if seed is not None:
+            self.add_sampled(*iops_sample_of(pb, self.sample.metric_units_per_sample, seed)[:2], now)
+            return
         if self.resolver_count <= 1 or pb.n_txn == 0:
             return
         expire = now + SAMPLE_EXPIRATION_TIME
@@ -373,17 +437,40 @@ class BalancedRouting:
         self.pending: List[Move] = []
         self.history: List[Tuple[int, List[Move]]] = []
 
-    def route(self, pb: PackedBatch, version: int):
-        """Route the batch at commit version `version` (moves decided earlier apply first)."""
+    def begin_batch(self, version: int):
+        """Apply the moves decided earlier at commit version `version`; returns the KeyResolvers the
+        batch of that version is routed under (by route() here, or on the devices with
+        ConflictBatch.add_routed_map)."""
         if self.pending:
             self.kr.apply_changes(self.pending, version)
             self.history.append((version, self.pending))
             self.pending = []
-        parts = self.kr.route(pb)
+        return self.kr
+
+    def end_batch(self, version: int, samples) -> None:
+        """The rest of the step for a batch routed elsewhere: samples[g] = (keys, metrics) of
+        resolver g's iops sample of the batch (ConflictBatch.iops_sample()[:2]); poll, add, balance
+        and coalesce exactly as route() does after its split."""
         now = version / VERSIONS_PER_SECOND
         for g in range(self.G):
             self.loads[g].poll(now)
-            self.loads[g].add_batch(parts[g].batch, now)
+            self.loads[g].add_sampled(samples[g][0], samples[g][1], now)
+        self._balance(version, now)
+
+    def route(self, pb: PackedBatch, version: int, seed: Optional[int] = None):
+        """Route the batch at commit version `version` (moves decided earlier apply first).  With a
+        seed (one per batch, e.g. its version) resolver g's sample is rolled by the counter-based
+        roll under seed_of(seed, g), which a device-routed batch reproduces (begin_batch /
+        end_batch); without one by each resolver's own generator."""
+        parts = self.begin_batch(version).route(pb)
+        now = version / VERSIONS_PER_SECOND
+        for g in range(self.G):
+            self.loads[g].poll(now)
+            self.loads[g].add_batch(parts[g].batch, now, None if seed is None else seed_of(seed, g))
+        self._balance(version, now)
+        return parts
+
+    def _balance(self, version: int, now: float) -> None:
         if self.next_balance is None:
             self.next_balance = now + self.balance_time
             self.next_coalesce = now + 1.0
@@ -394,4 +481,3 @@ class BalancedRouting:
         if now >= self.next_coalesce:
             self.next_coalesce = now + 1.0
             self.kr.coalesce(version)
-        return parts

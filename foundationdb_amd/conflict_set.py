@@ -20,6 +20,7 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
+from .balancing import KEY_BYTES_PER_SAMPLE
 from .packing import CommitTransaction, InvertedRange, PackedBatch, _CPackedBatch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -178,6 +179,10 @@ SIGNATURES = {
                                                   _I32, _I32, _I32, _I64, _VP, _I64, _VP, ctypes.c_uint32]),
     "fdbcs_batch_set_report_output": (ctypes.c_int, [_VP, _VP, _I64]),
     "fdbcs_batch_report_entries": (ctypes.c_int, [_VP, _VP, _I32]),
+    "fdbcs_batch_set_iops_sample": (ctypes.c_int, [_VP, _I32, ctypes.c_uint64]),
+    "fdbcs_batch_iops_sample": (ctypes.c_int, [_VP, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+    "fdbcs_batch_iops_sample_read": (ctypes.c_int, [_VP, _VP, _I64, _VP, _VP, _VP, _I64]),
+    "fdbcs_batch_iops_sample_timing": (ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_double)]),
     "fdbcs_debug_kernel_time": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
     "fdbcs_kernel_profile": (ctypes.c_int, [_VP, _I32, ctypes.c_char_p, _I32, ctypes.POINTER(_I64),
                                             ctypes.POINTER(ctypes.c_double)]),
@@ -677,6 +682,41 @@ class ConflictBatch:
         combine_report_bytes / an all-reduce MAX."""
         _check(load_library().fdbcs_batch_set_report_output(self._h, _VP(dev_out or None), int(n_global_reads)),
                "setReportOutput")
+
+    def set_iops_sample(self, units: int = KEY_BYTES_PER_SAMPLE, seed: int = 0) -> None:
+        """fdbcs_batch_set_iops_sample: on a routed batch, before detect, take the resolver's iops
+        sample (Resolver.actor.cpp:178-192) of the batch on the device, with `units` metric units
+        per sample under the counter-based roll balancing.iops_roll restates, seeded with `seed`
+        (64 bits).  iops_sample() fetches it."""
+        _check(load_library().fdbcs_batch_set_iops_sample(self._h, int(units), int(seed) & 0xFFFFFFFFFFFFFFFF),
+               "setIopsSample")
+
+    def iops_sample_raw(self):
+        """fdbcs_batch_iops_sample + _read: (key_bytes uint8[], key_offsets int64[n + 1], metrics
+        int32[n], index int32[n]) of the sampled range begins, in range order.  Waits for the
+        routing and the sample only, not for detect; may be called again until the batch is closed."""
+        L = load_library()
+        n, nb = _I64(), _I64()
+        _check(L.fdbcs_batch_iops_sample(self._h, ctypes.byref(n), ctypes.byref(nb)), "iopsSample")
+        kb = np.empty(nb.value, np.uint8)
+        ko = np.empty(n.value + 1, np.int64)
+        met = np.empty(n.value, np.int32)
+        idx = np.empty(n.value, np.int32)
+        _check(L.fdbcs_batch_iops_sample_read(self._h, _p(kb), nb.value, _p(ko), _p(met), _p(idx), n.value),
+               "iopsSampleRead")
+        return kb, ko, met, idx
+
+    def iops_sample(self) -> Tuple[List[bytes], np.ndarray, np.ndarray]:
+        """(keys, metrics, index) of the sampled range begins: what ResolverLoad.add_sampled takes."""
+        kb, ko, met, idx = self.iops_sample_raw()
+        raw = kb.tobytes()
+        return [raw[ko[i]:ko[i + 1]] for i in range(len(met))], met, idx
+
+    def iops_sample_timing(self) -> float:
+        """Milliseconds of the sample's kernels on the device (after iops_sample())."""
+        ms = ctypes.c_double()
+        _check(load_library().fdbcs_batch_iops_sample_timing(self._h, ctypes.byref(ms)), "iopsSampleTiming")
+        return ms.value
 
     def report_entries(self) -> np.ndarray:
         """fdbcs_batch_report_entries: uint8 per transaction, 1 where the reference would have

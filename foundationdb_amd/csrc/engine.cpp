@@ -450,6 +450,13 @@ struct BatchSlot {
     HBuf rt_res;
     hipEvent_t ev_rt0 = nullptr, ev_rt1 = nullptr;  // around the routing kernels
     bool rt_timed = false;
+    // fdbcs_batch_set_iops_sample: scan state, result arrays, host-mapped totals and the events
+    // around the kernel, all allocated by the slot's first sampled batch.  is_inflight: a sample
+    // was enqueued and nobody has waited for ev_is1 since (it reads the slot's device copy)
+    DBuf is_state, is_met, is_idx, is_off, is_bytes;
+    HBuf is_tot;
+    hipEvent_t ev_is0 = nullptr, ev_is1 = nullptr;
+    bool is_inflight = false;
     // per-kernel events of the batch (timing level 3, or the timed kernel at level 1)
     std::vector<hipEvent_t> prof_pool;
     size_t prof_next = 0;
@@ -504,6 +511,11 @@ struct fdbcs_batch {
     int32_t rT = 0, rR = 0, rW = 0;
     size_t r_tail = 0;
     int64_t r_global_R = 0;  // reads of all shares
+    int64_t r_cap_ranges = 0, r_cap_tail = 0;  // read + write and tail capacities it was routed with
+    // fdbcs_batch_set_iops_sample: requested; its totals read (fdbcs_batch_iops_sample)
+    bool is_req = false, is_done = false;
+    int64_t is_n = 0, is_nbytes = 0;
+    double is_ms = 0;
     // fdbcs_batch_set_report_output: device bytes per global read, written at detect
     uint8_t* rep_dev = nullptr;
     int64_t rep_n = 0;
@@ -994,6 +1006,14 @@ void release_slot(BatchSlot* sl) {
     if (sl->ev_up) (void)hipEventDestroy(sl->ev_up);
     if (sl->ev_rt0) (void)hipEventDestroy(sl->ev_rt0);
     if (sl->ev_rt1) (void)hipEventDestroy(sl->ev_rt1);
+    if (sl->ev_is0) (void)hipEventDestroy(sl->ev_is0);
+    if (sl->ev_is1) (void)hipEventDestroy(sl->ev_is1);
+    sl->is_state.release();
+    sl->is_met.release();
+    sl->is_idx.release();
+    sl->is_off.release();
+    sl->is_bytes.release();
+    sl->is_tot.release();
     sl->rt_scan.release();
     sl->rt_inv.release();
     sl->rt_rids.release();
@@ -2205,6 +2225,13 @@ void fdbcs_batch_destroy(fdbcs_batch* b) {
         (void)hipStreamSynchronize(b->cs->ustream);
         (void)hipStreamSynchronize(b->cs->astream);
     }
+    // a sample runs behind the routing, off the detect pipeline: the slot's device copy and the
+    // sample's own buffers are the next batch's only once it is over
+    if (b->slot && b->slot->is_inflight) {
+        (void)hipSetDevice(b->cs->device);
+        (void)hipEventSynchronize(b->slot->ev_is1);
+        b->slot->is_inflight = false;
+    }
     // done (waited or synchronized): dependencies on it need no wait any more
     for (int k = 0; k < kNumWork; k++) {
         if (b->cs->ws_user[k] == b) b->cs->ws_user[k] = nullptr;
@@ -2886,6 +2913,9 @@ static int add_routed_impl(fdbcs_batch* b, const void* shares, int64_t stride, i
     b->routed = true;
     b->route_pending = true;
     b->rT = b->rR = b->rW = 0;
+    b->r_cap_ranges = (int64_t)cap_reads + cap_writes;
+    b->r_cap_tail = cap_tail;
+    b->is_req = b->is_done = false;
     b->out_dev = conflict_out;
     b->out_n = n_global;
     b->out_ids.clear();
@@ -2932,6 +2962,7 @@ static int finish_route(fdbcs_batch* b) {
         b->out_n = 0;
         b->rep_dev = nullptr;
         b->rep_n = 0;
+        b->is_req = b->is_done = false;  // (its kernel found the error too and wrote an empty sample)
         b->state = 0;
         return r.error == 2 ? FDBCS_E_TIMEOUT
                             : r.error == 1 ? FDBCS_E_NOMEM : r.error == 3 ? FDBCS_E_INVALID : FDBCS_E_DEVICE;
@@ -3856,6 +3887,111 @@ int fdbcs_batch_set_report_output(fdbcs_batch* b, uint8_t* dev_out, int64_t n_gl
     // the size is compared with the shares' reads at detect, once the routing kernels have run
     b->rep_dev = dev_out;
     b->rep_n = n_global_reads;
+    return FDBCS_OK;
+}
+
+// ---- the resolver's iops sample of a routed batch (Resolver.actor.cpp:178-192)
+
+int fdbcs_batch_set_iops_sample(fdbcs_batch* b, int32_t units, uint64_t seed) {
+    if (!b || units < 1) return FDBCS_E_INVALID;
+    if (!b->cs || !b->routed || b->state >= 2) return FDBCS_E_STATE;
+    // the scan counts key bytes in 32 bits: every begin key's 16 prefix bytes and the whole tail arena bound them
+    const int64_t cap = b->r_cap_ranges, bytes_cap = 16 * cap + b->r_cap_tail;
+    if (bytes_cap >= ((int64_t)1 << 32)) return FDBCS_E_NOMEM;
+    fdbcs_conflict_set* cs = b->cs;
+    HIPOK(hipSetDevice(cs->device));
+    BatchSlot* sl = b->slot;
+    if (sl->is_inflight) {  // a request replaced: its kernel is over before its buffers are touched
+        HIPOK(hipEventSynchronize(sl->ev_is1));
+        sl->is_inflight = false;
+    }
+    b->is_req = b->is_done = false;
+    int rc;
+    const size_t state_bytes = 8 * (size_t)iops_scan_words(cap);
+    if ((rc = sl->is_state.ensure(state_bytes))) return rc;
+    if ((rc = sl->is_met.ensure(4 * (size_t)(cap + 1)))) return rc;
+    if ((rc = sl->is_idx.ensure(4 * (size_t)(cap + 1)))) return rc;
+    if ((rc = sl->is_off.ensure(8 * (size_t)(cap + 1)))) return rc;
+    if ((rc = sl->is_bytes.ensure((size_t)bytes_cap + 64))) return rc;
+    if ((rc = sl->is_tot.ensure(sizeof(IopsTotals), true))) return rc;
+    if (!sl->ev_is0) HIPOK(hipEventCreate(&sl->ev_is0));
+    if (!sl->ev_is1) HIPOK(hipEventCreate(&sl->ev_is1));
+    IopsArgs a{};
+    a.keys = b->bd.keys;
+    a.tail = b->bd.tail;
+    a.dres = (const RouteResult*)sl->rt_dres.p;
+    a.units = (uint32_t)units;
+    a.seed = seed;
+    a.cap = cap;
+    a.bytes_cap = bytes_cap;
+    a.metrics = (int32_t*)sl->is_met.p;
+    a.index = (int32_t*)sl->is_idx.p;
+    a.key_offsets = (int64_t*)sl->is_off.p;
+    a.bytes = (uint8_t*)sl->is_bytes.p;
+    a.totals = (IopsTotals*)sl->is_tot.dp;
+    ((IopsTotals*)sl->is_tot.p)->n = -1;  // not written yet
+    // behind the routing kernels and the ev_up record on their stream: the detect pipeline waits
+    // for ev_up only, so it never waits for the sample
+    hipStream_t us = cs->ustream;
+    HIPOK(hipMemsetAsync(sl->is_state.p, 0, state_bytes, us));
+    uint64_t* sw = (uint64_t*)sl->is_state.p;
+    ScanState st{sw + 8, (int*)sw, (int*)(sw + 1)};
+    t_record = nullptr;
+    HIPOK(hipEventRecord(sl->ev_is0, us));
+    launch_iops_sample(us, a, st);
+    HIPOK(take_launch_error());
+    HIPOK(hipEventRecord(sl->ev_is1, us));
+    sl->is_inflight = true;
+    b->is_req = true;
+    return FDBCS_OK;
+}
+
+int fdbcs_batch_iops_sample(fdbcs_batch* b, int64_t* n_out, int64_t* key_bytes_out) {
+    if (!b || !n_out || !key_bytes_out) return FDBCS_E_INVALID;
+    if (!b->cs) return FDBCS_E_STATE;
+    HIPOK(hipSetDevice(b->cs->device));
+    if (int rc = finish_route(b)) return rc;  // the routing's error first (the request went with the batch)
+    if (!b->is_req) return FDBCS_E_STATE;
+    BatchSlot* sl = b->slot;
+    if (!b->is_done) {
+        HIPOK(hipEventSynchronize(sl->ev_is1));
+        sl->is_inflight = false;
+        std::atomic_thread_fence(std::memory_order_acquire);
+        IopsTotals t;
+        memcpy(&t, (const void*)sl->is_tot.p, sizeof(t));
+        int32_t words[4];  // the scan's counter and error words
+        HIPOK(hipMemcpy(words, sl->is_state.p, sizeof(words), hipMemcpyDeviceToHost));
+        if (words[2] || t.n < 0) return FDBCS_E_DEVICE;  // look-back bound, key buffer
+        b->is_n = t.n;
+        b->is_nbytes = t.key_bytes;
+        b->is_ms = ev_ms(sl->ev_is0, sl->ev_is1);
+        b->is_done = true;
+    }
+    *n_out = b->is_n;
+    *key_bytes_out = b->is_nbytes;
+    return FDBCS_OK;
+}
+
+int fdbcs_batch_iops_sample_read(fdbcs_batch* b, uint8_t* key_bytes, int64_t key_bytes_cap, int64_t* key_offsets,
+                                 int32_t* metrics, int32_t* index, int64_t cap) {
+    if (!b || key_bytes_cap < 0 || cap < 0 || !key_offsets) return FDBCS_E_INVALID;
+    if (!b->cs || !b->is_req || !b->is_done) return FDBCS_E_STATE;
+    if (cap < b->is_n || key_bytes_cap < b->is_nbytes) return FDBCS_E_NOMEM;
+    if ((b->is_n && !metrics) || (b->is_nbytes && !key_bytes)) return FDBCS_E_INVALID;
+    HIPOK(hipSetDevice(b->cs->device));
+    const BatchSlot* sl = b->slot;
+    const size_t n = (size_t)b->is_n;
+    if (n) HIPOK(hipMemcpy(metrics, sl->is_met.p, 4 * n, hipMemcpyDeviceToHost));
+    if (n && index) HIPOK(hipMemcpy(index, sl->is_idx.p, 4 * n, hipMemcpyDeviceToHost));
+    HIPOK(hipMemcpy(key_offsets, sl->is_off.p, 8 * (n + 1), hipMemcpyDeviceToHost));
+    if (b->is_nbytes) HIPOK(hipMemcpy(key_bytes, sl->is_bytes.p, (size_t)b->is_nbytes, hipMemcpyDeviceToHost));
+    return FDBCS_OK;
+}
+
+int fdbcs_batch_iops_sample_timing(fdbcs_batch* b, double* ms_kernels) {
+    if (!b || !ms_kernels) return FDBCS_E_INVALID;
+    if (!b->is_req || !b->is_done) return FDBCS_E_STATE;
+    *ms_kernels = b->is_ms;
     return FDBCS_OK;
 }
 

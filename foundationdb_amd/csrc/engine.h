@@ -407,6 +407,34 @@ int64_t route_scan_words(int64_t n_elems, bool reports = false);
 // TooOld (SkipList.cpp:770) of a routed batch against the oldest version at detect time.
 void launch_route_too_old(hipStream_t s, const BatchDev& b, int64_t oldest);
 
+// ---- the resolver's iops sample of a routed batch (fdbcs_batch_set_iops_sample; Resolver.actor.cpp:
+// 178-192): the begin keys the roll keeps, in range order, in the layout of a history export.
+constexpr uint32_t kIopsOffsetPerKey = 100;  // SAMPLE_OFFSET_PER_KEY (fdbserver/Knobs.cpp)
+constexpr int kIopsScanP = 1;                // elements per thread of the sample's scan
+constexpr int kIopsTile = kScanThreads * kIopsScanP;
+// Totals of one sample (host-mapped).
+struct IopsTotals {
+    int64_t n, key_bytes;
+};
+struct IopsArgs {
+    const DKey* keys;          // the routed batch's endpoints (range i's begin at 2i: reads, then writes)
+    const uint8_t* tail;       // its tail arena
+    const RouteResult* dres;   // the routing's device result: R, W and its error
+    uint32_t units;            // metricUnitsPerSample, 1 .. 2^31 - 1
+    uint64_t seed;
+    int64_t cap;               // ranges the result arrays hold (the routing's read + write capacities)
+    int64_t bytes_cap;         // bytes the key buffer holds
+    int32_t* metrics;          // [n] what addMetric takes: max(metric, units)
+    int32_t* index;            // [n] the range
+    int64_t* key_offsets;      // [n + 1]
+    uint8_t* bytes;
+    IopsTotals* totals;        // host-mapped
+};
+// 8-byte words of the sample's scan state: counter and error words, then its granules.
+int64_t iops_scan_words(int64_t cap);
+// One launch on `s`, after the routing's; the scan state is zeroed by the caller.
+void launch_iops_sample(hipStream_t s, const IopsArgs& a, ScanState st);
+
 // ---- launchers (kernels.hip); all enqueue on `s` and never synchronize.
 // A history tier as the read check sees it.
 struct Tier {

@@ -4751,6 +4751,99 @@ void launch_export(hipStream_t s, const ExportArgs& a, const MaxLevels& basem, u
     fdb_launch(k_export_scan, dim3((unsigned)tiles), dim3(kScanThreads), 0, s, a, st);
 }
 
+// ------------------------------------------------------------------ iops sample
+//
+// The resolver's iopsSample (Resolver.actor.cpp:178-192) of a routed batch: the begin key of every
+// range the resolver kept, TooOld sub-transactions' included, is rolled with
+// TransientStorageMetricSample::add's odds (StorageMetrics.actor.h: metric / metricUnitsPerSample,
+// a metric at or above the unit always) and the sampled ones are handed to the host.  The roll is a
+// counter-based one, so that the host can restate it bit for bit (balancing.iops_roll): range i
+// (read r: r, write w: R + w) under the caller's seed takes the top 32 bits u of splitmix64's
+// finalizer over seed + 0x9E3779B97F4A7C15 (i + 1) and is sampled iff u * units < metric << 32.
+// One launch: a look-back scan with one element per thread (a kept element's store is a chain of
+// dependent loads, as the other gather scans') over two counters, the kept ranges and their key
+// bytes (32-bit: the host refuses capacities whose keys could pass 2^32 bytes).  R and W come from
+// the routing's device result; the grid is sized by the capacities, spare tiles leave at once.
+
+__device__ __forceinline__ uint32_t iops_mix(uint64_t seed, uint64_t i) {
+    uint64_t z = seed + 0x9E3779B97F4A7C15ull * (i + 1);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z = z ^ (z >> 31);
+    return (uint32_t)(z >> 32);
+}
+
+struct IopsScan {
+    IopsArgs a;
+    int* err;
+    static constexpr bool kOwn = true;
+    // [0] sampled ranges, [1] their begin keys' bytes
+    __device__ void load(int64_t i, uint32_t (&v)[2]) const {
+        const uint32_t len = a.keys[2 * i].len;
+        const uint64_t metric = kIopsOffsetPerKey + (uint64_t)len;
+        const bool hit = metric >= a.units || (uint64_t)iops_mix(a.seed, (uint64_t)i) * a.units < (metric << 32);
+        v[0] = hit ? 1u : 0u;
+        v[1] = hit ? len : 0u;
+    }
+    __device__ void store(int64_t i, const uint32_t (&ex)[2], const uint32_t (&own)[2]) const {
+        if (!own[0]) return;
+        const int64_t o = ex[0], P = ex[1];
+        const DKey k = a.keys[2 * i];
+        const uint64_t metric = kIopsOffsetPerKey + (uint64_t)k.len;
+        a.metrics[o] = (int32_t)(metric >= a.units ? metric : a.units);
+        a.index[o] = (int32_t)i;
+        a.key_offsets[o] = P;
+        if (P + (int64_t)k.len > a.bytes_cap) {  // never past the result buffer (the host sized it for every key)
+            atomicOr(err, 8);
+            return;
+        }
+        // the prefix words are big-endian: swapped back, the key's first byte is the lowest; the
+        // tail starts at any byte of the batch's arena (k_route_write packs them), so a tail word is
+        // cut from the two aligned words that hold it (the arena's slack covers the second)
+        const uint64_t w0 = __builtin_bswap64(k.hi), w1 = __builtin_bswap64(k.lo);
+        const uint8_t* tp = a.tail + (k.len > 16u ? k.tail : 0u);
+        export_put_key(a.bytes + P, k.len, (k.len + 7u) >> 3, [&](uint32_t q) {
+            if (q == 0u) return w0;
+            if (q == 1u) return w1;
+            const uintptr_t p = (uintptr_t)(tp + 8u * (q - 2u));
+            const uint64_t* w = (const uint64_t*)(p & ~(uintptr_t)7);
+            const uint32_t sh = (uint32_t)(p & 7u) * 8u;
+            const uint64_t x = w[0], y = w[1];
+            return sh ? (x >> sh) | (y << (64u - sh)) : x;
+        });
+    }
+    __device__ void finish(const uint32_t (&tot)[2]) const {
+        a.key_offsets[tot[0]] = tot[1];
+        a.totals->n = tot[0];
+        a.totals->key_bytes = tot[1];
+    }
+};
+
+__global__ __launch_bounds__(kScanThreads) void k_iops_sample(IopsArgs a, ScanState st) {
+    __shared__ uint32_t sv[2][scan_pad(kIopsScanP)];
+    __shared__ uint32_t swave[2][kScanThreads / 64];
+    __shared__ uint32_t sbase[2];
+    __shared__ int s_tile;
+    // a routing that reported an error placed nothing usable: an empty sample
+    const RouteResult res = *a.dres;
+    int64_t n = res.error ? 0 : (int64_t)res.R + res.W;
+    if (n > a.cap) n = a.cap;  // (the routing reports an error past the capacities: never taken)
+    if (threadIdx.x == 0) s_tile = atomicAdd(st.counter, 1);
+    __syncthreads();
+    const int tile = s_tile;
+    const int64_t ntiles = n > 0 ? (n + kIopsTile - 1) / kIopsTile : 1;
+    if (tile >= ntiles) return;  // spare tile of the capacity-sized launch: nobody waits on it
+    const IopsScan f{a, st.error};
+    scan_tile<2, IopsScan, kIopsScanP>(f, n, tile, ntiles, st, sv, swave, sbase);
+}
+
+int64_t iops_scan_words(int64_t cap) { return 8 + scan_granules(cap, 2, kIopsScanP); }
+
+void launch_iops_sample(hipStream_t s, const IopsArgs& a, ScanState st) {
+    const int64_t tiles = std::max<int64_t>(1, (a.cap + kIopsTile - 1) / kIopsTile);
+    fdb_launch(k_iops_sample, dim3((unsigned)tiles), dim3(kScanThreads), 0, s, a, st);
+}
+
 // ------------------------------------------------------------------ history import
 //
 // H'(k) = max(H(k), I(k)) for lo <= k < hi and H(k) elsewhere, I the step function of the imported

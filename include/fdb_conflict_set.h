@@ -434,6 +434,43 @@ int fdbcs_batch_set_report_output(fdbcs_batch* b, uint8_t* dev_out, int64_t n_gl
  * caller never saw its sub-transactions and learns the map's keys here. */
 int fdbcs_batch_report_entries(fdbcs_batch* b, uint8_t* entry_out, int32_t cap);
 
+/* The resolver's iops sample (Resolver.actor.cpp:178-192) of a routed batch, taken on the device:
+ * what the master's resolutionBalancing asks a resolver for (ResolutionMetricsRequest /
+ * ResolutionSplitRequest, :318-342) is fed by the begin key of every range of every transaction
+ * the resolver was sent, which for a routed batch only the device holds.  The begin key of range i
+ * of the routed batch (read r: i = r, write w: i = n_reads + w, the order of
+ * fdbcs_batch_routed_info's views; TooOld sub-transactions' ranges included, the roll does not
+ * depend on the verdicts) has metric = 100 + its length (SAMPLE_OFFSET_PER_KEY) and is sampled by
+ * TransientStorageMetricSample::add's rule (StorageMetrics.actor.h) under a counter-based roll:
+ *   z = seed + 0x9E3779B97F4A7C15 * (i + 1)                      (mod 2^64)
+ *   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB
+ *   z = z ^ (z >> 31);  u = z >> 32
+ *   sampled = metric >= units  or  u * units < (metric << 32)    (unsigned 64-bit)
+ *   value   = metric if metric >= units else units               (what addMetric is given)
+ * All integer: a host restatement gives the same sample bit for bit.
+ *   fdbcs_batch_set_iops_sample: after fdbcs_batch_add_routed / _map and before detect; enqueues
+ *     the sample behind the routing, off the detect pipeline's path (detect does not wait for it).
+ *     units = metricUnitsPerSample (KEY_BYTES_PER_SAMPLE, 20000 in the reference).  FDBCS_E_STATE on
+ *     a batch that is not routed or is already detected, FDBCS_E_INVALID for a NULL handle or
+ *     units < 1, FDBCS_E_NOMEM when 16 * (cap_reads + cap_writes) + cap_tail of the routing call
+ *     could pass 2^32 bytes of keys.  A second call before detect replaces the request.  A batch
+ *     that never asks launches and allocates nothing.
+ *   fdbcs_batch_iops_sample: blocks until the routing and the sample have run (it neither needs
+ *     nor waits for detect) and returns the sampled ranges and their key bytes.  A routing error
+ *     comes first (FDBCS_E_TIMEOUT / NOMEM / INVALID as from fdbcs_batch_routed_info: the batch is
+ *     empty again and the request is dropped with it); FDBCS_E_STATE when no sample was requested.
+ *   fdbcs_batch_iops_sample_read: the sampled keys in ascending i, in the layout of
+ *     fdbcs_history_export_read (key_offsets[n + 1]), metrics[n] the values above, index[n] (may be
+ *     NULL) the ranges i.  FDBCS_E_NOMEM when a capacity is too small (the result stays
+ *     available); the result can be read any number of times until the batch is destroyed.
+ *   fdbcs_batch_iops_sample_timing: device time of the sample's kernels (valid once
+ *     fdbcs_batch_iops_sample returned). */
+int fdbcs_batch_set_iops_sample(fdbcs_batch* b, int32_t units, uint64_t seed);
+int fdbcs_batch_iops_sample(fdbcs_batch* b, int64_t* n_out, int64_t* key_bytes_out);
+int fdbcs_batch_iops_sample_read(fdbcs_batch* b, uint8_t* key_bytes, int64_t key_bytes_cap, int64_t* key_offsets,
+                                 int32_t* metrics, int32_t* index /* may be NULL */, int64_t cap);
+int fdbcs_batch_iops_sample_timing(fdbcs_batch* b, double* ms_kernels);
+
 /* Diagnostics (tuning, not part of the ConflictSet contract): average device time of one launch
  * of a pipeline kernel over `reps` back-to-back launches on the uploaded batch `b` against the
  * current history, with no batch in flight.  which: 0 = the read check (D.CheckRead); 1-2 = the
