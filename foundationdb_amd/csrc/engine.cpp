@@ -646,11 +646,7 @@ int ensure_workspace(fdbcs_conflict_set* cs, int64_t T, int64_t R, int64_t W) {
     TAKE(samples, sizeof(SortItem) * kMaxSample);
     TAKE(srank, 4 * (kMaxSample + 64));
     w.slab_buckets = (int32_t)slab_buckets;
-    TAKE(pos, 4 * E);
-    TAKE(pmeta, 4 * E);
-    TAKE(cwb, 4 * (E + 1));
-    TAKE(crb, 4 * (E + 1));
-    TAKE(cwe, 4 * (E + 1));
+    TAKE(erec, sizeof(int4) * E);
     TAKE(wends, 8 * (2 * W + 1));
     TAKE(wkeys, sizeof(DKey) * (2 * W + 1));
     TAKE(segk, sizeof(DKey) * (2 * W + 2));
@@ -676,8 +672,6 @@ int ensure_workspace(fdbcs_conflict_set* cs, int64_t T, int64_t R, int64_t W) {
     TAKE(wpk, 4 * (W + 1));
     TAKE(tedges, 4 * edge_cap);
     TAKE(mcs_bits, 8 * (E / 64 + 2));
-    TAKE(seg_b, 4 * (W + 1));
-    TAKE(seg_e, 4 * (W + 1));
     TAKE(seg_lo, 8 * (W + 1));
     TAKE(seg_hi, 8 * (W + 1));
     TAKE(seg_rem, 8 * (W + 1));

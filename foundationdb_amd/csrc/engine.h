@@ -144,7 +144,7 @@ struct Segs {
 };
 
 // Scans of one batch (each owns a slice of the per-batch zeroed scan arena).
-enum ScanKind { kScanEdges, kScanSegSum, kScanCompact, kScanGc, kScanCover, kScanSegNum, kScanFold, kNumScans };
+enum ScanKind { kScanEdges, kScanSegSum, kScanCompact, kScanGc, kScanCover, kScanSegNum, kNumScans };
 
 // Device copy of one batch's packed input (tooOld transactions carry no ranges,
 // as in addTransaction, SkipList.cpp:770-790).
@@ -208,11 +208,8 @@ struct Work {
     int32_t* big_p;        // [E] a big bucket's endpoint ids in sorted order (workgroup path)
     SortItem* samples;     // [kMaxSample] cold start: sample items (k_sample)
     int32_t* srank;        // [kMaxSample + 64] cold start: sample ranks (zeroed per batch)
-    int32_t* pos;          // [2(R+W)] sorted position of each endpoint
-    uint32_t* pmeta;       // [E] meta of the item at each position
-    int32_t* cwb;          // [E+1] write-begins before each position
-    int32_t* crb;          // [E+1] read-begins before each position
-    int32_t* cwe;          // [E+1] write-ends before each position
+    int4* erec;            // [E] per endpoint id p (range p / 2, end p & 1): {sorted position P, write-begins,
+                           // read-begins, write-ends before P}; a range's two records are 32 contiguous bytes
     int2* wends;           // [2W] write endpoints in sorted order: (position, 2 owner + is-end; -1 empty write)
     DKey* wkeys;           // [2W] their keys (tails in the batch's tail region)
     DKey* segk;            // [2W] union segment j: begin key 2j, end key 2j + 1 (D.Combine)
@@ -225,7 +222,7 @@ struct Work {
     int32_t* poff;         // [R+W+1] first candidate pair of each range
     int32_t* pcg;          // [R+W+1] the ranges with candidate pairs, in order (then G)
     int32_t* pcoff;        // [R+W+1] their first pairs (then the pair count): k_edge_fill's index
-    int32_t* pcbase;       // [R+W] their partner lists' bases (cwb / crb at the range's begin)
+    int32_t* pcbase;       // [R+W] their partner lists' bases (write- / read-begins before the range's begin)
     int32_t* pca;          // [R+W] their side of the edge test (EdgePairScan::store)
     int32_t* ecur;         // [R] edges of each read (slots taken; zeroed by the epilogue)
     // write groups (groups != 0): consecutive write-begins (in sorted order) whose writes contain
@@ -249,8 +246,6 @@ struct Work {
     int32_t* tedges;       // [edge_cap] per transaction, its writers not known aborted (packed)
     uint64_t* mcs_bits;    // [E/64+1] sequential-fallback MiniConflictSet
     // union segments (<= W)
-    int32_t* seg_b;        // position of segment begin
-    int32_t* seg_e;        // position of segment end
     int64_t* seg_lo;
     int64_t* seg_hi;
     int64_t* seg_rem;      // -> exclusive prefix after scan

@@ -1506,11 +1506,13 @@ __global__ __launch_bounds__(kBlock) void k_sort_partition(BatchDev b, SortArgs 
     }
 }
 
-// Outputs of k_sort_bucket: what the later kernels read by sorted position.
+// Outputs of k_sort_bucket.  Everything the later kernels want to know about endpoint p's place in
+// the order is one 16-byte record erec[p] = {sorted position P, write-begins before P, read-begins
+// before P, write-ends before P}, indexed by endpoint id (p = 2 range + is-end), not by position: a
+// range's two records are 32 contiguous bytes, so the edge scan reads them coalesced instead of
+// gathering per-position count arrays through a position array.
 struct SortOut {
-    int32_t* pos;      // [E] position of endpoint p
-    uint32_t* pmeta;   // [E] meta at position P
-    int32_t *cwb, *crb, *cwe;  // [E + 1] write-begins / read-begins / write-ends before position P
+    int4* erec;        // [E] record of endpoint p
     int32_t *wbrange, *rbrange;  // ranges of the write-begins / read-begins in sorted order
     SortItem* items;   // [E] sorted items (FDBCS_VALIDATE) or null
     SplitKey* quant;   // quantiles of this batch for the next one, or null
@@ -1581,11 +1583,7 @@ __device__ __forceinline__ void put_position(const BatchDev& b, const SortOut& o
                                              int32_t rb, int32_t we) {
     const uint32_t meta = endpoint_meta(b, p);
     const uint32_t cls = item_class(meta);
-    o.pmeta[P] = meta;
-    o.pos[p] = (int32_t)P;
-    o.cwb[P] = wb;
-    o.crb[P] = rb;
-    o.cwe[P] = we;
+    o.erec[p] = make_int4((int32_t)P, wb, rb, we);
     if (cls == kWriteBegin) o.wbrange[wb] = p >> 1;  // (the edge scans want the range, not P)
     if (cls == kReadBegin) o.rbrange[rb] = p >> 1;
     if (o.items) o.items[P] = make_item(b, p);
@@ -1919,15 +1917,6 @@ __global__ __launch_bounds__(kBlock) void k_sort_bucket(BatchDev b, SortArgs a, 
                     s_base[q][c] = run[c];
                     run[c] += s_cnt[q][c];
                 }
-            if (blockIdx.x == 0) {  // class totals after the last position
-                uint32_t t4[4] = {0, 0, 0, 0};
-                for (int q = 0; q < kWaves; q++)
-#pragma unroll
-                    for (int c = 0; c < 4; c++) t4[c] += s_red[4 + c][q];
-                o.cwb[E] = (int32_t)t4[1];
-                o.crb[E] = (int32_t)t4[2];
-                o.cwe[E] = (int32_t)t4[3];
-            }
         }
         __syncthreads();
         if (threadIdx.x == 0) trace_max(a.trace, kTrBktPrologue);
@@ -1960,7 +1949,7 @@ __global__ __launch_bounds__(kBlock) void k_sort_bucket(BatchDev b, SortArgs a, 
                 put_position(b, o, ps[s], base + k, (int32_t)ex[0], (int32_t)ex[1], (int32_t)ex[2]);
                 if (o.quant) put_quantiles(b, o.quant, base + k, E, ps[s]);
             } else if (live && ex[0] == 0x7fffffff) {
-                o.pos[0] = 0;
+                o.erec[0] = make_int4(0, 0, 0, 0);
             }
         }
         if (a.trace && lane == 0) {
@@ -2081,7 +2070,7 @@ void launch_sort(hipStream_t s, const BatchDev& b, const Work& w, SplitKey* quan
     }
     const SortArgs a = sort_args(w, quant, nb, b.tail_n, long_keys);
     fdb_launch(k_sort_partition, dim3((E + kBlock - 1) / kBlock), dim3(kBlock), (uint32_t)(16 * (nb - 1)), s, b, a);
-    SortOut o{w.pos, w.pmeta, w.cwb, w.crb, w.cwe, w.wbrange, w.rbrange, validate ? w.items : nullptr,
+    SortOut o{w.erec, w.wbrange, w.rbrange, validate ? w.items : nullptr,
               quant_out, w.big, w.big_p};
     const int grid = (nb + kBlock / 64 - 1) / (kBlock / 64);
     if (long_keys)
@@ -2104,7 +2093,7 @@ hipError_t debug_time_sort(hipStream_t s, const BatchDev& b, const Work& w, Spli
     if ((err = hipEventCreate(&e0)) || (err = hipEventCreate(&e1))) return err;
     SortArgs a = sort_args(w, quant, nb, b.tail_n, long_keys);
     if (const char* v = getenv("FDBCS_SORT_EXP")) a.exp = atoi(v);  // cost breakdown (results unused)
-    SortOut o{w.pos, w.pmeta, w.cwb, w.crb, w.cwe, w.wbrange, w.rbrange, nullptr, nullptr, w.big, w.big_p};
+    SortOut o{w.erec, w.wbrange, w.rbrange, nullptr, nullptr, w.big, w.big_p};
     const int grid = (nb + kBlock / 64 - 1) / (kBlock / 64);
     double total = 0;
     for (int r = 0; r < reps && err == hipSuccess; r++) {
@@ -2133,16 +2122,18 @@ hipError_t debug_time_sort(hipStream_t s, const BatchDev& b, const Work& w, Spli
     return err;
 }
 
-// FDBCS_VALIDATE=1: check the endpoint order and that positions invert the permutation.
-__global__ __launch_bounds__(kBlock) void k_validate_sort(const SortItem* sorted, const int32_t* pos,
-                                                          const uint32_t* pmeta, int E, const uint8_t* arena,
-                                                          BatchScalars* sc) {
+// FDBCS_VALIDATE=1: check the endpoint order and that the records' positions invert the permutation.
+__global__ __launch_bounds__(kBlock) void k_validate_sort(const SortItem* sorted, const int4* erec, int E,
+                                                          const uint8_t* arena, BatchScalars* sc) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= E) return;
     bool bad = p > 0 && !item_less_total(sorted[p - 1], sorted[p], arena);
-    bad |= sorted[p].meta != pmeta[p];
-    const int q = pos[p];  // slot p -> position
-    bad |= q < 0 || q >= E || (2 * item_range(pmeta[q]) + item_is_end(pmeta[q])) != (uint32_t)p;
+    const int q = erec[p].x;  // endpoint p -> position
+    bad |= q < 0 || q >= E;
+    if (!bad) {
+        const uint32_t m = sorted[q].meta;
+        bad = (2 * item_range(m) + item_is_end(m)) != (uint32_t)p;
+    }
     if (bad) atomicOr(&sc->debug_error, 1);
 }
 
@@ -2150,7 +2141,7 @@ void launch_validate_sort(hipStream_t s, const BatchDev& b, const Work& w) {
     const int E = 2 * (b.R + b.W);
     if (E == 0) return;
     fdb_launch(k_validate_sort, dim3((E + kBlock - 1) / kBlock), dim3(kBlock), 0, s, (const SortItem*)w.items,
-               (const int32_t*)w.pos, (const uint32_t*)w.pmeta, E, (const uint8_t*)b.tail, w.bsc);
+               (const int4*)w.erec, E, (const uint8_t*)b.tail, w.bsc);
 }
 
 // ------------------------------------------------------------------ D.CheckIntraBatch: candidate edges
@@ -2163,24 +2154,25 @@ void launch_validate_sort(hipStream_t s, const BatchDev& b, const Work& w) {
 //
 // Every (range, candidate) pair is enumerated in parallel, so a hot key written by hundreds of
 // transactions and read by thousands (Zipf, C3) costs no serial per-range loop:
-//   * read r owns the write-begins inside (rb, re): wbrange[cwb[rb] .. cwb[re]) ("a" pairs);
-//   * write w owns the read-begins inside (wb, we): rbrange[crb[wb] .. crb[we]) ("b" pairs).
+//   * read r owns the write-begins inside (rb, re): wbrange[wb(rb) .. wb(re)) ("a" pairs), wb(p) =
+//     the write-begins before endpoint p (erec[p].y);
+//   * write w owns the read-begins inside (wb, we): rbrange[rb(wb) .. rb(we)) ("b" pairs), rb(p) =
+//     erec[p].z.
 // Read r owns eoff[r+1] - eoff[r] slots: its a pairs plus one per write covering rb, a count that
 // is #(write-begins before rb) - #(write-ends before rb), known without enumerating (an empty write
 // has its end before its begin and no read-begin between them, so it counts 0).  Only pairs that
 // pass the filter (earlier writer, both ranges non-empty) take a slot, so read r's edges are
 // edges[eoff[r] .. eoff[r] + ecur[r]).
 
-__device__ __forceinline__ bool range_nonempty(const Work& w, int g) { return w.pos[2 * g] < w.pos[2 * g + 1]; }
+__device__ __forceinline__ bool range_nonempty(const Work& w, int g) {
+    return w.erec[2 * g].x < w.erec[2 * g + 1].x;
+}
 
-// Per range g: slots (reads only) and pairs; exclusive prefixes give each read's first slot and
-// each range's first pair.
-// The read-begins a write contains, as an interval of read-begin indices (empty: none).
-__device__ __forceinline__ uint2 write_rb_interval(const Work& w, int g) {
-    const int b = w.pos[2 * g], e = w.pos[2 * g + 1];
-    if (b >= e) return make_uint2(0, 0);
-    const int lo = w.crb[b], hi = w.crb[e];
-    return hi > lo ? make_uint2((uint32_t)lo, (uint32_t)hi) : make_uint2(0, 0);
+// The read-begins a write contains, as an interval of read-begin indices (empty: none), from the
+// records of its two endpoints.
+__device__ __forceinline__ uint2 write_rb_interval(const int4& rb, const int4& re) {
+    if (rb.x >= re.x) return make_uint2(0, 0);
+    return re.z > rb.z ? make_uint2((uint32_t)rb.z, (uint32_t)re.z) : make_uint2(0, 0);
 }
 
 // Elements per thread of the scans whose visits are chains of dependent gathers (scan.h): one,
@@ -2190,6 +2182,13 @@ constexpr int kCombineP = 1;
 constexpr int kCombineTile = kScanThreads * kCombineP;
 constexpr int kRouteScanP = 1;
 
+// Per range g: slots (reads only) and pairs; exclusive prefixes give each read's first slot and
+// each range's first pair.  A visit reads the range's two endpoint records (32 contiguous bytes
+// per lane, one round) and derives from them alone whether the range is empty, its pair and slot
+// counts, a write's places in the sorted write endpoints and its write-begin index j.  Only the
+// group-lead test goes further: wbrange[j - 1], then that write's two records (three rounds for a
+// write, one for a read).  The arrays the sort wrote are read through restrict-qualified pointers,
+// so the scatter stores in between force no reload.
 struct EdgePairScan {
     Work w;
     int32_t R, G;
@@ -2197,55 +2196,57 @@ struct EdgePairScan {
     const DKey* keys;
     const int32_t* rowner;
     int32_t T;
-    __device__ void counts(int64_t g, uint32_t& slots, uint32_t& pairs, uint32_t& a) const {
-        slots = pairs = a = 0;
-        if (g >= R) {
-            // the write's two entries in the sorted list of write endpoints (index = write
-            // endpoints before its position), read by D.Combine at the end of k_resolve
-            const int pb = w.pos[2 * g], pe = w.pos[2 * g + 1];
-            const int code = pb < pe ? 2 * wowner[g - R] : -1;
-            const int ib = w.cwb[pb] + w.cwe[pb], ie = w.cwb[pe] + w.cwe[pe];
-            w.wends[ib] = make_int2(pb, code);
-            w.wends[ie] = make_int2(pe, code < 0 ? -1 : code + 1);
-            w.wkeys[ib] = keys[2 * g];
-            w.wkeys[ie] = keys[2 * g + 1];
-        }
-        if (g >= R && w.groups) {
-            // write-begin index j of this write; it leads a group unless the write before it in
-            // sorted order contains the same read-begins (then that group's edges cover it)
-            const int j = w.cwb[w.pos[2 * g]];
-            const uint2 iv = write_rb_interval(w, (int)g);
-            int lead = 0;
-            if (iv.y > iv.x) {
-                lead = 2;
-                if (j > 0) {
-                    const int gp = w.wbrange[j - 1];
-                    const uint2 ip = write_rb_interval(w, gp);
-                    if (ip.x == iv.x && ip.y == iv.y) lead = 1;
-                }
-            }
-            w.wlead[j] = lead;
-            w.wtxn[j] = wowner[g - R];
-            if (lead == 2) pairs = iv.y - iv.x;
-            return;
-        }
-        if (!range_nonempty(w, (int)g)) return;
-        const int b = w.pos[2 * g], e = w.pos[2 * g + 1];
-        if (g < R) {
-            a = (uint32_t)(w.cwb[e] - w.cwb[b]);
-            const int cover = w.cwb[b] - w.cwe[b];  // < 0 only with an inverted write (invalid input)
-            slots = a + (uint32_t)(cover > 0 ? cover : 0);
-            pairs = a;
-        } else {
-            pairs = (uint32_t)(w.crb[e] - w.crb[b]);
-        }
-    }
     static constexpr bool kOwn = true;
     // counts: edge slots, candidate pairs, has pairs (the compacted index k_edge_fill searches)
     __device__ void load(int64_t g, uint32_t (&v)[3]) const {
-        uint32_t a;
-        counts(g, v[0], v[1], a);
-        v[2] = v[1] > 0 ? 1u : 0u;
+        const int4* __restrict__ erec = w.erec;
+        const int32_t* __restrict__ wbrange = w.wbrange;
+        const int32_t* __restrict__ wown = wowner;
+        const DKey* __restrict__ k = keys;
+        const int4 rb = erec[2 * g], re = erec[2 * g + 1];
+        const bool nonempty = rb.x < re.x;
+        uint32_t slots = 0, pairs = 0;
+        if (g < R) {
+            if (nonempty) {
+                const uint32_t a = (uint32_t)(re.y - rb.y);
+                const int cover = rb.y - rb.w;  // < 0 only with an inverted write (invalid input)
+                slots = a + (uint32_t)(cover > 0 ? cover : 0);
+                pairs = a;
+            }
+        } else {
+            // the write's two entries in the sorted list of write endpoints (index = write
+            // endpoints before its position), read by D.Combine at the end of k_resolve
+            const int own = wown[g - R];
+            const int code = nonempty ? 2 * own : -1;
+            const int ib = rb.y + rb.w, ie = re.y + re.w;
+            w.wends[ib] = make_int2(rb.x, code);
+            w.wends[ie] = make_int2(re.x, code < 0 ? -1 : code + 1);
+            w.wkeys[ib] = k[2 * g];
+            w.wkeys[ie] = k[2 * g + 1];
+            if (w.groups) {
+                // write-begin index j of this write; it leads a group unless the write before it in
+                // sorted order contains the same read-begins (then that group's edges cover it)
+                const int j = rb.y;
+                const uint2 iv = write_rb_interval(rb, re);
+                int lead = 0;
+                if (iv.y > iv.x) {
+                    lead = 2;
+                    if (j > 0) {
+                        const int gp = wbrange[j - 1];
+                        const uint2 ip = write_rb_interval(erec[2 * gp], erec[2 * gp + 1]);
+                        if (ip.x == iv.x && ip.y == iv.y) lead = 1;
+                    }
+                }
+                w.wlead[j] = lead;
+                w.wtxn[j] = own;
+                if (lead == 2) pairs = iv.y - iv.x;
+            } else if (nonempty) {
+                pairs = (uint32_t)(re.z - rb.z);
+            }
+        }
+        v[0] = slots;
+        v[1] = pairs;
+        v[2] = pairs > 0 ? 1u : 0u;
     }
     __device__ void store(int64_t g, const uint32_t (&ex)[3], const uint32_t (&own)[3]) const {
         if (g < R) w.eoff[g] = (int32_t)ex[0];
@@ -2254,15 +2255,16 @@ struct EdgePairScan {
             w.pcg[ex[2]] = (int32_t)g;
             w.pcoff[ex[2]] = (int32_t)ex[1];
             // k_edge_fill's per-range operands (its staging then takes one load, not three): the
-            // base of the partner list (cwb / crb at the range's begin) and the range's side of the
-            // edge test (the read's owner; the write's owner, or its group's edge T + j)
-            const int p0 = w.pos[2 * g];
+            // base of the partner list (write- / read-begins before the range's begin) and the
+            // range's side of the edge test (the read's owner; the write's owner, or its group's
+            // edge T + j)
+            const int4 rb = w.erec[2 * g];
             if (g < R) {
-                w.pcbase[ex[2]] = w.cwb[p0];
+                w.pcbase[ex[2]] = rb.y;
                 w.pca[ex[2]] = rowner[g];
             } else {
-                w.pcbase[ex[2]] = w.crb[p0];
-                w.pca[ex[2]] = w.groups ? T + w.cwb[p0] : wowner[g - R];
+                w.pcbase[ex[2]] = rb.z;
+                w.pca[ex[2]] = w.groups ? T + rb.y : wowner[g - R];
             }
         }
     }
@@ -2305,7 +2307,7 @@ __device__ __forceinline__ int wave_last_le(const int32_t* a, int lo, int hi, in
 
 __global__ __launch_bounds__(kBlock) void k_edge_fill(BatchDev b, Work w) {
     // per compacted range of the step: first pair, range id, the base of its partner list
-    // (cwb / crb at its begin) and its side of the edge test (the read's owner, or the write's
+    // (write- / read-begins before its begin) and its side of the edge test (the read's owner, or the write's
     // edge target), staged once so each pair's chain starts at the partner list
     __shared__ int32_t s_off[kFillPairs + 2], s_g[kFillPairs + 1], s_b[kFillPairs + 1], s_a[kFillPairs + 1];
     __shared__ int s_c[2];
@@ -2464,14 +2466,8 @@ struct SegNumScan {
     __device__ void store(int64_t i, const uint32_t (&ex)[1]) const {
         const uint8_t f = w.cflag[i];
         if (!f) return;
-        const int x = w.wends[i].x;
-        if (f == 1) {  // segment ex opens here
-            w.seg_b[ex[0]] = x;
-            w.segk[2 * ex[0]] = w.wkeys[i];
-        } else {       // the segment opened last (ex - 1) closes here
-            w.seg_e[ex[0] - 1] = x;
-            w.segk[2 * ex[0] - 1] = w.wkeys[i];
-        }
+        if (f == 1) w.segk[2 * ex[0]] = w.wkeys[i];  // segment ex opens here
+        else w.segk[2 * ex[0] - 1] = w.wkeys[i];     // the segment opened last (ex - 1) closes here
     }
     __device__ void finish(const uint32_t (&tot)[1]) const { w.bsc->n_segments = tot[0]; }
 };
@@ -2956,7 +2952,7 @@ __global__ __launch_bounds__(kWG) void k_resolve(BatchDev b, Work w, uint8_t* vo
             if (st[t] != kUndecided) continue;  // uniform: st read after a barrier
             int conflict_at = INT_MAX;
             for (int r = b.roff[t]; r < b.roff[t + 1]; r++) {
-                const int a = w.pos[2 * r], e = w.pos[2 * r + 1];
+                const int a = w.erec[2 * r].x, e = w.erec[2 * r + 1].x;
                 int hit = 0;
                 if (a < e) {
                     for (int word = (a >> 6) + threadIdx.x; word <= ((e - 1) >> 6); word += blockDim.x) {
@@ -2975,7 +2971,7 @@ __global__ __launch_bounds__(kWG) void k_resolve(BatchDev b, Work w, uint8_t* vo
             if (conflict_at == INT_MAX) {
                 for (int x = b.woff[t]; x < b.woff[t + 1]; x++) {
                     const int g = b.R + x;
-                    const int a = w.pos[2 * g], e = w.pos[2 * g + 1];
+                    const int a = w.erec[2 * g].x, e = w.erec[2 * g + 1].x;
                     if (a < e) {
                         for (int word = (a >> 6) + threadIdx.x; word <= ((e - 1) >> 6); word += blockDim.x) {
                             uint64_t m = ~0ull;
@@ -3130,11 +3126,6 @@ struct Epilogue {
 // The batch merges into the delta tier, whose header is kHole: an E that inherits kHole lets the
 // base tier show through from E on, exactly as the reference's E keeps the old version.
 
-__device__ __forceinline__ const DKey& seg_key(const BatchDev& b, const Work& w, int pos, int end) {
-    const int g = (int)item_range(w.pmeta[pos]);
-    return b.keys[2 * g + end];
-}
-
 constexpr int kDeltaTile = 256;   // copy tile of the (small) delta tier: ~4 workgroups per CU at C2
 constexpr int kBaseTile = 4096;   // copy tile of the base tier during compaction
 
@@ -3208,9 +3199,11 @@ __global__ __launch_bounds__(seg_threads(LONG, WIDE)) void k_seg_prep(BatchDev b
     int64_t pos = 0;
     bool eq = false;
     DKey kb{}, ke{};
+    const DKey* __restrict__ segk = w.segk;
     if (live) {
-        kb = seg_key(b, w, w.seg_b[sg], 0);
-        ke = seg_key(b, w, w.seg_e[sg], 1);
+        // D.Combine left the segment's two keys side by side (their tails stay in b.tail)
+        kb = segk[2 * sg];
+        ke = segk[2 * sg + 1];
         const DKey& key = role ? ke : kb;
         if constexpr (LONG) {
             static_assert(WIDE, "long-key batches take the one-lane layout");
@@ -3231,7 +3224,7 @@ __global__ __launch_bounds__(seg_threads(LONG, WIDE)) void k_seg_prep(BatchDev b
             s_lo[0] = live ? pos : 0;
         } else if (live) {
             const int64_t lo = pos;
-            const bool glue = sg + 1 < U && dkey_cmp(seg_key(b, w, w.seg_b[sg + 1], 0), b.tail, ke, b.tail) == 0;
+            const bool glue = sg + 1 < U && dkey_cmp(segk[2 * (sg + 1)], b.tail, ke, b.tail) == 0;
             const bool endins = !exact && !glue;
             w.seg_lo[sg] = lo;
             w.seg_hi[sg] = hi;
@@ -3429,19 +3422,15 @@ __global__ __launch_bounds__(kBlock) void k_merge_copy(Segs g, Hist src, Hist ds
 // Inserts of a union segment: B at `now`, E (when needed) at the version it had.
 struct BatchIns {
     BatchDev b;
-    const uint32_t* pmeta;
-    const int32_t *seg_b, *seg_e;
+    const DKey* segk;  // segment s: begin key 2s, end key 2s + 1 (D.Combine); tails in b.tail
     const int64_t *tlen, *vend;
     const uint8_t* endins;
     uint8_t* htail;
     const Scalars* sc;
     int64_t now;
-    __device__ const DKey& key(int pos, int end) const {
-        return b.keys[2 * (int)item_range(pmeta[pos]) + end];
-    }
     __device__ void operator()(int s, Hist dst, int64_t o) const {
         int64_t tu = sc->tail_used / 8 + tlen[s];  // 8-byte unit of this segment's first tail
-        const DKey kb = key(seg_b[s], 0);
+        const DKey kb = segk[2 * s];
         uint32_t tb = 0;
         if (kb.len > 16) {
             tb = (uint32_t)tu;
@@ -3452,7 +3441,7 @@ struct BatchIns {
         dst.lt[o] = make_uint2(kb.len, tb);
         dst.ver[o] = now;
         if (endins[s]) {
-            const DKey ke = key(seg_e[s], 1);
+            const DKey ke = segk[2 * s + 1];
             uint32_t te = 0;
             if (ke.len > 16) {
                 te = (uint32_t)tu;
@@ -3527,9 +3516,7 @@ void launch_merge(hipStream_t s, const BatchDev& b, const Work& w, const Hist& s
     fdb_event(LaunchList::kTimingRecord, copy_begin, s);
     BatchIns ins{};
     ins.b = b;
-    ins.pmeta = w.pmeta;
-    ins.seg_b = w.seg_b;
-    ins.seg_e = w.seg_e;
+    ins.segk = w.segk;
     ins.tlen = w.seg_tlen;
     ins.vend = w.seg_vend;
     ins.endins = w.seg_endins;

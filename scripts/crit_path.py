@@ -39,7 +39,20 @@ def main():
     for k in occ:
         occ[k].sort()
     # the check may be two kernels per batch (split): keep the later-ending one per batch as "check"
-    n = min(len(v) for k, v in occ.items() if k != "k_check_lanes")
+    # the rounds and the combine kernel are left out of batches without a candidate edge
+    optional = ("k_resolve<", "k_combine")
+    n = min(len(v) for k, v in occ.items() if k != "k_check_lanes" and k not in optional)
+    for k in optional:
+        # a launch belongs to the batch whose pre-pass ended last before it; a batch without one
+        # gets an empty interval at its pre-pass's end
+        pre = occ["k_resolve_pre"][len(occ["k_resolve_pre"]) - n:]
+        by = {}
+        for s, e, q in occ.get(k, []):
+            i = max((j for j in range(n) if pre[j][1] <= s), default=None)
+            if i is not None:
+                by[i] = (s, e, q)
+        print(f"{k}: in {len(by)} of {n} batches")
+        occ[k] = [by.get(i, (pre[i][1], pre[i][1], pre[i][2])) for i in range(n)]
     # extra launches before the first batch (the history's initial index build runs k_epilogue)
     for k in occ:
         if k != "k_check_lanes" and len(occ[k]) > n:
@@ -47,6 +60,9 @@ def main():
             occ[k] = occ[k][len(occ[k]) - n:]
     checks = occ.get("k_check_lanes", [])
     per = len(checks) // n if n else 1
+    if len(checks) > per * n:  # the check's launches of the passes before the traced batches
+        print(f"k_check_lanes: {len(checks) - per * n} launches before the first batch dropped")
+        checks = occ["k_check_lanes"] = checks[len(checks) - per * n:]
     if per > 1:
         print(f"{per} check launches per batch: grouped")
         grp = [checks[i * per:(i + 1) * per] for i in range(n)]
@@ -75,6 +91,11 @@ def main():
     ends = [en("k_epilogue", i) for i in range(n)]
     iv = [us(ends[i + 1] - ends[i]) for i in B]
     print(f"batches {n}, steady {len(B)}: epilogue-to-epilogue median {statistics.median(iv):.1f} us, mean {statistics.mean(iv):.1f}")
+    # each chain's stream over the steady batches: the share of the span its kernels occupy
+    span = ends[B[-1]] - ends[B[0] - 1] if B[0] > 0 else ends[B[-1]] - st("k_sort_partition", B[0])
+    for name, ks in (("A", A), ("X", X), ("Y", Y)):
+        busy = sum(en(k, i) - st(k, i) for k in ks for i in B)
+        print(f"  stage {name} stream busy share {100.0 * busy / span:5.1f} %  ({us(busy) / len(B):.1f} us of {us(span) / len(B):.1f} us per batch)")
     rows = {
         "A busy (partition start..edge_fill end)": lambda i: en("k_edge_fill", i) - st("k_sort_partition", i),
         "A kernels sum": lambda i: sum(en(k, i) - st(k, i) for k in A),
