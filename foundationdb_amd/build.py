@@ -10,8 +10,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "libfdbcs.so")
-SOURCES = ["engine.cpp", "kernels.hip"]
-HEADERS = ["dkey.h", "engine.h", "scan.h", "launch.h", "lane_xor.h"]
+# The engine's sources, named here once: roofline.BUILD_SOURCES (the build id of profile files) and
+# scripts/build_variant.sh (same-box A/B libraries) read these lists.
+SOURCES = ["engine.cpp", "transfer.cpp", "kernels.hip", "transfer.hip"]
+HEADERS = ["dkey.h", "engine.h", "engine_impl.h", "transfer.h", "search.h", "scan.h", "launch.h", "lane_xor.h"]
+PUBLIC_HEADER = "include/fdb_conflict_set.h"  # relative to the repository root
 ARCH = os.environ.get("FDBCS_OFFLOAD_ARCH", "gfx950")
 
 
@@ -26,7 +29,7 @@ def _stale() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in SOURCES + HEADERS] + [os.path.join(ROOT, "include", "fdb_conflict_set.h")]
+    deps = [os.path.join(CSRC, f) for f in SOURCES + HEADERS] + [os.path.join(ROOT, PUBLIC_HEADER)]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -38,7 +41,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     common = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
               "-mllvm", "-disable-promote-alloca-to-lds"]
     for src in SOURCES:
-        obj = os.path.join(CSRC, src.rsplit(".", 1)[0] + ".o")
+        obj = os.path.join(CSRC, src + ".o")  # transfer.cpp and transfer.hip: the suffix stays in the name
         cmd = [hipcc, *common, "-c", os.path.join(CSRC, src), "-o", obj]
         if src.endswith(".cpp"):
             cmd = [hipcc, "-O3", "-std=c++17", "-fPIC", "-Wall", "-c", os.path.join(CSRC, src), "-o", obj]

@@ -49,10 +49,14 @@ FDB_HD uint32_t item_class(uint32_t meta) { return meta & 3u; }
 FDB_HD uint32_t item_range(uint32_t meta) { return meta >> 3; }
 FDB_HD uint32_t item_is_end(uint32_t meta) { return (meta >> 2) & 1u; }
 
-#if defined(__HIP_DEVICE_COMPILE__)
-// Eight tail bytes starting at p as a big-endian word, from the two aligned words that hold them
-// (tail arenas start 8-aligned and carry >= 40 bytes of slack past their last tail, so the
-// aligned loads of tail_cmp stay inside the allocation).
+#if defined(__HIPCC__)
+// The eight bytes starting at p (any alignment) as a big-endian word, from the two aligned words
+// that hold them: the one unaligned load of the device code.  Both words are always read, so a
+// buffer read this way starts 8-aligned and has >= 8 readable bytes past the last byte asked for:
+// history and overlay tail arenas and the export's bound tails carry kTailSlack = 64 bytes past
+// their capacity (engine_impl.h), a batch's tail region 48 (engine.cpp upload_layout), and the
+// imported or exported key bytes (i_bytes, x_bytes) and the import's bounds (i_bnd) are allocated
+// with 64 bytes to spare (transfer.cpp).
 __device__ __forceinline__ uint64_t tail_word(const uint8_t* p) {
     const uintptr_t a = (uintptr_t)p;
     const uint64_t* w = (const uint64_t*)(a & ~(uintptr_t)7);
@@ -60,6 +64,10 @@ __device__ __forceinline__ uint64_t tail_word(const uint8_t* p) {
     const uint64_t x = w[0], y = w[1];
     return __builtin_bswap64(sh ? (x >> sh) | (y << (64u - sh)) : x);
 }
+// The same bytes with p[0] lowest (the two swaps cancel in the compiler).  The hot path's
+// tail_word keeps the body: as a wrapper of this one it compiled to other schedules in the
+// pipeline's kernels.
+__device__ __forceinline__ uint64_t load8_unaligned(const uint8_t* p) { return __builtin_bswap64(tail_word(p)); }
 #endif
 
 // Compare the bytes of two tails [16, min(la, lb)) then lengths.  On the device, 32 bytes per

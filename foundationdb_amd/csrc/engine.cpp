@@ -6,531 +6,14 @@
 // key prefixes plus a tail arena; detectConflicts uploads the batch with one pinned H2D copy,
 // enqueues the kernel pipeline on the set's stream, and copies back one verdict byte per
 // transaction.  No CPU fallback exists: without a usable HIP device every entry point fails.
-#include <hip/hip_runtime.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <unistd.h>
-
-#include <cxxabi.h>
-
-#include <algorithm>
-#include <array>
-#include <atomic>
-#include <chrono>
-#include <condition_variable>
-#include <functional>
-#include <mutex>
-#include <new>
-#include <string>
-#include <thread>
-#include <unordered_set>
-#include <vector>
-
-#include "../../include/fdb_conflict_set.h"
-#include "engine.h"
-
-using namespace fdbcs;
-
-#define HIPOK(expr)                                                                                   \
-    do {                                                                                              \
-        hipError_t _e = (expr);                                                                       \
-        if (_e != hipSuccess) {                                                                       \
-            fprintf(stderr, "fdbcs: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(_e), __FILE__, \
-                    __LINE__);                                                                        \
-            return FDBCS_E_DEVICE;                                                                    \
-        }                                                                                             \
-    } while (0)
+// The entry points of the maintenance side (history export and import, the iops sample) are in
+// transfer.cpp; the set's state both files work on is in engine_impl.h.
+#include "engine_impl.h"
 
 // Base-tier size from which the read check splits by default (FDBCS_SPLIT_CHECK=2).
 constexpr int64_t kSplitCheckMinBase = 16 << 20;
 
-namespace {
-
-size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-constexpr int64_t kTailSlack = 64;  // bytes past a tail arena's capacity (dkey.h tail_word reads aligned words)
-// History tails are 8-byte aligned and addressed in 8-byte units by the uint32 Hist::lt.y: the
-// arena holds up to 32 GiB of tail bytes per conflict set (detect refuses a batch past that).
-constexpr int64_t kTailLimit = (int64_t)8 << 32;
-constexpr int64_t kTailReclaimDefault = kTailLimit / 2;  // force the GC repack past half of that
-
-// Grow-only device allocation.
-struct DBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= cap) return FDBCS_OK;
-        size_t want = std::max(bytes, cap + cap / 2);
-        want = align_up(want < 256 ? 256 : want, 256);
-        if (p) HIPOK(hipFree(p));
-        p = nullptr;
-        cap = 0;
-        HIPOK(hipMalloc(&p, want));
-        cap = want;
-        return FDBCS_OK;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-
-// Grow-only pinned host allocation; `mapped` buffers are fine-grained and written by kernels directly.
-struct HBuf {
-    void* p = nullptr;
-    void* dp = nullptr;  // device view (mapped buffers)
-    size_t cap = 0;
-    int ensure(size_t bytes, bool mapped = false, bool noncoherent = false) {
-        if (bytes <= cap) return FDBCS_OK;
-        size_t want = align_up(std::max(bytes, cap + cap / 2), 4096);
-        if (p) HIPOK(hipHostFree(p));
-        p = dp = nullptr;
-        cap = 0;
-        const unsigned fl = !mapped ? hipHostMallocDefault
-                                    : (hipHostMallocMapped | (noncoherent ? hipHostMallocNonCoherent : hipHostMallocCoherent));
-        HIPOK(hipHostMalloc(&p, want, fl));
-        if (mapped) HIPOK(hipHostGetDevicePointer(&dp, p, 0));
-        cap = want;
-        return FDBCS_OK;
-    }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = dp = nullptr;
-        cap = 0;
-    }
-};
-
-enum Phase {
-    kPhStart, kPhUpload, kPhSort, kPhEdges, kPhCheck, kPhIntra, kPhCombine, kPhCopyBegin, kPhCopyEnd, kPhMerge,
-    kPhCompBegin, kPhCompEnd, kPhCompact, kPhGc, kPhEpilogue, kPhEnd,
-    kPhCheckBegin, kPhCheckEnd, kPhSortBegin, kPhSortEnd, kPhCount
-};
-
-}  // namespace
-
-struct fdbcs_batch;
-struct BatchSlot;
-
-// ws[k] slots: ensure_workspace TAKEs [0, kWsTileSlot); then the copy-tile index and the scan arena.
-constexpr int kWsTileSlot = 54, kWsArenaSlot = 55;
-// Batch workspaces in rotation: stage A can run up to two batches ahead of stage B, so each
-// workspace is reused every third batch.
-constexpr int kNumWork = 3;
-constexpr int kGcEveryCompactions = 4;  // removeBefore cadence of size-triggered compactions
-
-// FDBCS_HOST_TRACE=<path>: host-side spans of the pipeline (steady_clock ns, the clock rocprofv3
-// timestamps use), written as CSV when the set is destroyed: per batch sequence number the detect
-// call (D), the helper's issue of stage A (A) and of a Y half (Y), the calling thread's issue of an
-// X half (X) and the wait for the completion flag (W).  scripts/host_trace.py joins them with a
-// rocprofv3 kernel trace: when each chain's launches were issued against when they ran.
-struct HSpan {
-    uint32_t seq;
-    char kind;
-    int64_t t0, t1;
-};
-inline int64_t mono_ns(std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now()) {
-    return std::chrono::duration_cast<std::chrono::nanoseconds>(t.time_since_epoch()).count();
-}
-
-// Host threads for addTransaction of whole batches (fdbcs_batch_add_packed): the endpoint keys'
-// validation and normalization into pinned staging split over chunks of transactions.  The
-// calling thread works too.  A ticket carries the job's generation, so a worker that wakes late
-// never takes a ticket of a later job with the earlier job's function.  Between jobs a worker
-// sleeps on the condition variable (spinning ~300 us for the next job measured no better:
-// DESIGN.md §5).
-struct AddPool {
-    std::vector<std::thread> th;
-    std::mutex m;
-    std::condition_variable cv;
-    std::atomic<uint64_t> ticket{0};  // generation << 32 | next ticket
-    std::atomic<int> done{0};         // tickets finished in the current generation
-    std::atomic<uint32_t> gen{0};
-    std::atomic<int> sleepers{0};
-    int n = 0;
-    const std::function<void(int)>* job = nullptr;
-    bool stop = false;
-
-    // std::thread's constructor throws (std::system_error) at the process's thread limit: the
-    // workers already started are stopped and joined before the exception leaves, so the caller
-    // can fall back to the serial loop
-    explicit AddPool(int workers) {
-        try {
-            for (int i = 0; i < workers; i++) th.emplace_back([this] { worker(); });
-        } catch (...) {
-            shutdown();
-            throw;
-        }
-    }
-    ~AddPool() { shutdown(); }
-    void shutdown() {
-        {
-            std::lock_guard<std::mutex> lk(m);
-            stop = true;
-            gen.fetch_add(1);
-        }
-        cv.notify_all();
-        for (auto& t : th)
-            if (t.joinable()) t.join();
-    }
-    void run(uint32_t g, int nn, const std::function<void(int)>* fn) {
-        uint64_t cur = ticket.load(std::memory_order_acquire);
-        for (;;) {
-            if ((uint32_t)(cur >> 32) != g || (int)(cur & 0xffffffffu) >= nn) return;
-            if (ticket.compare_exchange_weak(cur, cur + 1, std::memory_order_acq_rel)) {
-                (*fn)((int)(cur & 0xffffffffu));
-                done.fetch_add(1, std::memory_order_acq_rel);
-                cur = ticket.load(std::memory_order_acquire);
-            }
-        }
-    }
-    void worker() {
-        uint32_t seen = 0;
-        for (;;) {
-            uint32_t g;
-            int nn;
-            const std::function<void(int)>* fn;
-            {
-                std::unique_lock<std::mutex> lk(m);
-                if (gen.load(std::memory_order_relaxed) == seen && !stop) {
-                    sleepers.fetch_add(1);
-                    cv.wait(lk, [&] { return stop || gen.load(std::memory_order_relaxed) != seen; });
-                    sleepers.fetch_sub(1);
-                }
-                if (stop) return;
-                seen = g = gen.load(std::memory_order_relaxed);
-                nn = n;
-                fn = job;
-            }
-            run(g, nn, fn);
-        }
-    }
-    // fn(c) for c in [0, tickets), in ticket order across the workers and the calling thread;
-    // returns when all are done.
-    void parallel_for(int tickets, const std::function<void(int)>& fn) {
-        uint32_t g;
-        {
-            std::lock_guard<std::mutex> lk(m);
-            g = gen.load(std::memory_order_relaxed) + 1;
-            n = tickets;
-            job = &fn;
-            done.store(0, std::memory_order_relaxed);
-            ticket.store((uint64_t)g << 32, std::memory_order_release);
-            gen.store(g, std::memory_order_release);
-        }
-        if (sleepers.load(std::memory_order_acquire) > 0) cv.notify_all();
-        run(g, tickets, &fn);
-        while (done.load(std::memory_order_acquire) < tickets) __builtin_ia32_pause();
-    }
-};
-
-struct fdbcs_conflict_set {
-    int device = 0;
-    hipStream_t stream = nullptr;   // stage B: everything that reads or writes the history, in batch order
-    hipStream_t astream = nullptr;  // stage A (and every upload): history-independent sort and edges
-    hipStream_t cstream = nullptr;  // split read check: the base-tier half (history-independent between
-                                    // compactions) beside stage A
-    hipEvent_t ev_c[kNumWork] = {}; // base-tier check of the batch using workspace k is done
-    hipEvent_t ev_cmp = nullptr;    // stage B of the last batch that rewrote the base (compaction / GC)
-    bool cmp_recorded = false;
-    // FDBCS_SPLIT_CHECK: 0 = one read check over both tiers in stage B, 1 = the base-tier half on
-    // its own stream beside stage A, 2 (default) = split only over a large base tier (>= 16M
-    // boundaries): there the base check is long (C4: ~150 us) and must leave the batch-order
-    // chain; over a 5M base (C2) the single launch measured faster (device-resident 34.0M vs
-    // 32.1M txns/s: one launch and two cross-stream events fewer, no third stream competing)
-    int split_check = 2;
-    hipStream_t ustream = nullptr;  // batch uploads (k_upload over PCIe), so batch i+1's upload overlaps
-                                    // batch i's stage A; stage A waits for the upload's event
-    hipEvent_t ev_a[kNumWork] = {}; // stage A of the batch using workspace k is done
-    hipEvent_t ev_b[kNumWork] = {}; // stage B (epilogue) of the batch using workspace k is done
-    // Stage B in two halves on two streams: X (`stream`: read check, resolution, D.Combine) and Y
-    // (`ystream`: merge into the delta, compaction / GC, epilogue).  The check of batch i + 1 runs
-    // against the delta before batch i's merge plus batch i's union segments (PrevSegs), so it does
-    // not wait for that merge: Y(i) overlaps X(i + 1).
-    hipStream_t ystream = nullptr;
-    hipEvent_t ev_res[kNumWork] = {};   // X of the batch using workspace k is done (Y waits for it)
-    // the next batch's check is done with workspace k's segments: that batch's ev_res (the end of
-    // its half X, recorded anyway, and not re-recorded before workspace k's next user records)
-    hipEvent_t xfree_ev[kNumWork] = {};
-    bool prev_segs = false;             // the last batch's segments are not merged when the next check runs
-    int prev_wp = 0;
-    int64_t prev_now = 0;
-    int last_wp = -1, prev2_wp = -1;    // workspaces of the last two batches submitted (their Y events)
-    bool xfree_rec[kNumWork] = {};      // xfree_ev[k] set since workspace k's last use
-    // The batches behind ws ev_b[k] (workspace k's last user) and xfree_ev[k] (the batch whose check
-    // reads workspace k's segments), or null once destroyed: while a batch lives its completion
-    // flag tells whether its stages are done, one load from host-mapped memory instead of an event
-    // query (a runtime call) per dependency per batch.
-    fdbcs_batch* ws_user[kNumWork] = {};
-    fdbcs_batch* xfree_user[kNumWork] = {};
-    bool y_async[kNumWork] = {};        // Y of workspace k's last batch ran on ystream (not in `stream` order)
-    bool wused[kNumWork] = {};
-    int wpar = 0;                   // workspace of the next batch
-    int timing = 0;       // 0: no events; 1: the copy kernels; 2: every phase (fdbcs_set_timing)
-    uint32_t seq = 0;     // batches submitted (completion flag values)
-    int64_t oldest = 0;          // ConflictSet::oldestVersion (SkipList.cpp:736)
-    int64_t header_version = 0;  // SkipList(Version) header (SkipList.cpp:398-404)
-    int64_t max_written = 0;     // highest version present in the history
-    int gc_interval = 0;          // compaction (and GC) at least every this many batches; 0: by size only
-    int batches_since_compact = 0;
-    int compactions_since_gc = 0;
-    int64_t gc_applied = 0;
-    int64_t delta_limit = 0;      // compaction once the delta may exceed this; 0: automatic
-
-    // base tier: two buffer sets (ping-pong) + range-max levels
-    DBuf hkey[2], hlt[2], hver[2];
-    DBuf lvl[kMaxLevels];  // lvl[0]: sampled key index (the level-0 versions are hver[cur])
-    DBuf dir;              // radix directory over the base tier's level-0 samples (k_directory)
-    DBuf edir[2];          // each delta buffer's directory (epoch-tagged entries, filled by k_epilogue)
-    uint32_t ddir_epoch[2] = {0, 0};  // epoch of each delta buffer's directory (0: none)
-    uint32_t ddir_counter = 0;  // last epoch handed out
-    int cur = 0;
-    int64_t hist_cap = 0;  // elements per buffer set
-    int64_t n_ub = 0;      // upper bound of live base boundaries (exact after a wait)
-    int64_t lvl3_n = 0;
-    int64_t lvl2_n = 0;
-    // delta tier: the same layout, small
-    DBuf dkey[2], dlt[2], dver[2];
-    DBuf dlvl[2][kMaxLevels];  // per delta buffer: the next batch's check reads one while the epilogue builds the other
-    int dcur = 0;
-    int64_t delta_cap = 0;
-    int64_t nd_ub = 0;
-    int64_t dlvl3_n = 0;
-    int64_t dlvl2_n = 0;
-    DBuf cws[6];  // compaction arrays (per delta boundary)
-    DBuf htail[2];  // tail arenas (bytes [16, len) of long keys): append-only between GCs; each GC
-    int tcur = 0;   // repacks the live tails into the other one, reclaiming the rest
-    int64_t tail_ub = 0;
-    int64_t tail_cap = 0;
-    DBuf scal;  // Scalars
-    int64_t route_timeout_ms = 60000;  // FDBCS_ROUTE_TIMEOUT_MS: bound of a routed batch's wait for its shares
-    DBuf route_btail;                  // device routing: tails of this resolver's key-range bounds
-    std::vector<uint8_t> route_bounds; // the bounds route_btail holds (lo | hi bytes), to skip re-uploads
-    // batch workspaces (rotating)
-    DBuf ws[kNumWork][56];  // [0, kWsTileSlot): TAKE slots of ensure_workspace
-    DBuf wbtail[kNumWork];  // Work::btail of each workspace (ensure_btail)
-    int64_t ws_T = -1, ws_R = -1, ws_W = -1;
-    Work work[kNumWork]{};
-    int64_t edge_cap = 0;
-
-    int inflight = 0;
-    bool validate = false;  // FDBCS_VALIDATE=1: device-side invariant checks (tests)
-    int bucket_target = 0;  // FDBCS_SORT_BUCKET: endpoints per sort bucket on average (0 = kSortTarget)
-    bool sort_cold = false; // FDBCS_SORT_COLD=1: splitters from every batch's own samples (tests)
-    DBuf quant;             // the sort's splitter source, two tables: quantiles of the last batch of
-    int qcur = 0;           // >= kQuantMinE endpoints in table qcur; the next such batch writes the other
-    bool quant_valid = false;
-    // the stream of the last stage A (its sort read one splitter table and wrote the other): a batch
-    // whose stage A runs on another stream (a timing-level change) waits for ev_quant recorded there
-    hipStream_t quant_sa = nullptr;
-    hipEvent_t ev_quant = nullptr;
-    int64_t sort_big_buckets = 0;  // buckets past kSlab so far (host view, from the published scalars)
-    bool trace = false;     // FDBCS_TRACE=1: device timestamps of kernel sections printed per batch
-    bool serial = false;    // FDBCS_SERIAL=1: both stages on one stream (no cross-batch overlap)
-    bool no_prepass = false;  // FDBCS_RESOLVE_PREPASS=0: k_resolve without its pre-pass (tests)
-    int64_t tail_reclaim = kTailReclaimDefault;  // FDBCS_TAIL_RECLAIM: tail bytes that force the GC repack
-    bool write_groups = true;  // FDBCS_WRITE_GROUPS=0: one candidate edge per (read, writer) pair (A/B)
-    bool directory = true;  // FDBCS_DIRECTORY=0: base-tier lookups descend the whole sample tree (A/B)
-    // Directory code (MaxLevels::dir_p .. dir_w; set_dir_map): the loaded keys' common prefix
-    // (capped at 15) and the value range of each byte position after it, as many positions as fit
-    // the slot budget (dir_bits).  Keys written later outside the loaded values take neighbouring
-    // codes, so the mapping stays monotone.  (Round 4's directory on the first two key bytes, and
-    // its prefix-only variant, are the special cases this code replaced: DESIGN.md §5.)
-    uint32_t dir_p = 0;
-    uint64_t dir_phi = 0, dir_plo = 0;
-    uint32_t dir_e = 0, dir_top = 0;
-    uint32_t dir_pos[kDirPos] = {}, dir_w[kDirPos] = {};
-    // FDBCS_DIR_BITS: slot budget 2^bits.  0 (default): 2^16, doubled while the base has over
-    // eight level-0 samples per slot (C4: 2^17; a slot of up to 16 samples is counted directly).
-    // A directory is read cold by every batch's check, so a larger one costs cache misses: C2's
-    // isolated check 11.0 us at 2^16, 16.4 at 2^18; C4's 57.3 at 2^17, 62 at 2^19 and 2^20, 64 on
-    // the first two bytes.
-    int dir_bits = 0;
-    DBuf trace_buf;
-    // Per-kernel device time (fdbcs_kernel_profile): launches and milliseconds by kernel, from the
-    // events of timing level 3 (every kernel) or of the timed kernel at level 1.
-    struct KProf {
-        const void* func;
-        int64_t launches;
-        double ms;
-    };
-    std::vector<KProf> kprof;
-    const void* timed_func = nullptr;  // fdbcs_set_timed_kernel
-    HBuf hold;                         // fdbcs_debug_hold: host-mapped release word of the hold kernels
-    HBuf hedge;                        // per workspace {batch seq, any candidate edge} (Work::hedge)
-    bool skip_edges = true;            // FDBCS_SKIP_EDGES=0: always issue the kGroupEdges launches
-    fdbcs_stats stats{};
-    std::vector<BatchSlot*> pool;  // staging slots of destroyed batches, reused by new ones
-    // Two submitting threads (the default since round 4: C2 +3-10 % over five same-box A/Bs, C3 and
-    // C4 unchanged; FDBCS_SUBMIT_THREAD=0 keeps one).  A helper thread issues stage A of batch i
-    // (and its base-tier check) while the calling thread issues stage B's X half of batch i-1,
-    // which waited for this call; the helper then issues that batch's Y half once X is out:
-    // kernel launches on two streams from two threads take about half the wall time of one
-    // thread's (tools/threadbench.hip: 3.4 -> 1.85 us per launch).  The
-    // check of batch i waits (host side) until stage B of batch i-1 is issued, because it may wait
-    // on that stage's compaction event; stage B of batch i waits for the helper to go idle.
-    bool submit_thread = true;
-    // addTransaction threads (FDBCS_ADD_THREADS, workers besides the calling thread; 0 = serial)
-    int add_threads = 5;
-    AddPool* add_pool = nullptr;
-    int wait_query_ms = 2;  // FDBCS_WAIT_QUERY_MS: stream error checks while a wait spins (0: every 4096 spins)
-    // FDBCS_HOST_TRACE: spans of the calling thread [0] and of the helper [1]
-    bool htrace = false;
-    std::vector<HSpan> htr[2];
-    uint32_t work_a_seq = 0, work_y_seq = 0;
-    double add_prof[4] = {0, 0, 0, 0};  // FDBCS_ADD_PROFILE: ms in add's serial pass, slot, count, fill
-    int64_t add_prof_n = 0;
-    std::thread worker;
-    std::mutex wmu;
-    std::condition_variable wcv;
-    std::atomic<int> wjob{0};           // 0 idle, 1 job queued or running, 2 exit
-    std::atomic<uint32_t> b_issued{0};  // stage-B lists issued (their Y halves: helper or flush)
-    uint32_t b_recorded = 0;            // stage-B lists recorded
-    std::atomic<int> werr{0};           // first HIP error of the helper
-    LaunchList work_a, work_c;          // the helper's lists
-    hipStream_t work_sa = nullptr;
-    uint32_t work_need_b = 0;           // the check goes out once b_issued >= this
-    // Stage B's Y half of the previous batch, issued by the helper once the calling thread has
-    // issued its X half.  The calling thread issues record + X, the helper stage A + Y + base
-    // check: their runtime calls split about evenly instead of ~2:1.
-    LaunchList work_y;
-    hipStream_t work_ys = nullptr;
-    uint32_t work_need_x = 0;            // Y goes out once x_issued >= this
-    std::atomic<uint32_t> x_issued{0};   // stage-B X lists issued (calling thread)
-    fdbcs_batch* work_y_batch = nullptr; // whose Y the helper holds (calling thread's view)
-    LaunchList rec_a, rec_b, rec_c, rec_y, pending_b, pending_y;
-    hipStream_t pending_ys = nullptr;  // the stream of pending_y
-    fdbcs_batch* pending_batch = nullptr;
-    std::unordered_set<fdbcs_batch*> live;  // batches not yet destroyed (detached if the set goes first)
-    // fdbcs_history_export: scratch (per delta boundary), the bounds' tails, scan granules + export
-    // words, and the result arrays; all allocated by the first export.  x_valid: a result is pending
-    // and the set has not changed since (detect, load, clear and another export end it).
-    DBuf x_pos, x_val, x_btail, x_state, x_ver, x_off, x_bytes;
-    bool x_valid = false;
-    int64_t x_n = 0, x_nbytes = 0;
-    hipEvent_t x_ev0 = nullptr, x_ev1 = nullptr;  // around the export's kernels
-    double x_ms_kernels = 0, x_ms_d2h = 0;        // of the last export / read (fdbcs_history_export_timing)
-    int64_t x_hdr = 0;                            // the pending result's header version
-    // fdbcs_history_import: device copies of the imported arrays (host-array form), the bounds' bytes,
-    // the overlay stream (keys, lt, versions, tails), the merged stream (value, key, lt) and the import
-    // words; all allocated by the first import and freed with the set.
-    DBuf i_bytes, i_off, i_ver, i_bnd, i_okey, i_olt, i_over, i_otail, i_mval, i_mkey, i_mlt, i_dblt, i_vblt, i_state;
-    DBuf i_gran;                                  // the fold's scan granules
-    hipEvent_t i_ev[6] = {};                      // around the import's three groups of kernels
-    double i_ms_kernels = 0, i_ms_host = 0;       // of the last import (fdbcs_history_import_timing)
-    // fdbcs_history_import_delta: its words + scan granules (allocated by the first delta import), and
-    // what the last successful import of either kind did (fdbcs_history_import_info)
-    DBuf i_dstate;
-    int32_t i_path = 0;                           // 0: folded into a new base, 1: merged into the delta
-    int64_t i_info_base = 0, i_info_before = 0, i_info_after = 0;  // base size; delta size around it
-};
-
-// Host/device staging of one batch.  Batches are short-lived (one per commit batch, as the
-// reference's ConflictBatch), so their pinned and device buffers come from a per-set pool instead
-// of fresh hipHostMalloc / hipMalloc calls.  A slot goes back to the pool only when its batch is
-// destroyed, after its completion flag was seen (the epilogue's last store) or, for a batch still
-// in flight, after its streams were synchronized: the next user's upload needs no event.
-struct BatchSlot {
-    DBuf dev;
-    HBuf pin_in;
-    HBuf pin_out;
-    DBuf dverdict;
-    hipEvent_t ev[kPhCount] = {};
-    bool events_made = false;
-    hipEvent_t ev_up = nullptr;    // upload done (recorded on stage A's stream)
-    HBuf pin_inv;  // fdbcs_batch_set_conflict_output: global -> batch transaction map (host-mapped)
-    // device routing (fdbcs_batch_add_routed): scan state, global -> batch map, read ids, totals
-    DBuf rt_scan, rt_inv, rt_rids, rt_dres, rt_info, rt_txpre;
-    DBuf rt_gids;  // global read index of each kept read (reporting routed batches only)
-    // fdbcs_batch_add_routed_map: the keyResolvers map the batch is routed under (route_map_layout)
-    // and the pinned staging it is copied from
-    DBuf rt_map;
-    HBuf rt_map_pin;
-    HBuf rt_res;
-    hipEvent_t ev_rt0 = nullptr, ev_rt1 = nullptr;  // around the routing kernels
-    bool rt_timed = false;
-    // fdbcs_batch_set_iops_sample: scan state, result arrays, host-mapped totals and the events
-    // around the kernel, all allocated by the slot's first sampled batch.  is_inflight: a sample
-    // was enqueued and nobody has waited for ev_is1 since (it reads the slot's device copy)
-    DBuf is_state, is_met, is_idx, is_off, is_bytes;
-    HBuf is_tot;
-    hipEvent_t ev_is0 = nullptr, ev_is1 = nullptr;
-    bool is_inflight = false;
-    // per-kernel events of the batch (timing level 3, or the timed kernel at level 1)
-    std::vector<hipEvent_t> prof_pool;
-    size_t prof_next = 0;
-    std::vector<std::pair<const void*, std::pair<hipEvent_t, hipEvent_t>>> prof_spans;
-    LaunchList::Profile prof{&prof_pool, &prof_next, &prof_spans};
-};
-
-struct fdbcs_batch {
-    fdbcs_conflict_set* cs = nullptr;
-    BatchSlot* slot = nullptr;
-    int report_enabled = 0;
-    int state = 0;  // 0 adding, 1 uploaded, 2 submitted, 3 done
-    // host staging (pageable); in `direct` mode (one fdbcs_batch_add_packed) the endpoint keys,
-    // owners and tails were normalized straight into slot->pin_in at add time
-    std::vector<int64_t> snap;
-    std::vector<uint8_t> flags;
-    std::vector<int32_t> roff{0}, woff{0};
-    std::vector<int32_t> rowner, wowner;
-    std::vector<DKey> rkeys, wkeys;
-    std::vector<uint8_t> tail;
-    bool direct = false;
-    size_t d_keys = 0, d_rown = 0, d_wown = 0, d_tail = 0, d_small = 0;  // pin_in offsets (direct mode)
-    size_t d_tail_bytes = 0;
-    // device copy
-    BatchDev bd{};
-    size_t tail_bytes = 0;
-    // results
-    uint8_t* h_verdict = nullptr;
-    Scalars* h_scal = nullptr;
-    uint8_t* h_rconf = nullptr;
-    uint8_t* h_hist = nullptr;
-    int32_t* h_first = nullptr;
-    bool gc_ran = false;
-    bool compacted = false;
-    uint32_t seq = 0;
-    volatile uint32_t* h_flag = nullptr;
-    int64_t n_report = 0;  // transactions added with report_conflicting_keys (and reports enabled)
-    uint32_t recorded = 0;  // phases whose events were recorded (bit per Phase)
-    bool any_report = false;
-    int64_t check_hist = 0;  // boundaries (both tiers, upper bound) the read check searched
-    std::vector<int32_t> out_ids;  // fdbcs_batch_set_conflict_output: global index per transaction
-    int64_t out_n = 0;
-    uint8_t* out_dev = nullptr;
-    int wp = 0;           // the workspace this batch's detect used
-    int32_t max_len = 0;  // longest key added (the sort stages tail windows only past kSortNxLen)
-    int64_t wtail = 0;       // history tail bytes the batch's write endpoints could add (8-byte padded)
-    std::vector<int32_t> conf_off, conf_idx;
-    int32_t n_committed = 0, n_too_old = 0;
-
-    // device-routed batch (fdbcs_batch_add_routed): sizes known once the route kernels finished
-    bool routed = false, route_pending = false;
-    int32_t rT = 0, rR = 0, rW = 0;
-    size_t r_tail = 0;
-    int64_t r_global_R = 0;  // reads of all shares
-    int64_t r_cap_ranges = 0, r_cap_tail = 0;  // read + write and tail capacities it was routed with
-    // fdbcs_batch_set_iops_sample: requested; its totals read (fdbcs_batch_iops_sample)
-    bool is_req = false, is_done = false;
-    int64_t is_n = 0, is_nbytes = 0;
-    double is_ms = 0;
-    // fdbcs_batch_set_report_output: device bytes per global read, written at detect
-    uint8_t* rep_dev = nullptr;
-    int64_t rep_n = 0;
-    // a routed reporting batch's roff [T+1] and flags [T], copied into the result buffer at detect
-    // (the wait-time report loop reads them; other batches read the host vectors above)
-    const int32_t* h_roff = nullptr;
-    const uint8_t* h_flags = nullptr;
-
-    int32_t T() const { return routed ? rT : (int32_t)snap.size(); }
-    int32_t R() const { return routed ? rR : roff.back(); }
-    int32_t W() const { return routed ? rW : woff.back(); }
-    size_t tail_size() const { return routed ? r_tail : direct ? d_tail_bytes : tail.size(); }
-};
-
-namespace {
+namespace fdbcs::impl {
 
 void add_key(fdbcs_batch* b, std::vector<DKey>& out, const uint8_t* p, int32_t len) {
     DKey k;
@@ -1055,7 +538,7 @@ UploadLayout upload_layout(size_t T, size_t R, size_t W, size_t tail_bytes) {
     return L;
 }
 
-// History tail bytes a key of this length takes when inserted (8-byte aligned, kernels.hip tail_units).
+// History tail bytes a key of this length takes when inserted (8-byte aligned, search.h tail_units).
 inline int64_t padded_tail(int32_t len) { return len > 16 ? ((int64_t)len - 16 + 7) / 8 * 8 : 0; }
 
 // Prefix words of a key (dkey_prefix), two big-endian loads when the key has 16 bytes or more.
@@ -1289,7 +772,7 @@ double ev_ms(hipEvent_t a, hipEvent_t b) {
     return (double)ms;
 }
 
-}  // namespace
+}  // namespace fdbcs::impl
 
 extern "C" {
 
@@ -1596,501 +1079,6 @@ int fdbcs_load_history(fdbcs_conflict_set* cs, int64_t n, const uint8_t* key_byt
     cs->n_ub = n;
     cs->nd_ub = 0;
     cs->tail_ub = (int64_t)tail.size();
-    return FDBCS_OK;
-}
-
-int fdbcs_history_export(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key,
-                         int32_t hi_len, int64_t floor_version, int64_t* n_out, int64_t* key_bytes_out,
-                         int64_t* header_version_out) {
-    if (!cs || !n_out || !key_bytes_out || !header_version_out) return FDBCS_E_INVALID;
-    if ((lo_len > 0 && !lo_key) || (hi_len > 0 && !hi_key)) return FDBCS_E_INVALID;
-    if (lo_len >= 0 && hi_len >= 0 && cmp_bytes(lo_key, lo_len, hi_key, hi_len) > 0) return FDBCS_E_INVALID;
-    if (cs->inflight) return FDBCS_E_STATE;
-    HIPOK(hipSetDevice(cs->device));
-    if (int rc = sync_all(cs)) return rc;
-    cs->x_valid = false;
-    Scalars sc;
-    HIPOK(hipMemcpy(&sc, cs->scal.p, sizeof(sc), hipMemcpyDeviceToHost));
-    ExportArgs a{};
-    a.nb = sc.n;
-    a.nd = sc.ndb[cs->dcur];
-    const int64_t total = a.nb + a.nd;
-    // the byte scan's exact range (kernels.hip, history export): refuse rather than wrap
-    if (total >= ((int64_t)1 << 29) || 16 * total + sc.tail_used >= ((int64_t)1 << 35)) return FDBCS_E_NOMEM;
-    a.base = hist_of(cs, cs->cur);
-    a.delta = delta_of(cs, cs->dcur);
-    a.htail = (const uint8_t*)cs->htail[cs->tcur].p;
-    a.hdr = cs->header_version;
-    a.floor = floor_version;
-    // lo / hi as RouteArgs::lo / hi: DKey + tail bytes in a small device buffer
-    std::vector<uint8_t> bt;
-    auto norm = [&](const uint8_t* p, int32_t len, DKey& k) {
-        dkey_prefix(p, (uint32_t)len, &k.hi, &k.lo);
-        k.len = (uint32_t)len;
-        k.tail = (uint32_t)bt.size();
-        if (len > 16) bt.insert(bt.end(), p + 16, p + len);
-    };
-    a.has_lo = lo_len >= 0;
-    a.has_hi = hi_len >= 0;
-    if (a.has_lo) norm(lo_key, lo_len, a.lo);
-    if (a.has_hi) norm(hi_key, hi_len, a.hi);
-    const int64_t tiles = export_tiles(total);
-    int rc;
-    if ((rc = cs->x_btail.ensure(bt.size() + kTailSlack))) return rc;
-    if ((rc = cs->x_pos.ensure(8 * (size_t)(a.nd + 1)))) return rc;
-    if ((rc = cs->x_val.ensure(8 * (size_t)(a.nd + 1)))) return rc;
-    if ((rc = cs->x_state.ensure(8 * (size_t)(kXwWords + 4 * tiles)))) return rc;
-    if ((rc = cs->x_ver.ensure(8 * (size_t)(total + 1)))) return rc;
-    if ((rc = cs->x_off.ensure(8 * (size_t)(total + 1)))) return rc;
-    if ((rc = cs->x_bytes.ensure((size_t)(16 * total + sc.tail_used + 64)))) return rc;
-    if (!cs->x_ev0) HIPOK(hipEventCreate(&cs->x_ev0));
-    if (!cs->x_ev1) HIPOK(hipEventCreate(&cs->x_ev1));
-    a.btail = (const uint8_t*)cs->x_btail.p;
-    a.d_pos = (int64_t*)cs->x_pos.p;
-    a.d_val = (int64_t*)cs->x_val.p;
-    a.words = (int64_t*)cs->x_state.p;
-    a.tile_tb = a.words + kXwWords + 3 * tiles;  // after the scan's granules
-    a.versions = (int64_t*)cs->x_ver.p;
-    a.offsets = (int64_t*)cs->x_off.p;
-    a.bytes = (uint8_t*)cs->x_bytes.p;
-    a.bytes_cap = (int64_t)cs->x_bytes.cap;
-    hipStream_t s = cs->stream;
-    if (!bt.empty()) HIPOK(hipMemcpyAsync(cs->x_btail.p, bt.data(), bt.size(), hipMemcpyHostToDevice, s));
-    HIPOK(hipMemsetAsync(cs->x_state.p, 0, 8 * (size_t)(kXwWords + 3 * tiles), s));
-    HIPOK(hipEventRecord(cs->x_ev0, s));
-    launch_export(s, a, levels_of(cs, cs->cur), (uint64_t*)cs->x_state.p + kXwWords, sc.tail_used > 0 ? 2 : 1);
-    HIPOK(take_launch_error());
-    HIPOK(hipEventRecord(cs->x_ev1, s));
-    int64_t words[kXwWords];
-    HIPOK(hipMemcpyAsync(words, cs->x_state.p, sizeof(words), hipMemcpyDeviceToHost, s));
-    HIPOK(hipStreamSynchronize(s));
-    cs->x_ms_kernels = ev_ms(cs->x_ev0, cs->x_ev1);
-    cs->x_ms_d2h = 0;
-    if (((const int32_t*)&words[kXwScan])[1]) return FDBCS_E_DEVICE;  // look-back bound, positions out of order, key buffer
-    cs->x_n = words[kXwN];
-    cs->x_nbytes = words[kXwBytes];
-    cs->x_hdr = words[kXwHeader];
-    cs->x_valid = true;
-    *n_out = cs->x_n;
-    *key_bytes_out = cs->x_nbytes;
-    *header_version_out = words[kXwHeader];
-    return FDBCS_OK;
-}
-
-int fdbcs_history_export_read(fdbcs_conflict_set* cs, uint8_t* key_bytes, int64_t key_bytes_cap, int64_t* key_offsets,
-                              int64_t* versions, int64_t cap) {
-    if (!cs || key_bytes_cap < 0 || cap < 0 || !key_offsets) return FDBCS_E_INVALID;
-    if (!cs->x_valid) return FDBCS_E_STATE;
-    if (cap < cs->x_n || key_bytes_cap < cs->x_nbytes) return FDBCS_E_NOMEM;
-    if ((cs->x_n && !versions) || (cs->x_nbytes && !key_bytes)) return FDBCS_E_INVALID;
-    HIPOK(hipSetDevice(cs->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    if (cs->x_n) HIPOK(hipMemcpy(versions, cs->x_ver.p, 8 * (size_t)cs->x_n, hipMemcpyDeviceToHost));
-    HIPOK(hipMemcpy(key_offsets, cs->x_off.p, 8 * (size_t)(cs->x_n + 1), hipMemcpyDeviceToHost));
-    if (cs->x_nbytes) HIPOK(hipMemcpy(key_bytes, cs->x_bytes.p, (size_t)cs->x_nbytes, hipMemcpyDeviceToHost));
-    cs->x_ms_d2h = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    cs->x_valid = false;
-    return FDBCS_OK;
-}
-
-int fdbcs_history_export_timing(fdbcs_conflict_set* cs, double* ms_kernels, double* ms_d2h) {
-    if (!cs || !ms_kernels || !ms_d2h) return FDBCS_E_INVALID;
-    *ms_kernels = cs->x_ms_kernels;
-    *ms_d2h = cs->x_ms_d2h;
-    return FDBCS_OK;
-}
-
-// What the last successful import did (fdbcs_history_import_info).
-static void import_note(fdbcs_conflict_set* cs, int32_t path, int64_t base, int64_t delta_before, int64_t delta_after) {
-    cs->i_path = path;
-    cs->i_info_base = base;
-    cs->i_info_before = delta_before;
-    cs->i_info_after = delta_after;
-}
-
-// What phase 1 of an import leaves for its continuation.
-struct ImportPlan {
-    Scalars sc;            // the set's scalars before the import
-    int64_t m;             // overlay boundaries
-    int64_t u_end;         // 8-byte units of the overlay's tail arena
-    ImportDeltaArgs d;     // d.a: the arguments both imports share; the rest is the delta import's
-    int64_t dw[kIdWords];  // what k_impd_bounds found (to_delta only)
-};
-
-// The tier pointers of an import's arguments (again after a capacity change: the buffers may have
-// moved).  The fold writes the non-current base buffer and arena, the delta import the non-current
-// delta buffer and the current arena.
-static void import_tiers(fdbcs_conflict_set* cs, ImportArgs& a, bool to_delta) {
-    a.base = hist_of(cs, cs->cur);
-    a.delta = delta_of(cs, cs->dcur);
-    a.htail = (const uint8_t*)cs->htail[cs->tcur].p;
-    a.dst = to_delta ? delta_of(cs, cs->dcur ^ 1) : hist_of(cs, cs->cur ^ 1);
-    a.tdst = (uint8_t*)cs->htail[to_delta ? cs->tcur : cs->tcur ^ 1].p;
-    a.dst_cap = to_delta ? cs->delta_cap : cs->hist_cap;
-    a.tdst_units = cs->tail_cap / 8;
-}
-
-// The merged arrays of phase 2, for `total` positions.
-static int import_merged(fdbcs_conflict_set* cs, ImportArgs& a, int64_t total) {
-    int rc;
-    if ((rc = cs->i_mval.ensure(8 * (size_t)total))) return rc;
-    if ((rc = cs->i_mkey.ensure(16 * (size_t)total))) return rc;
-    if ((rc = cs->i_mlt.ensure(8 * (size_t)total))) return rc;
-    if ((rc = cs->i_dblt.ensure(8 * (size_t)(a.nd + 1)))) return rc;
-    a.m_val = (int64_t*)cs->i_mval.p;
-    a.m_key = (ulonglong2*)cs->i_mkey.p;
-    a.m_lt = (uint2*)cs->i_mlt.p;
-    a.d_blt = (int64_t*)cs->i_dblt.p;
-    return FDBCS_OK;
-}
-
-// Phase 1 of both imports, on device arrays.  The set is idle, its streams drained; d_bytes is
-// 8-byte aligned with >= 16 readable bytes past nbytes.  The host does no per-boundary work: it
-// sizes the overlay from n and nbytes, launches the validation and the overlay's build (to_delta:
-// and the search that places lo and hi in both tiers) and reads the words back once.  *done: the
-// import is over (an empty range: validated, nothing to do).
-static int import_phase1(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key,
-                         int32_t hi_len, int64_t n, const uint8_t* d_bytes, int64_t nbytes, const int64_t* d_off,
-                         const int64_t* d_ver, int64_t ihdr, int64_t* boundaries_out, bool to_delta, ImportPlan& pl,
-                         bool* done) {
-    *done = false;
-    Scalars& sc = pl.sc;
-    HIPOK(hipMemcpy(&sc, cs->scal.p, sizeof(sc), hipMemcpyDeviceToHost));
-    const int64_t nb = sc.n, nd = sc.ndb[cs->dcur];
-    if (nb + nd + n + 2 >= ((int64_t)1 << 31)) return FDBCS_E_NOMEM;  // the fold's 32-bit scan components
-    const bool has_lo = lo_len >= 0, has_hi = hi_len >= 0;
-    const int64_t ll = has_lo ? lo_len : 0, hl = has_hi ? hi_len : 0;
-    // overlay tails, in 8-byte units: imported boundary j at (offset_j >> 3) + j, then lo's and hi's
-    const int64_t u_lo = ((nbytes + 7) >> 3) + n + 1, u_hi = u_lo + ((ll + 7) >> 3) + 1, u_end = u_hi + ((hl + 7) >> 3) + 1;
-    // the fold packs at most that many units behind the arena's bytes, the delta import appends
-    // them from the next whole unit on
-    const int64_t tail_base = (sc.tail_used + 7) >> 3;
-    const int64_t tail_need = to_delta ? 8 * (tail_base + u_end) : sc.tail_used + 8 * u_end;
-    if (tail_need + 1 >= kTailLimit) return FDBCS_E_NOMEM;
-    int rc;
-    const int64_t bnd_hi = (ll + 7) / 8 * 8 + 16;
-    if ((rc = cs->i_bnd.ensure((size_t)(bnd_hi + hl + 64)))) return rc;
-    if ((rc = cs->i_okey.ensure(16 * (size_t)(n + 2)))) return rc;
-    if ((rc = cs->i_olt.ensure(8 * (size_t)(n + 2)))) return rc;
-    if ((rc = cs->i_over.ensure(8 * (size_t)(n + 2)))) return rc;
-    if ((rc = cs->i_otail.ensure(8 * (size_t)u_end + kTailSlack))) return rc;
-    if ((rc = cs->i_vblt.ensure(8 * (size_t)(n + 2)))) return rc;
-    if ((rc = cs->i_state.ensure(8 * (size_t)kIwWords))) return rc;
-    if (to_delta && (rc = cs->i_dstate.ensure(8 * (size_t)kIdWords))) return rc;
-    for (hipEvent_t& e : cs->i_ev)
-        if (!e) HIPOK(hipEventCreate(&e));
-    pl.u_end = u_end;
-    pl.d = ImportDeltaArgs{};
-    ImportArgs& a = pl.d.a;
-    import_tiers(cs, a, to_delta);
-    a.nb = nb;
-    a.nd = nd;
-    a.hdr = cs->header_version;
-    a.n = n;
-    a.bytes = d_bytes;
-    a.nbytes = nbytes;
-    a.offsets = d_off;
-    a.versions = d_ver;
-    a.ihdr = ihdr;
-    a.has_lo = has_lo;
-    a.has_hi = has_hi;
-    a.lo_len = (int32_t)ll;
-    a.hi_len = (int32_t)hl;
-    a.bnd = (const uint8_t*)cs->i_bnd.p;
-    a.bnd_hi = bnd_hi;
-    a.ov.key = (ulonglong2*)cs->i_okey.p;
-    a.ov.lt = (uint2*)cs->i_olt.p;
-    a.ov.ver = (int64_t*)cs->i_over.p;
-    a.otail = (uint8_t*)cs->i_otail.p;
-    a.otail_lo = u_lo;
-    a.otail_hi = u_hi;
-    a.ovhdr = has_lo ? kHole : ihdr;
-    a.words = (int64_t*)cs->i_state.p;
-    a.v_blt = (int64_t*)cs->i_vblt.p;
-    a.new_hdr = has_lo ? cs->header_version : std::max(cs->header_version, ihdr);
-    pl.d.dwords = (int64_t*)cs->i_dstate.p;
-    pl.d.tail_base = tail_base;
-    hipStream_t s = cs->stream;
-    if (ll) HIPOK(hipMemcpyAsync(cs->i_bnd.p, lo_key, (size_t)ll, hipMemcpyHostToDevice, s));
-    if (hl) HIPOK(hipMemcpyAsync((uint8_t*)cs->i_bnd.p + bnd_hi, hi_key, (size_t)hl, hipMemcpyHostToDevice, s));
-    HIPOK(hipMemsetAsync(cs->i_state.p, 0, 8 * (size_t)kIwWords, s));
-    if (to_delta) HIPOK(hipMemsetAsync(cs->i_dstate.p, 0, 8 * (size_t)kIdWords, s));
-    const int64_t none = kHole;
-    HIPOK(hipMemcpyAsync(&a.words[kIwMaxVer], &none, 8, hipMemcpyHostToDevice, s));
-    int64_t words[kIwWords];
-    HIPOK(hipEventRecord(cs->i_ev[0], s));
-    launch_import_overlay(s, a);
-    if (to_delta) launch_import_delta_bounds(s, pl.d);
-    HIPOK(take_launch_error());
-    HIPOK(hipEventRecord(cs->i_ev[1], s));
-    HIPOK(hipMemcpyAsync(words, cs->i_state.p, sizeof(words), hipMemcpyDeviceToHost, s));
-    if (to_delta) HIPOK(hipMemcpyAsync(pl.dw, cs->i_dstate.p, sizeof(pl.dw), hipMemcpyDeviceToHost, s));
-    HIPOK(hipStreamSynchronize(s));
-    cs->i_ms_kernels = ev_ms(cs->i_ev[0], cs->i_ev[1]);
-    if ((int32_t)words[kIwError] & 1) return FDBCS_E_INVALID;
-    if (words[kIwError]) return FDBCS_E_DEVICE;
-    if (has_lo && has_hi && cmp_bytes(lo_key, lo_len, hi_key, hi_len) == 0) {
-        *boundaries_out = nb + nd;
-        import_note(cs, to_delta ? 1 : 0, nb, nd, nd);
-        *done = true;
-        return FDBCS_OK;
-    }
-    pl.m = words[kIwM];
-    if (pl.m < (has_lo ? 1 : 0) + (has_hi ? 1 : 0) || pl.m > n + 2) return FDBCS_E_DEVICE;
-    return FDBCS_OK;
-}
-
-// The end both imports share, once the device scalars hold the new sizes: rebuild the range-max
-// levels of the tier that changed (n_new boundaries), read its greatest version off their top and
-// raise the set's header and greatest written version.
-static int import_finish(fdbcs_conflict_set* cs, const ImportArgs& a, bool delta_tier, int64_t n_new) {
-    hipStream_t s = cs->stream;
-    Scalars* dsc = (Scalars*)cs->scal.p;
-    const MaxLevels lv = delta_tier ? dlevels_of(cs, cs->dcur) : levels_of(cs, cs->cur);
-    const int64_t lvl3_n = delta_tier ? cs->dlvl3_n : cs->lvl3_n, lvl2_n = delta_tier ? cs->dlvl2_n : cs->lvl2_n;
-    HIPOK(hipEventRecord(cs->i_ev[4], s));
-    launch_rangemax(s, lv, dsc, delta_tier ? &dsc->ndb[cs->dcur] : &dsc->n, lvl3_n, lvl2_n,
-                    std::max<int64_t>(n_new, 1));
-    // the top of the rebuilt levels (holes are INT64_MIN), never a pass over the elements
-    launch_import_max(s, lv, lvl3_n, &a.words[kIwMaxVer]);
-    HIPOK(take_launch_error());
-    HIPOK(hipEventRecord(cs->i_ev[5], s));
-    int64_t max_ver;
-    HIPOK(hipMemcpyAsync(&max_ver, &a.words[kIwMaxVer], 8, hipMemcpyDeviceToHost, s));
-    HIPOK(hipStreamSynchronize(s));
-    cs->i_ms_kernels += ev_ms(cs->i_ev[4], cs->i_ev[5]);
-    cs->header_version = a.new_hdr;
-    cs->max_written = std::max({cs->max_written, a.new_hdr, max_ver});
-    cs->ddir_epoch[0] = cs->ddir_epoch[1] = 0;  // the delta's directory: not trusted until an epilogue refills it
-    cs->prev_segs = false;
-    return FDBCS_OK;
-}
-
-// Phase 2 of the fold, from a finished phase 1 of either import: merges the three streams into the
-// non-current base buffer and tail arena and, on success, switches to them with an empty delta.
-static int import_fold(fdbcs_conflict_set* cs, ImportPlan& pl, int64_t* boundaries_out) {
-    ImportArgs& a = pl.d.a;
-    const int64_t nb = a.nb, nd = a.nd, m = pl.m;
-    const int64_t total_ub = nb + nd + a.n + 2;
-    const int64_t tail_need = pl.sc.tail_used + 8 * pl.u_end;
-    int rc;
-    if ((rc = ensure_history(cs, total_ub + 1, tail_need + 1))) return rc;
-    if ((rc = import_merged(cs, a, total_ub))) return rc;
-    // the scan's granules have a buffer of their own: the words of phase 1 stay where they are
-    const size_t gran = 8 * (size_t)scan_granules(total_ub, 2);
-    if ((rc = cs->i_gran.ensure(gran))) return rc;
-    import_tiers(cs, a, false);
-    hipStream_t s = cs->stream;
-    HIPOK(hipMemsetAsync(cs->i_gran.p, 0, gran, s));
-    HIPOK(hipEventRecord(cs->i_ev[2], s));
-    HIPOK(hipMemsetAsync(cs->i_mlt.p, 0, 8 * (size_t)(nb + nd + m), s));
-    launch_import_fold(s, a, m, (uint64_t*)cs->i_gran.p);
-    HIPOK(take_launch_error());
-    HIPOK(hipEventRecord(cs->i_ev[3], s));
-    int64_t words[kIwWords];
-    HIPOK(hipMemcpyAsync(words, cs->i_state.p, sizeof(words), hipMemcpyDeviceToHost, s));
-    HIPOK(hipStreamSynchronize(s));
-    cs->i_ms_kernels += ev_ms(cs->i_ev[2], cs->i_ev[3]);
-    if ((int32_t)words[kIwError] & 8) return FDBCS_E_NOMEM;
-    if (words[kIwError] || ((const int32_t*)&words[kIwScan])[1]) return FDBCS_E_DEVICE;
-    // success: the buffers the fold filled become current, the delta is empty
-    const int64_t kept = words[kIwKept], tail_used = 8 * words[kIwTailUnits];
-    cs->cur ^= 1;
-    cs->tcur ^= 1;
-    Scalars ns{};
-    ns.n = kept;
-    ns.tail_used = tail_used;
-    HIPOK(hipMemcpyAsync(cs->scal.p, &ns, sizeof(ns), hipMemcpyHostToDevice, s));
-    if ((rc = import_finish(cs, a, false, kept))) return rc;
-    cs->n_ub = kept;
-    cs->nd_ub = 0;
-    cs->tail_ub = tail_used;
-    *boundaries_out = kept;
-    import_note(cs, 0, kept, nd, 0);
-    return FDBCS_OK;
-}
-
-// The import that folds into a new base (both of its entry points end here).
-static int import_device(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key,
-                         int32_t hi_len, int64_t n, const uint8_t* d_bytes, int64_t nbytes, const int64_t* d_off,
-                         const int64_t* d_ver, int64_t ihdr, int64_t* boundaries_out) {
-    ImportPlan pl;
-    bool done;
-    const int rc = import_phase1(cs, lo_key, lo_len, hi_key, hi_len, n, d_bytes, nbytes, d_off, d_ver, ihdr,
-                                 boundaries_out, false, pl, &done);
-    return rc || done ? rc : import_fold(cs, pl, boundaries_out);
-}
-
-// The import into the delta tier (same contract).  After phase 1 the host knows an upper bound of
-// the delta afterwards and either goes on (phase 2 writes the non-current delta buffer and arena
-// bytes past tail_used, and the host switches to them after reading the result words) or goes on
-// with the fold's phase 2 on the overlay it has, which leaves an empty delta.
-static int import_delta_device(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key,
-                               int32_t hi_len, int64_t n, const uint8_t* d_bytes, int64_t nbytes, const int64_t* d_off,
-                               const int64_t* d_ver, int64_t ihdr, int64_t* boundaries_out) {
-    ImportPlan pl;
-    bool done;
-    int rc = import_phase1(cs, lo_key, lo_len, hi_key, hi_len, n, d_bytes, nbytes, d_off, d_ver, ihdr, boundaries_out,
-                           true, pl, &done);
-    if (rc || done) return rc;
-    ImportDeltaArgs& d = pl.d;
-    ImportArgs& a = d.a;
-    ImportWindow& w = d.w;
-    Scalars& sc = pl.sc;
-    const int64_t nb = a.nb, nd = a.nd, m = pl.m;
-    const int64_t* dw = pl.dw;
-    w.p_lo = dw[kIdPlo];
-    w.p_hi = dw[kIdPhi];
-    w.q_lo = dw[kIdQlo];
-    w.q_hi = dw[kIdQhi];
-    w.e_ver = dw[kIdEver];
-    d.e_skip = dw[kIdEskip] ? 1 : 0;
-    if (w.p_lo < 0 || w.p_lo > w.p_hi || w.p_hi > nd || w.q_lo < 0 || w.q_lo > w.q_hi || w.q_hi > nb) return FDBCS_E_DEVICE;
-    const int64_t nbr = w.q_hi - w.q_lo;
-    w.closing = a.has_hi ? 1 : 0;
-    w.mr = m - w.closing;
-    w.R = (w.p_hi - w.p_lo) + nbr + w.mr;
-    // the delta afterwards holds at most its boundaries outside the range, the range's and the closing one
-    const int64_t nd_bound = nd + nbr + m + 2;
-    bool fold = nd_bound > delta_limit_for(cs, cs->n_ub);
-    if (!fold) {
-        rc = ensure_delta(cs, nd_bound);
-        if (rc == FDBCS_E_NOMEM)
-            fold = true;
-        else if (rc)
-            return rc;
-    }
-    // the fold takes every range the delta cannot hold: exact, with an empty delta
-    if (fold) return import_fold(cs, pl, boundaries_out);
-    if ((rc = ensure_history(cs, cs->hist_cap, 8 * (d.tail_base + pl.u_end) + 1))) return rc;
-    const int64_t total = w.R + w.closing;
-    const int64_t gran = scan_granules(total, 2);
-    if ((rc = import_merged(cs, a, total + 1))) return rc;
-    if ((rc = cs->i_dstate.ensure(8 * (size_t)(kIdWords + gran)))) return rc;
-    import_tiers(cs, a, true);
-    d.dwords = (int64_t*)cs->i_dstate.p;
-    hipStream_t s = cs->stream;
-    HIPOK(hipMemsetAsync(cs->i_dstate.p, 0, 8 * (size_t)(kIdWords + gran), s));
-    HIPOK(hipEventRecord(cs->i_ev[2], s));
-    HIPOK(hipMemsetAsync(cs->i_mlt.p, 0, 8 * (size_t)(total + 1), s));
-    launch_import_delta_merge(s, d, (uint64_t*)cs->i_dstate.p + kIdWords);
-    HIPOK(take_launch_error());
-    HIPOK(hipEventRecord(cs->i_ev[3], s));
-    HIPOK(hipMemcpyAsync(pl.dw, cs->i_dstate.p, sizeof(pl.dw), hipMemcpyDeviceToHost, s));
-    HIPOK(hipStreamSynchronize(s));
-    cs->i_ms_kernels += ev_ms(cs->i_ev[2], cs->i_ev[3]);
-    if ((int32_t)dw[kIdError] & 8) return FDBCS_E_NOMEM;
-    if (dw[kIdError] || ((const int32_t*)&dw[kIdScan])[1]) return FDBCS_E_DEVICE;
-    const int64_t kept = dw[kIdKept], units = dw[kIdTailUnits];
-    const int64_t nd_new = w.p_lo + kept + (nd - w.p_hi);
-    if (kept < 0 || kept > total || nd_new > cs->delta_cap || units < 0 || units > pl.u_end) return FDBCS_E_DEVICE;
-    // success: the delta buffer the kernels filled becomes current, the appended tails count
-    const int64_t tail_used = units ? 8 * (d.tail_base + units) : sc.tail_used;
-    cs->dcur ^= 1;
-    sc.nd = nd_new;
-    sc.ndb[cs->dcur] = nd_new;
-    sc.tail_used = tail_used;
-    HIPOK(hipMemcpyAsync(cs->scal.p, &sc, sizeof(sc), hipMemcpyHostToDevice, s));
-    if ((rc = import_finish(cs, a, true, nd_new))) return rc;
-    cs->nd_ub = nd_new;  // exact: the next batch's compaction trigger counts the import
-    cs->tail_ub = tail_used;
-    *boundaries_out = nb + nd_new;
-    import_note(cs, 1, nb, nd, nd_new);
-    return FDBCS_OK;
-}
-
-static int import_bounds_ok(const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key, int32_t hi_len) {
-    if ((lo_len > 0 && !lo_key) || (hi_len > 0 && !hi_key)) return FDBCS_E_INVALID;
-    if (lo_len >= 0 && hi_len >= 0 && cmp_bytes(lo_key, lo_len, hi_key, hi_len) > 0) return FDBCS_E_INVALID;
-    return FDBCS_OK;
-}
-
-static int import_arrays(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key,
-                         int32_t hi_len, int64_t n, const uint8_t* key_bytes, const int64_t* key_offsets,
-                         const int64_t* versions, int64_t header_version, int64_t* boundaries_out, bool to_delta) {
-    if (!cs || !boundaries_out || n < 0 || (n > 0 && (!key_offsets || !versions))) return FDBCS_E_INVALID;
-    if (int rc = import_bounds_ok(lo_key, lo_len, hi_key, hi_len)) return rc;
-    const int64_t nbytes = n ? key_offsets[n] : 0;
-    if (nbytes < 0 || (nbytes > 0 && !key_bytes)) return FDBCS_E_INVALID;
-    if (cs->inflight) return FDBCS_E_STATE;
-    const auto t0 = std::chrono::steady_clock::now();
-    HIPOK(hipSetDevice(cs->device));
-    if (int rc = sync_all(cs)) return rc;
-    cs->x_valid = false;
-    // the three arrays go up as they are
-    int rc;
-    if ((rc = cs->i_bytes.ensure((size_t)nbytes + 64))) return rc;
-    if ((rc = cs->i_off.ensure(8 * (size_t)(n + 1)))) return rc;
-    if ((rc = cs->i_ver.ensure(8 * (size_t)(n + 1)))) return rc;
-    hipStream_t s = cs->stream;
-    if (nbytes) HIPOK(hipMemcpyAsync(cs->i_bytes.p, key_bytes, (size_t)nbytes, hipMemcpyHostToDevice, s));
-    if (n) {
-        HIPOK(hipMemcpyAsync(cs->i_off.p, key_offsets, 8 * (size_t)(n + 1), hipMemcpyHostToDevice, s));
-        HIPOK(hipMemcpyAsync(cs->i_ver.p, versions, 8 * (size_t)n, hipMemcpyHostToDevice, s));
-    }
-    rc = (to_delta ? import_delta_device : import_device)(
-        cs, lo_key, lo_len, hi_key, hi_len, n, (const uint8_t*)cs->i_bytes.p, nbytes, (const int64_t*)cs->i_off.p,
-        (const int64_t*)cs->i_ver.p, header_version, boundaries_out);
-    cs->i_ms_host = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return rc;
-}
-
-static int import_pending(fdbcs_conflict_set* dst, fdbcs_conflict_set* src, const uint8_t* lo_key, int32_t lo_len,
-                          const uint8_t* hi_key, int32_t hi_len, int64_t* boundaries_out, bool to_delta) {
-    if (!dst || !src || src == dst || !boundaries_out || src->device != dst->device) return FDBCS_E_INVALID;
-    if (int rc = import_bounds_ok(lo_key, lo_len, hi_key, hi_len)) return rc;
-    if (dst->inflight || src->inflight || !src->x_valid) return FDBCS_E_STATE;
-    const auto t0 = std::chrono::steady_clock::now();
-    HIPOK(hipSetDevice(dst->device));
-    if (int rc = sync_all(dst)) return rc;
-    dst->x_valid = false;
-    // src's export finished on its own stream before fdbcs_history_export returned: its result
-    // arrays are read in place, and stay pending
-    const int rc = (to_delta ? import_delta_device : import_device)(
-        dst, lo_key, lo_len, hi_key, hi_len, src->x_n, (const uint8_t*)src->x_bytes.p, src->x_nbytes,
-        (const int64_t*)src->x_off.p, (const int64_t*)src->x_ver.p, src->x_hdr, boundaries_out);
-    dst->i_ms_host = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return rc;
-}
-
-int fdbcs_history_import(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key,
-                         int32_t hi_len, int64_t n, const uint8_t* key_bytes, const int64_t* key_offsets,
-                         const int64_t* versions, int64_t header_version, int64_t* boundaries_out) {
-    return import_arrays(cs, lo_key, lo_len, hi_key, hi_len, n, key_bytes, key_offsets, versions, header_version,
-                         boundaries_out, false);
-}
-
-int fdbcs_history_import_pending(fdbcs_conflict_set* dst, fdbcs_conflict_set* src, const uint8_t* lo_key, int32_t lo_len,
-                                 const uint8_t* hi_key, int32_t hi_len, int64_t* boundaries_out) {
-    return import_pending(dst, src, lo_key, lo_len, hi_key, hi_len, boundaries_out, false);
-}
-
-int fdbcs_history_import_delta(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key,
-                               int32_t hi_len, int64_t n, const uint8_t* key_bytes, const int64_t* key_offsets,
-                               const int64_t* versions, int64_t header_version, int64_t* boundaries_out) {
-    return import_arrays(cs, lo_key, lo_len, hi_key, hi_len, n, key_bytes, key_offsets, versions, header_version,
-                         boundaries_out, true);
-}
-
-int fdbcs_history_import_delta_pending(fdbcs_conflict_set* dst, fdbcs_conflict_set* src, const uint8_t* lo_key,
-                                       int32_t lo_len, const uint8_t* hi_key, int32_t hi_len, int64_t* boundaries_out) {
-    return import_pending(dst, src, lo_key, lo_len, hi_key, hi_len, boundaries_out, true);
-}
-
-int fdbcs_history_import_info(fdbcs_conflict_set* cs, int32_t* path, int64_t* base_boundaries, int64_t* delta_before,
-                              int64_t* delta_after) {
-    if (!cs || !path || !base_boundaries || !delta_before || !delta_after) return FDBCS_E_INVALID;
-    *path = cs->i_path;
-    *base_boundaries = cs->i_info_base;
-    *delta_before = cs->i_info_before;
-    *delta_after = cs->i_info_after;
-    return FDBCS_OK;
-}
-
-int fdbcs_history_import_timing(fdbcs_conflict_set* cs, double* ms_kernels, double* ms_host) {
-    if (!cs || !ms_kernels || !ms_host) return FDBCS_E_INVALID;
-    *ms_kernels = cs->i_ms_kernels;
-    *ms_host = cs->i_ms_host;
     return FDBCS_OK;
 }
 
@@ -2938,7 +1926,7 @@ int fdbcs_batch_add_routed_map(fdbcs_batch* b, const void* shares, int64_t strid
 }
 
 // Sizes of a routed batch, once its route kernels are done (blocks until then).
-static int finish_route(fdbcs_batch* b) {
+extern "C++" int fdbcs::impl::finish_route(fdbcs_batch* b) {
     if (!b->route_pending) return FDBCS_OK;
     BatchSlot* sl = b->slot;
     HIPOK(hipEventSynchronize(sl->ev_up));
@@ -3881,111 +2869,6 @@ int fdbcs_batch_set_report_output(fdbcs_batch* b, uint8_t* dev_out, int64_t n_gl
     // the size is compared with the shares' reads at detect, once the routing kernels have run
     b->rep_dev = dev_out;
     b->rep_n = n_global_reads;
-    return FDBCS_OK;
-}
-
-// ---- the resolver's iops sample of a routed batch (Resolver.actor.cpp:178-192)
-
-int fdbcs_batch_set_iops_sample(fdbcs_batch* b, int32_t units, uint64_t seed) {
-    if (!b || units < 1) return FDBCS_E_INVALID;
-    if (!b->cs || !b->routed || b->state >= 2) return FDBCS_E_STATE;
-    // the scan counts key bytes in 32 bits: every begin key's 16 prefix bytes and the whole tail arena bound them
-    const int64_t cap = b->r_cap_ranges, bytes_cap = 16 * cap + b->r_cap_tail;
-    if (bytes_cap >= ((int64_t)1 << 32)) return FDBCS_E_NOMEM;
-    fdbcs_conflict_set* cs = b->cs;
-    HIPOK(hipSetDevice(cs->device));
-    BatchSlot* sl = b->slot;
-    if (sl->is_inflight) {  // a request replaced: its kernel is over before its buffers are touched
-        HIPOK(hipEventSynchronize(sl->ev_is1));
-        sl->is_inflight = false;
-    }
-    b->is_req = b->is_done = false;
-    int rc;
-    const size_t state_bytes = 8 * (size_t)iops_scan_words(cap);
-    if ((rc = sl->is_state.ensure(state_bytes))) return rc;
-    if ((rc = sl->is_met.ensure(4 * (size_t)(cap + 1)))) return rc;
-    if ((rc = sl->is_idx.ensure(4 * (size_t)(cap + 1)))) return rc;
-    if ((rc = sl->is_off.ensure(8 * (size_t)(cap + 1)))) return rc;
-    if ((rc = sl->is_bytes.ensure((size_t)bytes_cap + 64))) return rc;
-    if ((rc = sl->is_tot.ensure(sizeof(IopsTotals), true))) return rc;
-    if (!sl->ev_is0) HIPOK(hipEventCreate(&sl->ev_is0));
-    if (!sl->ev_is1) HIPOK(hipEventCreate(&sl->ev_is1));
-    IopsArgs a{};
-    a.keys = b->bd.keys;
-    a.tail = b->bd.tail;
-    a.dres = (const RouteResult*)sl->rt_dres.p;
-    a.units = (uint32_t)units;
-    a.seed = seed;
-    a.cap = cap;
-    a.bytes_cap = bytes_cap;
-    a.metrics = (int32_t*)sl->is_met.p;
-    a.index = (int32_t*)sl->is_idx.p;
-    a.key_offsets = (int64_t*)sl->is_off.p;
-    a.bytes = (uint8_t*)sl->is_bytes.p;
-    a.totals = (IopsTotals*)sl->is_tot.dp;
-    ((IopsTotals*)sl->is_tot.p)->n = -1;  // not written yet
-    // behind the routing kernels and the ev_up record on their stream: the detect pipeline waits
-    // for ev_up only, so it never waits for the sample
-    hipStream_t us = cs->ustream;
-    HIPOK(hipMemsetAsync(sl->is_state.p, 0, state_bytes, us));
-    uint64_t* sw = (uint64_t*)sl->is_state.p;
-    ScanState st{sw + 8, (int*)sw, (int*)(sw + 1)};
-    t_record = nullptr;
-    HIPOK(hipEventRecord(sl->ev_is0, us));
-    launch_iops_sample(us, a, st);
-    HIPOK(take_launch_error());
-    HIPOK(hipEventRecord(sl->ev_is1, us));
-    sl->is_inflight = true;
-    b->is_req = true;
-    return FDBCS_OK;
-}
-
-int fdbcs_batch_iops_sample(fdbcs_batch* b, int64_t* n_out, int64_t* key_bytes_out) {
-    if (!b || !n_out || !key_bytes_out) return FDBCS_E_INVALID;
-    if (!b->cs) return FDBCS_E_STATE;
-    HIPOK(hipSetDevice(b->cs->device));
-    if (int rc = finish_route(b)) return rc;  // the routing's error first (the request went with the batch)
-    if (!b->is_req) return FDBCS_E_STATE;
-    BatchSlot* sl = b->slot;
-    if (!b->is_done) {
-        HIPOK(hipEventSynchronize(sl->ev_is1));
-        sl->is_inflight = false;
-        std::atomic_thread_fence(std::memory_order_acquire);
-        IopsTotals t;
-        memcpy(&t, (const void*)sl->is_tot.p, sizeof(t));
-        int32_t words[4];  // the scan's counter and error words
-        HIPOK(hipMemcpy(words, sl->is_state.p, sizeof(words), hipMemcpyDeviceToHost));
-        if (words[2] || t.n < 0) return FDBCS_E_DEVICE;  // look-back bound, key buffer
-        b->is_n = t.n;
-        b->is_nbytes = t.key_bytes;
-        b->is_ms = ev_ms(sl->ev_is0, sl->ev_is1);
-        b->is_done = true;
-    }
-    *n_out = b->is_n;
-    *key_bytes_out = b->is_nbytes;
-    return FDBCS_OK;
-}
-
-int fdbcs_batch_iops_sample_read(fdbcs_batch* b, uint8_t* key_bytes, int64_t key_bytes_cap, int64_t* key_offsets,
-                                 int32_t* metrics, int32_t* index, int64_t cap) {
-    if (!b || key_bytes_cap < 0 || cap < 0 || !key_offsets) return FDBCS_E_INVALID;
-    if (!b->cs || !b->is_req || !b->is_done) return FDBCS_E_STATE;
-    if (cap < b->is_n || key_bytes_cap < b->is_nbytes) return FDBCS_E_NOMEM;
-    if ((b->is_n && !metrics) || (b->is_nbytes && !key_bytes)) return FDBCS_E_INVALID;
-    HIPOK(hipSetDevice(b->cs->device));
-    const BatchSlot* sl = b->slot;
-    const size_t n = (size_t)b->is_n;
-    if (n) HIPOK(hipMemcpy(metrics, sl->is_met.p, 4 * n, hipMemcpyDeviceToHost));
-    if (n && index) HIPOK(hipMemcpy(index, sl->is_idx.p, 4 * n, hipMemcpyDeviceToHost));
-    HIPOK(hipMemcpy(key_offsets, sl->is_off.p, 8 * (n + 1), hipMemcpyDeviceToHost));
-    if (b->is_nbytes) HIPOK(hipMemcpy(key_bytes, sl->is_bytes.p, (size_t)b->is_nbytes, hipMemcpyDeviceToHost));
-    return FDBCS_OK;
-}
-
-int fdbcs_batch_iops_sample_timing(fdbcs_batch* b, double* ms_kernels) {
-    if (!b || !ms_kernels) return FDBCS_E_INVALID;
-    if (!b->is_req || !b->is_done) return FDBCS_E_STATE;
-    *ms_kernels = b->is_ms;
     return FDBCS_OK;
 }
 

@@ -19,6 +19,10 @@
 //   routing   (multi-resolver)   k_route_mark (or k_route_mark_map under a keyResolvers map),
 //                                k_scan<RouteScan>, k_route_write
 //
+// Only the detect pipeline lives here.  The searches of a tier are in search.h; the kernels that
+// run on an idle set or off the detect stream (history export and import, the iops sample) are in
+// transfer.hip and do not go into this file.
+//
 // Memory-bound integer/byte work: no MFMA anywhere (BASELINE.json north_star).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -29,6 +33,7 @@
 
 #include "engine.h"
 #include "lane_xor.h"
+#include "search.h"
 
 namespace fdbcs {
 
@@ -36,337 +41,7 @@ thread_local LaunchList* t_record = nullptr;
 thread_local uint8_t t_group = 0;
 thread_local hipError_t t_launch_error = hipSuccess;
 
-// ------------------------------------------------------------------ helpers
-
-// History tails are 8-byte aligned and Hist::lt.y counts 8-byte units (32 GiB of tail arena per
-// conflict set with a 32-bit offset).
-__device__ __forceinline__ const uint8_t* hist_tail(const uint8_t* htail, uint32_t unit) {
-    return htail + 8 * (size_t)unit;
-}
-__device__ __forceinline__ uint32_t tail_units(uint32_t len) { return len > 16u ? (len - 16u + 7u) / 8u : 0u; }
-
-// Copy the n tail bytes at src (any alignment; the arena has >= 16 bytes of slack past them) to the
-// 8-aligned dst as whole words; the bytes past n in the last word are never compared (tail_cmp).
-__device__ __forceinline__ void copy_tail_words(uint8_t* dst, const uint8_t* src, uint32_t n) {
-    const uintptr_t a = (uintptr_t)src;
-    const uint64_t* w = (const uint64_t*)(a & ~(uintptr_t)7);
-    const uint32_t sh = (uint32_t)(a & 7u) * 8u;
-    uint64_t* d = (uint64_t*)dst;
-    for (uint32_t i = 0; i < (n + 7u) / 8u; i++) d[i] = sh ? (w[i] >> sh) | (w[i + 1] << (64u - sh)) : w[i];
-}
-
-__device__ __forceinline__ int hist_cmp(const Hist& h, int64_t i, const uint8_t* htail, const DKey& q,
-                                        const uint8_t* qtail) {
-    ulonglong2 k = h.key[i];
-    if (k.x != q.hi) return k.x < q.hi ? -1 : 1;
-    if (k.y != q.lo) return k.y < q.lo ? -1 : 1;
-    uint2 lt = h.lt[i];
-    if (lt.x > 16u && q.len > 16u) return tail_cmp(hist_tail(htail, lt.y), lt.x, qtail + q.tail, q.len);
-    return (lt.x > q.len) - (lt.x < q.len);
-}
-
-__device__ __forceinline__ bool prefix_less(const ulonglong2& k, const DKey& q) {
-    return k.x < q.hi || (k.x == q.hi && k.y < q.lo);
-}
-
-// Full key comparison of boundary i with q, given its prefix already loaded.
-__device__ __forceinline__ int probe_cmp(const Hist& h, int64_t i, const ulonglong2& k, const uint8_t* htail,
-                                         const DKey& q, const uint8_t* qtail) {
-    if (k.x != q.hi) return k.x < q.hi ? -1 : 1;
-    if (k.y != q.lo) return k.y < q.lo ? -1 : 1;
-    return hist_cmp(h, i, htail, q, qtail);  // equal prefixes: length / tail
-}
-// The same with a word-at-a-time tail comparison (one pair of 8-byte words live, not four): keeps
-// the read check's register footprint low; equal 16-byte prefixes are the rare path.
-__device__ __forceinline__ int probe_cmp_lean(const Hist& h, int64_t i, const ulonglong2& k, const uint8_t* htail,
-                                              const DKey& q, const uint8_t* qtail) {
-    if (k.x != q.hi) return k.x < q.hi ? -1 : 1;
-    if (k.y != q.lo) return k.y < q.lo ? -1 : 1;
-    const uint2 lt = h.lt[i];
-#if defined(__HIP_DEVICE_COMPILE__)
-    if (lt.x > 16u && q.len > 16u) {
-        const uint8_t* ta = hist_tail(htail, lt.y);
-        const uint8_t* tb = qtail + q.tail;
-        const uint32_t nb = (lt.x < q.len ? lt.x : q.len) - 16u;
-        for (uint32_t o = 0; o < nb; o += 8) {
-            const int vb = (int)(nb - o);
-            const uint64_t msk = vb >= 8 ? ~0ull : ~0ull << (64 - 8 * vb);
-            const uint64_t x = tail_word(ta + o) & msk, y = tail_word(tb + o) & msk;
-            if (x != y) return x < y ? -1 : 1;
-        }
-    }
-#endif
-    return (lt.x > q.len) - (lt.x < q.len);
-}
-
-// ---- long-key probes (batches with keys over 16 bytes: C4 tuple keys)
-//
-// Keys of one tuple subspace/user share their 16-byte prefix, so the last rounds of a lookup tie
-// on the prefix and compare tails.  The generic probe loads the boundary's (len, tail) only after
-// its prefix tied, then the two tails 32 bytes per dependent round, each tail word through two
-// unaligned loads.  The long-key probe instead holds the query's tail words in registers for the
-// whole lookup (kQW words), loads the boundary's (len, tail) beside its prefix, and reads the
-// history tail (8-byte aligned in its arena) as whole words, kHW per round: one dependent round
-// after the prefix for tails up to 48 bytes, two up to 96.
-constexpr int kQW = 12;  // query tail words in registers: keys up to 112 bytes compare without reloads
-[[maybe_unused]] constexpr int kHW = 6;  // history tail words per load round
-struct QTail {
-    uint64_t w[kQW];  // big-endian words of query bytes [16, 16 + 8 kQW), garbage past the key's end
-};
-
-__device__ __forceinline__ void load_qtail(QTail& qt, const DKey& q, const uint8_t* qtail) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const uint32_t n = q.len > 16u ? q.len - 16u : 0u;
-    const uintptr_t a = (uintptr_t)(qtail + q.tail);
-    const uint64_t* w = (const uint64_t*)(a & ~(uintptr_t)7);
-    const uint32_t sh = (uint32_t)(a & 7u) * 8u;
-    const uint32_t cnt = ((uint32_t)(a & 7u) + n + 7u) / 8u;  // aligned words holding the tail
-    uint64_t raw[kQW + 1];
-#pragma unroll
-    for (int j = 0; j <= kQW; j++) raw[j] = (uint32_t)j < cnt ? w[j] : 0ull;
-#pragma unroll
-    for (int j = 0; j < kQW; j++) qt.w[j] = __builtin_bswap64(sh ? (raw[j] >> sh) | (raw[j + 1] << (64u - sh)) : raw[j]);
-#endif
-}
-
-// probe_cmp with the boundary's (len, tail) already loaded and the query tail in registers.
-__device__ __forceinline__ int probe_cmp_long(const ulonglong2& k, const uint2& lt, const uint8_t* htail, const DKey& q,
-                                              const QTail& qt, const uint8_t* qtail) {
-    if (k.x != q.hi) return k.x < q.hi ? -1 : 1;
-    if (k.y != q.lo) return k.y < q.lo ? -1 : 1;
-#if defined(__HIP_DEVICE_COMPILE__)
-    if (lt.x > 16u && q.len > 16u) {
-        const uint64_t* ha = (const uint64_t*)hist_tail(htail, lt.y);
-        const uint32_t n = (lt.x < q.len ? lt.x : q.len) - 16u;  // common tail bytes
-        const int nw = (int)((n + 7u) / 8u);
-#pragma unroll
-        for (int j0 = 0; j0 < kQW; j0 += kHW) {
-            if (j0 >= nw) break;
-            uint64_t x[kHW];
-#pragma unroll
-            for (int u = 0; u < kHW; u++) x[u] = j0 + u < nw ? ha[j0 + u] : 0ull;
-#pragma unroll
-            for (int u = 0; u < kHW; u++) {
-                const int j = j0 + u;
-                const int vb = (int)n - 8 * j;  // bytes of word j inside the shorter tail
-                if (vb <= 0) break;
-                const uint64_t msk = vb >= 8 ? ~0ull : ~0ull << (64 - 8 * vb);
-                const uint64_t hx = __builtin_bswap64(x[u]) & msk, qy = qt.w[j] & msk;
-                if (hx != qy) return hx < qy ? -1 : 1;
-            }
-        }
-        if (nw > kQW)  // both tails run past the registers: the rest from memory
-            return tail_cmp(hist_tail(htail, lt.y) + 8 * kQW, lt.x - 8 * kQW, qtail + q.tail + 8 * kQW,
-                            q.len - 8 * kQW);
-    }
-#endif
-    return (lt.x > q.len) - (lt.x < q.len);
-}
-
-// ---- cooperative search: kArity lanes per query, one kArity-entry tree node per level
-//
-// Each lane of an aligned kArity-lane group loads one entry of the node, so a level is one
-// coalesced kArity*16-byte access (one 128-byte line at kArity 8).  All lanes of a group call with
-// the same query and get the same result.  gmask(): the group's bits of a wave ballot.
-__device__ __forceinline__ uint32_t gmask(bool pred) {
-    const uint64_t m = __ballot(pred);
-    return (uint32_t)(m >> (threadIdx.x & 63 & ~(kArity - 1))) & ((1u << kArity) - 1u);
-}
-
-// Directory slot of a 16-byte prefix (MaxLevels::dir_p .. dir_w), monotone over all keys: keys
-// below the loaded keys' common prefix take slot 0, keys above it dir_top, keys under it 1 + the
-// mixed-radix code of the next dir_e bytes (each byte's offset in its position's value range; the
-// code ends at the first byte outside its range).  ALU only.  Both tiers' directories
-// (k_directory, the epilogue's delta fill) and every lookup use it.
-__device__ __forceinline__ uint32_t dir_slot(const MaxLevels& m, uint64_t hi, uint64_t lo) {
-    const uint32_t p = m.dir_p;
-    if (p) {
-        const uint64_t mh = p >= 8 ? ~0ull : ~0ull << (64 - 8 * p);
-        const uint64_t ml = p <= 8 ? 0ull : ~0ull << (128 - 8 * p);
-        const uint64_t xh = hi & mh, xl = lo & ml;
-        if (xh != m.dir_phi || xl != m.dir_plo)
-            return (xh < m.dir_phi || (xh == m.dir_phi && xl < m.dir_plo)) ? 0u : m.dir_top;
-    }
-    // the bytes after the prefix, left-aligned: position p + i is byte i of h
-    const uint64_t h = p == 0 ? hi : (p < 8 ? (hi << (8 * p)) | (lo >> (64 - 8 * p)) : lo << (8 * (p - 8)));
-    uint32_t code = 1;
-    bool live = true;
-#pragma unroll
-    for (int i = 0; i < kDirPos; i++) {
-        const uint32_t b = (uint32_t)(h >> (56 - 8 * i)) & 255u;
-        const uint32_t pos = m.dir_pos[i];
-        const uint32_t l = pos & 255u, d = (pos >> 8) & 511u, s = pos >> 17;
-        const uint32_t r = b < l ? 0u : (b - l < d ? b - l : d);
-        if (live && (uint32_t)i < m.dir_e) code += (r >> s) * m.dir_w[i];
-        live = live && b >= l && b - l < d;
-    }
-    return code;
-}
-
-// The directory range of q's slot, in skey8 entries (every 8th boundary): entries [d8a, d8b) share
-// q's slot, every entry before d8a lies below q and every entry from d8b on above it (dir_slot is
-// monotone over the 16-byte prefix).  Both tiers' directories count skey8 entries (base:
-// k_directory, exact; delta: the epilogue's fill, entries of the current epoch only).  false: no
-// directory, or a delta slot of another epoch.
-__device__ __forceinline__ bool dir_range8(const MaxLevels& m, const DKey& q, int64_t& d8a, int64_t& d8b) {
-    if (!m.dir && !m.edir_epoch) return false;
-    const uint32_t dv = dir_slot(m, q.hi, q.lo);
-    if (m.dir) {
-        d8a = m.dir[dv];
-        d8b = m.dir[dv + 1];
-        return true;
-    }
-    const uint64_t x0 = m.edir[dv], x1 = m.edir[dv + 1];
-    d8a = (uint32_t)x0;
-    d8b = (uint32_t)x1;
-    return (uint32_t)(x0 >> 32) == m.edir_epoch && (uint32_t)(x1 >> 32) == m.edir_epoch;
-}
-
-// LONG: the long-key probes above (the batch has keys over 16 bytes); same result.
-template <bool LONG = false>
-__device__ __forceinline__ int64_t group_lower_bound(const Hist& h, const MaxLevels& m, int64_t n, const DKey& q,
-                                                     const uint8_t* htail, const uint8_t* qtail, bool& eq) {
-    const int gl = threadIdx.x & (kArity - 1);
-    const int g0 = threadIdx.x & 63 & ~(kArity - 1);  // first lane of the group
-    eq = false;
-    if (n <= 0) return 0;
-    QTail qt;
-    if constexpr (LONG) load_qtail(qt, q, qtail);  // in flight during the descent
-    // one probe of boundary p (prefix k): the long-key form loads (len, tail) beside the prefix
-    auto probe = [&](int64_t p, const ulonglong2* kp) -> int {
-        if constexpr (LONG) {
-            const ulonglong2 k = *kp;
-            const uint2 lt = h.lt[p];
-            return probe_cmp_long(k, lt, htail, q, qt, qtail);
-        } else {
-            return probe_cmp(h, p, *kp, htail, q, qtail);
-        }
-    };
-    int64_t sz[kIdxLevels];
-    sz[0] = (n + kFan - 1) / kFan;
-#pragma unroll
-    for (int L = 1; L < kIdxLevels; L++) sz[L] = (sz[L - 1] + kArity - 1) / kArity;
-    int top = 0;
-    while (top + 1 < kIdxLevels && sz[top] > kArity) top++;
-    // c = number of entries of level `top` whose prefix is < q.  When level 0 is probed, also learn
-    // whether the first sample not below q shares q's prefix (`bknown`: it does not).
-    auto prefix_eq = [&](const ulonglong2& k) { return k.x == q.hi && k.y == q.lo; };
-    int64_t c = 0;
-    bool bknown = false;
-    // the top level's first group is loaded beside the directory slot (no added round trip when
-    // the slot is crowded and the tree is taken)
-    const bool v_top = gl < sz[top];
-    const ulonglong2 e_top = m.skey[top][v_top ? gl : 0];
-    bool direct = false;
-    int64_t d8a, d8b;
-    if (dir_range8(m, q, d8a, d8b)) {
-        // radix directory: the level-0 samples (every 8th skey8 entry) sharing q's directory bits
-        // are [d0, d1); a slot of at most two groups is counted directly at level 0
-        const int64_t d0 = (d8a + 7) >> 3, d1 = (d8b + 7) >> 3;
-        if (d1 - d0 <= 2 * kArity && d1 <= sz[0]) {
-            direct = true;
-            c = d0;
-            bknown = true;  // all of the slot below q: the next sample's first two bytes are greater
-            for (int64_t j0 = d0; j0 < d1; j0 += kArity) {
-                const bool v = j0 + gl < d1;
-                const ulonglong2 e = m.skey[0][v ? j0 + gl : 0];
-                const int k = __popc(gmask(v && prefix_less(e, q)));
-                c += k;
-                if (k < __popc(gmask(v))) {
-                    bknown = !((gmask(v && prefix_eq(e)) >> k) & 1u);
-                    break;
-                }
-            }
-        }
-    }
-    if (!direct) {
-        for (int64_t j0 = 0; j0 < sz[top]; j0 += kArity) {
-            const bool v = j0 == 0 ? v_top : j0 + gl < sz[top];
-            const ulonglong2 e = j0 == 0 ? e_top : m.skey[top][v ? j0 + gl : 0];
-            const int k = __popc(gmask(v && prefix_less(e, q)));
-            if (top == 0 && k < __popc(gmask(v))) bknown = !((gmask(v && prefix_eq(e)) >> k) & 1u);
-            c += k;
-            if (k < kArity) break;
-        }
-        for (int L = top; L > 0; L--) {
-            if (c == 0) continue;  // nothing below q at this level: nothing below it underneath either
-            // entries of level L-1 below q: [0, c') with c' in [A(c-1)+1, Ac]
-            const int64_t base = (int64_t)kArity * (c - 1) + 1;
-            const int64_t end = min((int64_t)kArity * c, sz[L - 1]);
-            const bool v = base + gl < end;
-            const ulonglong2 e = m.skey[L - 1][v ? base + gl : 0];
-            const int k = __popc(gmask(v && prefix_less(e, q)));
-            if (L == 1 && k < __popc(gmask(v))) bknown = !((gmask(v && prefix_eq(e)) >> k) & 1u);
-            c = base + k;
-        }
-    }
-    // c = #samples below q; samples equal to q's prefix (shared prefixes) widen the block
-    int64_t b = c;
-    for (; !bknown;) {
-        const bool v = b + gl < sz[0];
-        const ulonglong2 k = m.skey[0][v ? b + gl : 0];
-        const uint32_t same = gmask(v && k.x == q.hi && k.y == q.lo);
-        const int run = __ffs(~same) - 1;  // leading lanes equal to q's prefix
-        b += run;
-        if (run < kArity) break;
-    }
-    int64_t lo = c > 0 ? kFan * (c - 1) + 1 : 0;
-    const int64_t hi = min(n, kFan * b);
-    if (b == c && m.skey8) {
-        // Boundary 64(c-1) < q < boundary 64c (sample c's prefix is greater): the answer lies in one
-        // 64-boundary block.  Round one probes the starts of its eight 8-groups through skey8 (one
-        // 128-byte line, not eight); round two the seven keys after the last start below q (one
-        // line).  Prefix ties compare lengths / tails against the boundary itself (probe_cmp).
-        const int64_t B = c > 0 ? kFan * (c - 1) : 0;
-        const int64_t p8 = B + 8 * gl;
-        const bool v8 = p8 < hi;
-        int r8 = 1;
-        if (v8) r8 = probe(p8, &m.skey8[p8 / 8]);
-        const int k8 = __popc(gmask(v8 && r8 < 0));  // group starts below q
-        const int r_first = __shfl(r8, g0, 64);
-        if (k8 == 0) {  // c == 0 and q <= boundary 0
-            eq = hi > 0 && r_first == 0;
-            return 0;
-        }
-        const int64_t g = B + 8 * (k8 - 1);  // boundary g < q; the answer is in (g, min(g + 8, hi)]
-        const int64_t gend = min(g + 8, hi);
-        const int64_t pk = g + 1 + gl;
-        const bool vk = gl < 7 && pk < gend;
-        int rk = 1;
-        if (vk) rk = probe(pk, &h.key[pk]);
-        const int k1 = __popc(gmask(vk && rk < 0));
-        const int64_t lb = g + 1 + k1;
-        const int r_stop = __shfl(rk, g0 + (k1 < 7 ? k1 : 6), 64);
-        const int r_next = __shfl(r8, g0 + (k8 < kArity ? k8 : kArity - 1), 64);
-        if (lb < gend)
-            eq = r_stop == 0;  // the probe that stopped the count
-        else if (lb < hi)
-            eq = r_next == 0;  // lb = g + 8: the next group's start, probed in round one
-        return lb;
-    }
-    // lower_bound in [lo, lo + span]: rounds of kArity probes at a shrinking stride.  span <= 64
-    // normally; a long run of boundaries sharing q's 16-byte prefix (tuple keys) only starts the
-    // stride higher, so the lanes still compare tails side by side.
-    int64_t span = hi - lo;
-    int64_t stride0 = kFan / kArity;
-    while (stride0 * kArity < span) stride0 *= kArity;
-    bool eq_cand = false;  // cmp == 0 at the last probe that stopped a count (the answer, if < hi)
-    for (int64_t stride = stride0; span > 0; stride = stride > kArity ? stride / kArity : 1) {
-        const int64_t p = lo + stride * (gl + 1) - 1;
-        const bool v = stride * (gl + 1) <= span && p < hi;
-        int r = 1;
-        if (v) r = probe(p, &h.key[p]);
-        const uint32_t valid = gmask(v);
-        const int cnt = __popc(gmask(v && r < 0));
-        const int stop = __shfl(r, g0 + (cnt < kArity ? cnt : kArity - 1), 64);
-        if (cnt < __popc(valid)) eq_cand = stop == 0;  // lane cnt probed a key >= q
-        lo += stride * cnt;
-        span = cnt < __popc(valid) ? stride - 1 : span - stride * cnt;
-        if (stride == 1) break;
-    }
-    if (lo < hi) eq = eq_cand;
-    return lo;
-}
+// ------------------------------------------------------------------ range-max lookups and scans
 
 // Entry i of the top level (the max over its kL3Rep replicas).
 __device__ __forceinline__ int64_t l3_at(const int64_t* a, int64_t i) {
@@ -475,457 +150,6 @@ __device__ __forceinline__ bool tier_conflict(const Hist& h, const MaxLevels& m,
     // segments [ub-1, j): the one containing b (header if ub == 0) and boundaries in (b, e)
     if (ub == 0) return hdr > snap || range_max(m, 0, j, snap) > snap;
     return range_max(m, ub - 1, j, snap) > snap;
-}
-
-// ---- per-lane lookups (SkipList.cpp:426-458 + CheckMax :619-706, as the step-function rule of
-// SURVEY A.2)
-//
-// The history is the base tier overlaid by the delta tier; every delta version is >= the base
-// versions it covers (versions only grow), so the max over the overlay equals the max of the two
-// tiers' maxima, and holes (kHole) never conflict.
-//
-// One lane per lookup.  Round 3's cooperative lookups (group_lower_bound, still used by the
-// segment search of small batches) gave each lookup kArity lanes that load one node entry each,
-// so a wave served kArity lookups and the wave's instruction stream (ballots, shuffles, 64-bit
-// compares) was paid per kArity lookups: at C2 12,500 waves of ~350 VALU + ~260 SALU instructions
-// each, 77 % of their life waiting on loads (rocprofv3 SQ counters), the chip never holding all
-// of them at once.  Here a lane issues a whole node's (or directory slot's)
-// entries itself, up to kLaneProbe independent 16-byte loads in flight, and counts them in
-// registers: the same dependent rounds per lookup, 64 lookups per wave, every wave of a C2 batch
-// resident at once.
-constexpr int kLaneProbe = 16;  // entries one lane loads per round (a directory slot of two groups)
-
-// Number of the first cnt (<= N) entries of a[base, ...) whose 16-byte prefix is below q's, and
-// whether the first entry not below it has q's prefix (eq_next; false if all are below).
-template <int N>
-__device__ __forceinline__ int lane_count(const ulonglong2* a, int64_t base, int cnt, const DKey& q, bool& eq_next) {
-    ulonglong2 k[N];
-#pragma unroll
-    for (int i = 0; i < N; i++)
-        if (i < cnt) k[i] = a[base + i];
-    int c = 0;
-    eq_next = false;
-    bool stop = false;
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-        if (i < cnt && !stop) {
-            if (prefix_less(k[i], q)) {
-                c++;
-            } else {
-                stop = true;
-                eq_next = k[i].x == q.hi && k[i].y == q.lo;
-            }
-        }
-    }
-    return c;
-}
-
-// The level-0 samples of a tier below q's 16-byte prefix (c) and the end of the run of samples
-// sharing that prefix (b >= c), by one lane: the radix directory slot (at most kLaneProbe level-0
-// samples) or the kArity-ary sample tree, each node's entries loaded by the lane as independent
-// 16-byte loads.  Boundary 64(c-1) lies below q and boundary 64b (if any) above it.
-__device__ __forceinline__ void lane_sample_range(const MaxLevels& m, int64_t n, const DKey& q, int64_t& c_out,
-                                                  int64_t& b_out) {
-    int64_t sz[kIdxLevels];
-    sz[0] = (n + kFan - 1) / kFan;
-#pragma unroll
-    for (int L = 1; L < kIdxLevels; L++) sz[L] = (sz[L - 1] + kArity - 1) / kArity;
-    int top = 0;
-    while (top + 1 < kIdxLevels && sz[top] > kArity) top++;
-    int64_t c = 0;      // level-0 samples whose prefix is below q
-    bool bknown = false;  // the sample at c (if any) is known not to share q's prefix
-    bool direct = false;
-    int64_t w0 = -1, w1 = -1;  // a directory slot too wide to count at level 0
-    int64_t d8a, d8b;
-    if (dir_range8(m, q, d8a, d8b)) {
-        // the level-0 samples (every 8th skey8 entry) in q's slot: [d0, d1)
-        const int64_t d0 = (d8a + 7) >> 3, d1 = (d8b + 7) >> 3;
-        if (d1 - d0 <= kLaneProbe && d1 <= sz[0]) {
-            direct = true;
-            bool eqn;
-            const int cnt = (int)(d1 - d0);
-            const int k = lane_count<kLaneProbe>(m.skey[0], d0, cnt, q, eqn);
-            c = d0 + k;
-            // all of the slot below q: the next sample's first two bytes are greater
-            bknown = k < cnt ? !eqn : true;
-        } else if (d1 <= sz[0]) {
-            w0 = d0;
-            w1 = d1;
-        }
-    }
-    if (!direct) {
-        // A wide slot (keys whose directory bits take few values: C4's decimal digits after the
-        // shared prefix) still bounds q: samples before w0 lie below it and from w1 on above it, so
-        // the descent starts at the lowest level whose entries over [w0, w1) fit one probe round
-        // (entry j of level L is sample j A^L) instead of at the top.
-        int lv = top;
-        bool started = false;
-        if (w0 >= 0) {
-            int64_t span = 1;
-            for (int L = 1; L < top; L++) {
-                span *= kArity;
-                const int64_t a = w0 / span, z = (w1 - 1) / span;
-                if (z - a + 1 <= kLaneProbe) {
-                    bool eqn;
-                    c = a + lane_count<kLaneProbe>(m.skey[L], a, (int)(z - a + 1), q, eqn);
-                    lv = L;
-                    started = true;
-                    break;
-                }
-            }
-        }
-        for (int64_t j0 = 0; !started && j0 < sz[top]; j0 += kArity) {
-            const int cnt = (int)min((int64_t)kArity, sz[top] - j0);
-            bool eqn;
-            const int k = lane_count<kArity>(m.skey[top], j0, cnt, q, eqn);
-            if (top == 0 && k < cnt) bknown = !eqn;
-            c += k;
-            if (k < cnt) break;
-        }
-        for (int L = lv; L > 0; L--) {
-            if (c == 0) continue;  // nothing below q at this level: nothing below it underneath either
-            const int64_t base = (int64_t)kArity * (c - 1) + 1;
-            const int64_t end = min((int64_t)kArity * c, sz[L - 1]);
-            bool eqn;
-            const int cnt = (int)(end - base);
-            const int k = lane_count<kArity>(m.skey[L - 1], base, cnt, q, eqn);
-            if (L == 1 && k < cnt) bknown = !eqn;
-            c = base + k;
-        }
-    }
-    // samples sharing q's prefix widen the block
-    int64_t b = c;
-    while (!bknown && b < sz[0]) {
-        const ulonglong2 k = m.skey[0][b];
-        if (k.x != q.hi || k.y != q.lo) break;
-        b++;
-    }
-    c_out = c;
-    b_out = b;
-}
-
-// std::lower_bound of q over the n boundaries of a tier by one lane (the result and eq as
-// group_lower_bound's): lane_sample_range down to one 64-boundary block, then the block's eight
-// group starts (skey8) and the seven boundaries after the last start below q; prefix ties compare
-// lengths and tails against the boundary itself (probe_cmp_lean).  A run of boundaries sharing q's
-// 16-byte prefix over more than one block (tuple subspaces) falls back to a binary search.
-__device__ __forceinline__ int64_t lane_lower_bound(const Hist& h, const MaxLevels& m, int64_t n, const DKey& q,
-                                                    const uint8_t* htail, const uint8_t* qtail, bool& eq) {
-    eq = false;
-    if (n <= 0) return 0;
-    // Directory slot of at most kLaneProbe skey8 entries (C2: ~10 per slot of the base, ~2 of the
-    // delta): the group starts of q's slot are probed at once, so the lookup takes three dependent
-    // rounds (directory, group starts, the seven boundaries after the last start below q) instead
-    // of four (the level-0 samples first).  Entries before the slot lie below q, entries past it
-    // above q (dir_range8); prefix ties compare against the boundary itself (probe_cmp_lean).
-    int64_t d8a, d8b;
-    const int64_t n8 = (n + 7) >> 3;
-    if (dir_range8(m, q, d8a, d8b) && d8b - d8a <= kLaneProbe && d8b <= n8) {
-        const int cnt = (int)(d8b - d8a);
-        ulonglong2 s8[kLaneProbe];
-#pragma unroll
-        for (int i = 0; i < kLaneProbe; i++)
-            if (i < cnt) s8[i] = m.skey8[d8a + i];
-        int r8[kLaneProbe];
-        int k8 = 0;
-        bool stop = false;
-#pragma unroll
-        for (int i = 0; i < kLaneProbe; i++) {
-            r8[i] = 1;
-            if (i < cnt && !stop) {
-                r8[i] = probe_cmp_lean(h, 8 * (d8a + i), s8[i], htail, q, qtail);
-                if (r8[i] < 0) k8++; else stop = true;
-            }
-        }
-        const int64_t g = d8a + k8 - 1;  // the last group start below q (-1: none)
-        if (g < 0) {                     // q <= boundary 0 (probed when the slot holds entry 0)
-            eq = cnt > 0 && r8[0] == 0;
-            return 0;
-        }
-        const int64_t B = 8 * g, gend = min(B + 8, n);
-        const int nk = (int)(gend - B - 1);
-        ulonglong2 kk[7];
-#pragma unroll
-        for (int i = 0; i < 7; i++)
-            if (i < nk) kk[i] = h.key[B + 1 + i];
-        int k1 = 0, r_stop = 1;
-        stop = false;
-#pragma unroll
-        for (int i = 0; i < 7; i++) {
-            if (i < nk && !stop) {
-                const int r = probe_cmp_lean(h, B + 1 + i, kk[i], htail, q, qtail);
-                if (r < 0) {
-                    k1++;
-                } else {
-                    stop = true;
-                    r_stop = r;
-                }
-            }
-        }
-        const int64_t lb = B + 1 + k1;
-        if (lb < gend)
-            eq = r_stop == 0;
-        else if (lb < n)  // lb = 8(g + 1): the next group start, probed above unless past the slot
-            eq = k8 < cnt && r8[k8] == 0;
-        return lb;
-    }
-    int64_t c, b;
-    lane_sample_range(m, n, q, c, b);
-    const int64_t hi = min(n, kFan * b);
-    if (b == c) {
-        // boundary 64(c-1) < q < boundary 64c: one 64-boundary block; its group starts, then the
-        // boundaries after the last start below q
-        const int64_t B = c > 0 ? kFan * (c - 1) : 0;
-        const int n8 = (int)min((int64_t)8, (hi - B + 7) / 8);  // group starts below hi
-        ulonglong2 s8[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++)
-            if (i < n8) s8[i] = m.skey8[B / 8 + i];
-        int r8[8];
-        int k8 = 0;
-        bool stop = false;
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            r8[i] = 1;
-            if (i < n8 && !stop) {
-                r8[i] = probe_cmp_lean(h, B + 8 * i, s8[i], htail, q, qtail);
-                if (r8[i] < 0) k8++; else stop = true;
-            }
-        }
-        if (k8 == 0) {  // c == 0 and q <= boundary 0
-            eq = hi > 0 && r8[0] == 0;
-            return 0;
-        }
-        const int64_t g = B + 8 * (k8 - 1);  // boundary g < q; the answer lies in (g, min(g + 8, hi)]
-        const int64_t gend = min(g + 8, hi);
-        const int nk = (int)(gend - g - 1);
-        ulonglong2 kk[7];
-#pragma unroll
-        for (int i = 0; i < 7; i++)
-            if (i < nk) kk[i] = h.key[g + 1 + i];
-        int k1 = 0;
-        int r_stop = 1;
-        stop = false;
-#pragma unroll
-        for (int i = 0; i < 7; i++) {
-            if (i < nk && !stop) {
-                const int r = probe_cmp_lean(h, g + 1 + i, kk[i], htail, q, qtail);
-                if (r < 0) {
-                    k1++;
-                } else {
-                    stop = true;
-                    r_stop = r;
-                }
-            }
-        }
-        const int64_t lb = g + 1 + k1;
-        if (lb < gend)
-            eq = r_stop == 0;
-        else if (lb < hi)
-            eq = k8 < 8 && r8[k8] == 0;  // lb = g + 8: the next group's start, probed above
-        return lb;
-    }
-    // a run of boundaries sharing q's prefix across blocks: binary search with full compares
-    int64_t lo = c > 0 ? kFan * (c - 1) + 1 : 0, hh = hi;
-    while (lo < hh) {
-        const int64_t mid = (lo + hh) >> 1;
-        const int r = hist_cmp(h, mid, htail, q, qtail);
-        if (r < 0) {
-            lo = mid + 1;
-        } else {
-            hh = mid;
-            eq = r == 0;
-        }
-    }
-    if (lo >= hi) eq = false;
-    return lo;
-}
-
-// ---- per-lane lookups of long keys (batches with keys over 24 bytes: C4 tuple keys)
-//
-// Keys of one tuple subspace / user share their 16-byte prefix, so a lookup that reaches their run
-// compares tails.  One lane per lookup, in three steps: lane_sample_range; the run [s, e) of
-// boundaries sharing q's prefix, by prefix-only counts (the group starts of skey8, then the seven
-// boundaries after a start: no tails); inside the run a (kRunProbes + 1)-ary search by full
-// compares, whose probes' (len, tail offset) and then tails are loaded together against the query
-// tail held in registers (QTail): two dependent loads per round.  Keys between two probes share
-// with q at least the tail words both probes share with it, so later rounds load and compare only
-// the words from there on (C4: the item bytes after a user's ~20-85 shared bytes).
-#ifndef FDBCS_RUN_PROBES
-#define FDBCS_RUN_PROBES 3
-#endif
-[[maybe_unused]] constexpr int kRunProbes = FDBCS_RUN_PROBES;
-
-// Boundaries of [lo1, hi) whose prefix is below q's, counted among the n <= N from `base` (sorted).
-template <int N>
-__device__ __forceinline__ int lane_count_below(const ulonglong2* a, int64_t base, int n, const DKey& q, bool not_above) {
-    ulonglong2 k[N];
-#pragma unroll
-    for (int i = 0; i < N; i++)
-        if (i < n) k[i] = a[base + i];
-    int c = 0;
-#pragma unroll
-    for (int i = 0; i < N; i++)
-        if (i < n) c += (not_above ? !(q.hi < k[i].x || (q.hi == k[i].x && q.lo < k[i].y)) : prefix_less(k[i], q)) ? 1 : 0;
-    return c;
-}
-
-// The run of boundaries of [lo1, hi) sharing q's 16-byte prefix: s = the first whose prefix is not
-// below q's, e = the first whose prefix is above it (hi if none).  Boundaries before lo1 lie below
-// q's prefix, hi and after it above.
-__device__ __forceinline__ void lane_prefix_run(const Hist& h, const MaxLevels& m, int64_t lo1, int64_t hi,
-                                                const DKey& q, int64_t& s, int64_t& e) {
-    const int64_t G0 = (lo1 + 7) / 8;                           // group starts 8g in [lo1, hi)
-    const int64_t NG = hi > 8 * G0 ? (hi - 1) / 8 - G0 + 1 : 0;
-    if (NG > kLaneProbe) {  // a run over several blocks (a hot subspace): binary searches on prefixes
-        int64_t lo = lo1, hh = hi;
-        while (lo < hh) {
-            const int64_t mid = (lo + hh) >> 1;
-            if (prefix_less(h.key[mid], q)) lo = mid + 1; else hh = mid;
-        }
-        s = lo;
-        hh = hi;
-        while (lo < hh) {
-            const int64_t mid = (lo + hh) >> 1;
-            const ulonglong2 k = h.key[mid];
-            if (!(q.hi < k.x || (q.hi == k.x && q.lo < k.y))) lo = mid + 1; else hh = mid;
-        }
-        e = lo;
-        return;
-    }
-    ulonglong2 g[kLaneProbe];
-#pragma unroll
-    for (int i = 0; i < kLaneProbe; i++)
-        if (i < NG) g[i] = m.skey8[G0 + i];
-    int kl = 0, kle = 0;
-#pragma unroll
-    for (int i = 0; i < kLaneProbe; i++) {
-        if (i < NG) {
-            kl += prefix_less(g[i], q) ? 1 : 0;
-            kle += (q.hi < g[i].x || (q.hi == g[i].x && q.lo < g[i].y)) ? 0 : 1;
-        }
-    }
-    // s lies in [as, bs], e in [ae, be]: at most seven boundaries after a group start each
-    const int64_t as = kl > 0 ? 8 * (G0 + kl - 1) + 1 : lo1, bs = kl < NG ? 8 * (G0 + kl) : hi;
-    const int64_t ae = kle > 0 ? 8 * (G0 + kle - 1) + 1 : lo1, be = kle < NG ? 8 * (G0 + kle) : hi;
-    ulonglong2 ks[7], ke[7];
-    const int ns = (int)(bs - as), ne = (int)(be - ae);
-#pragma unroll
-    for (int i = 0; i < 7; i++) {
-        if (i < ns) ks[i] = h.key[as + i];
-        if (i < ne) ke[i] = h.key[ae + i];
-    }
-    int cs = 0, ce = 0;
-#pragma unroll
-    for (int i = 0; i < 7; i++) {
-        if (i < ns) cs += prefix_less(ks[i], q) ? 1 : 0;
-        if (i < ne) ce += (q.hi < ke[i].x || (q.hi == ke[i].x && q.lo < ke[i].y)) ? 0 : 1;
-    }
-    s = as + cs;
-    e = ae + ce;
-}
-
-// lane_lower_bound for long keys (same result and eq); qt: q's tail words (load_qtail).  RP: probes
-// per round inside a prefix run (more per round made k_seg_prep's few, latency-bound lookups slower
-// at C4: 37.7 / 41.4 / 42.9 us at 3 / 5 / 7).
-template <int RP = kRunProbes>
-__device__ __forceinline__ int64_t lane_lower_bound_long(const Hist& h, const MaxLevels& m, int64_t n, const DKey& q,
-                                                         const QTail& qt, const uint8_t* htail, const uint8_t* qtail,
-                                                         bool& eq) {
-    eq = false;
-    if (n <= 0) return 0;
-    int64_t c, b;
-    lane_sample_range(m, n, q, c, b);
-    int64_t lo, hh;
-    lane_prefix_run(h, m, c > 0 ? kFan * (c - 1) + 1 : 0, min(n, kFan * b), q, lo, hh);
-#if defined(__HIP_DEVICE_COMPILE__)
-    // [lo, hh): boundaries sharing q's prefix, lower_bound among them by full compares.  dlo / dhi:
-    // tail words known equal to q's in the boundaries just below lo and at hh (none at first: their
-    // prefixes differ from q's).
-    int dlo = 0, dhi = 0;
-    bool eq_hh = false;  // the boundary at hh equals q (hh was set by a probe)
-    const bool qlong = q.len > 16u;
-    while (lo < hh) {
-        const int64_t span = hh - lo;
-        const int w0 = dlo < dhi ? dlo : dhi;  // tail words every boundary in [lo, hh) shares with q
-        int64_t p[RP];
-        bool v[RP];
-        uint2 lt[RP];
-#pragma unroll
-        for (int j = 0; j < RP; j++) {
-            p[j] = lo + (span * (j + 1)) / (RP + 1);
-            v[j] = p[j] < hh && (j == 0 || p[j] != p[j - 1]);
-            if (v[j]) lt[j] = h.lt[p[j]];
-        }
-        uint64_t x[RP][kQW];
-        uint32_t nb[RP];
-#pragma unroll
-        for (int j = 0; j < RP; j++) {
-            nb[j] = v[j] && qlong && lt[j].x > 16u ? (lt[j].x < q.len ? lt[j].x : q.len) - 16u : 0u;
-            const uint64_t* ha = (const uint64_t*)hist_tail(htail, v[j] ? lt[j].y : 0u);
-            const int nw = (int)((nb[j] + 7u) / 8u);
-#pragma unroll
-            for (int u = 0; u < kQW; u++)
-                if (u >= w0 && u < nw) x[j][u] = ha[u];
-        }
-        int r[RP], d[RP];
-#pragma unroll
-        for (int j = 0; j < RP; j++) {
-            r[j] = 1;
-            d[j] = 0;
-            if (!v[j]) continue;
-            const int nw = (int)((nb[j] + 7u) / 8u);
-            bool found = false;
-#pragma unroll
-            for (int u = 0; u < kQW; u++) {
-                if (!found && u >= w0 && u < nw) {
-                    const int vb = (int)nb[j] - 8 * u;
-                    const uint64_t msk = vb >= 8 ? ~0ull : ~0ull << (64 - 8 * vb);
-                    const uint64_t hx = __builtin_bswap64(x[j][u]) & msk, qy = qt.w[u] & msk;
-                    if (hx != qy) {
-                        r[j] = hx < qy ? -1 : 1;
-                        d[j] = u;
-                        found = true;
-                    }
-                }
-            }
-            if (!found) {
-                if (nw > kQW) {  // both tails run past the registers: the rest from memory
-                    r[j] = tail_cmp(hist_tail(htail, lt[j].y) + 8 * kQW, lt[j].x - 8 * kQW, qtail + q.tail + 8 * kQW,
-                                    q.len - 8 * kQW);
-                    d[j] = kQW;
-                } else {
-                    r[j] = (lt[j].x > q.len) - (lt[j].x < q.len);
-                    d[j] = (int)(nb[j] / 8u);
-                }
-            }
-        }
-        // the probes below q form a prefix of the valid ones
-        int64_t nlo = lo, nhh = hh;
-        int ndlo = dlo, ndhi = dhi;
-        bool neq = eq_hh, hit = false;
-#pragma unroll
-        for (int j = 0; j < RP; j++) {
-            if (!v[j] || hit) continue;
-            if (r[j] < 0) {
-                nlo = p[j] + 1;
-                ndlo = d[j];
-            } else {
-                nhh = p[j];
-                ndhi = d[j];
-                neq = r[j] == 0;
-                hit = true;
-            }
-        }
-        lo = nlo;
-        hh = nhh;
-        dlo = ndlo;
-        dhi = ndhi;
-        eq_hh = neq;
-    }
-    eq = eq_hh;
-#endif
-    return lo;
 }
 
 // Does the read [kb, ke) (degenerate: [kb, kb)) meet a union segment of the previous batch, i.e.
@@ -3550,15 +2774,10 @@ __global__ __launch_bounds__(kBlock) void k_compact_search(Hist base, MaxLevels 
     const int64_t nd = *nd_ptr;
     if (j >= nd) return;
     const int64_t nb = *nb_ptr;
-    const ulonglong2 k = delta.key[j];
-    const uint2 lt = delta.lt[j];
     DKey q;
-    q.hi = k.x;
-    q.lo = k.y;
-    q.len = lt.x;
-    q.tail = 0;  // the query's tail arena below starts at its own tail
+    const uint8_t* qtail;
+    tier_query(delta, j, htail, q, qtail);
     bool exact;
-    const uint8_t* qtail = hist_tail(htail, lt.y);
     int64_t lo;
     if constexpr (MODE == 1) {
         lo = lane_lower_bound(base, basem, nb, q, htail, qtail, exact);
@@ -3624,12 +2843,9 @@ void launch_compact(hipStream_t s, const Work& w, const Hist& base, const MaxLev
                     hipEvent_t copy_end, int mode, int base_tile, bool nt) {
     int64_t blocks = (delta_hint_n + kBlock - 1) / kBlock;
     if (blocks < 1) blocks = 1;
-    if (mode == 1)
-        fdb_launch(k_compact_search<1>, dim3((unsigned)blocks), dim3(kBlock), 0, s, base, basem, delta, htail,
-                   &sc->n, &sc->nd_next, header_version, w, basem.lvl[3], lvl3_n, basem.lvl[2], lvl2_n);
-    else
-        fdb_launch(k_compact_search<2>, dim3((unsigned)blocks), dim3(kBlock), 0, s, base, basem, delta, htail,
-                   &sc->n, &sc->nd_next, header_version, w, basem.lvl[3], lvl3_n, basem.lvl[2], lvl2_n);
+    fdb_launch(search_mode_kernel(mode, k_compact_search<1>, k_compact_search<2>), dim3((unsigned)blocks), dim3(kBlock),
+               0, s, base, basem, delta, htail, &sc->n, &sc->nd_next, header_version, w, basem.lvl[3], lvl3_n,
+               basem.lvl[2], lvl2_n);
     const Segs g{w.c_lo, w.c_hi, w.c_rem, w.c_ins, w.tile_first};
     const TierIO io{&sc->n, &sc->n_next, &sc->c_before, &sc->c_rem};
     const int tile = base_tile == 1024 || base_tile == 2048 ? base_tile : kBaseTile;
@@ -4464,868 +3680,6 @@ void launch_epilogue(hipStream_t s, const BatchDev& b, const Work& w, const MaxL
     else
         fdb_launch(k_epilogue<false>, dim3((unsigned)epilogue_grid(grid_hint_n, extra)), dim3(kEpiThreads), 0, s, m, sc,
                    (const int64_t*)nullptr, ep);
-}
-
-// ------------------------------------------------------------------ history export
-//
-// The canonical description of H_f(k) = the version a read of k sees (delta entry unless kHole, else
-// base entry, else the header), clamped to floor - 1 below the floor, over (lo, hi): the keys where
-// it changes, with their new values, in the layout fdbcs_load_history takes.  Read-only: nothing of
-// the set, its levels, index, directories, Scalars or batch workspaces is written.
-//
-// Both tiers' boundaries in key order form one merged stream (on equal keys the delta's first).  H at
-// every stream element is known from the element and the delta boundary covering it, and an element
-// is kept when its clamped value differs from its predecessor's: base boundaries hidden under a
-// written delta segment, the second of two equal keys and runs the floor made equal all repeat their
-// predecessor's value, so no case is special.
-//   k_export_search  one lane per delta boundary j: lower bound lb in the base (the compaction's
-//                    search, without its side effects) -> stream position j + lb, and H(d_j)
-//   k_export_bounds  stream positions of lo and hi by plain binary searches, and the header H_f(lo)
-//   k_export_tile_starts  per scan tile, the delta boundaries below its first element (one thread each)
-//   k_export_scan    per 1024-element tile of the stream: the delta positions the tile can meet are
-//                    staged in LDS (consecutive elements meet consecutive delta boundaries), every
-//                    element is resolved to its source and clamped value there, then flagged and
-//                    scanned (scan.h look-back) and the kept ones written.
-// Key bytes are scanned as three 32-bit components, kept count c, bytes mod 2^32 a, and sum of
-// (len >> 3) b: a prefix P lies in [8 b, 8 b + 7 c] and is congruent to a, which determines it while
-// 7 c < 2^32 and b < 2^32: exact 64-bit offsets below 2^29 boundaries and 32 GiB of key bytes (the
-// host refuses an export that could pass either).
-
-__device__ __forceinline__ int64_t export_prefix64(uint32_t a, uint32_t b) {
-    const uint64_t lower = 8ull * b;
-    return (int64_t)(lower + (uint32_t)(a - (uint32_t)lower));
-}
-
-__device__ __forceinline__ int64_t export_clamp(int64_t v, int64_t floor) {
-    return (floor == kHole || v >= floor) ? v : floor - 1;
-}
-
-template <int MODE>
-__global__ __launch_bounds__(kBlock) void k_export_search(Hist base, MaxLevels basem, Hist delta,
-                                                          const uint8_t* htail, int64_t nb, int64_t nd, int64_t hdr,
-                                                          int64_t* d_pos, int64_t* d_val) {
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= nd) return;
-    const ulonglong2 k = delta.key[j];
-    const uint2 lt = delta.lt[j];
-    DKey q;
-    q.hi = k.x;
-    q.lo = k.y;
-    q.len = lt.x;
-    q.tail = 0;  // the query's tail arena below starts at its own tail
-    bool exact = false;
-    const uint8_t* qtail = hist_tail(htail, lt.y);
-    int64_t lb;
-    if constexpr (MODE == 1) {
-        lb = lane_lower_bound(base, basem, nb, q, htail, qtail, exact);
-    } else {
-        QTail qt;
-        load_qtail(qt, q, qtail);
-        lb = lane_lower_bound_long(base, basem, nb, q, qt, htail, qtail, exact);
-    }
-    const int64_t dv = delta.ver[j];
-    d_pos[j] = j + lb;
-    // a hole takes the base value at its key: the base boundary there, or the one covering it
-    d_val[j] = dv != kHole ? dv : exact ? base.ver[lb] : lb > 0 ? base.ver[lb - 1] : hdr;
-}
-
-// Boundaries of a tier below q (upper: or equal to it).
-__device__ __forceinline__ int64_t export_bound(const Hist& h, int64_t n, const uint8_t* htail, const DKey& q,
-                                                const uint8_t* qtail, bool upper) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        const int c = hist_cmp(h, mid, htail, q, qtail);
-        if (c < 0 || (upper && c == 0))
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    return lo;
-}
-
-__global__ __launch_bounds__(64) void k_export_bounds(ExportArgs a) {
-    __shared__ int64_t r[4];  // boundaries <= lo in base, delta; boundaries < hi in base, delta
-    const int t = threadIdx.x;
-    if (t < 4) {
-        const bool is_hi = t >= 2, is_delta = t & 1;
-        const int64_t n = is_delta ? a.nd : a.nb;
-        if (is_hi ? a.has_hi : a.has_lo)
-            r[t] = export_bound(is_delta ? a.delta : a.base, n, a.htail, is_hi ? a.hi : a.lo, a.btail, !is_hi);
-        else
-            r[t] = is_hi ? n : 0;
-    }
-    __syncthreads();
-    if (t != 0) return;
-    int64_t h = a.hdr;
-    if (r[0] > 0) h = a.base.ver[r[0] - 1];
-    if (r[1] > 0) {
-        const int64_t dv = a.delta.ver[r[1] - 1];
-        if (dv != kHole) h = dv;
-    }
-    const int64_t m_lo = r[0] + r[1], m_hi = r[2] + r[3];
-    a.words[kXwLo] = m_lo;
-    a.words[kXwHi] = m_hi > m_lo ? m_hi : m_lo;
-    a.words[kXwHeader] = export_clamp(h, a.floor);
-}
-
-// Write the n bytes of a key, given as little-endian 8-byte words get(0 .. nw - 1) in key order, to
-// d (any alignment): bytes up to d's next 8-byte line, whole words, then the rest.
-template <class G>
-__device__ __forceinline__ void export_put_key(uint8_t* d, uint32_t n, uint32_t nw, const G& get) {
-    uint32_t head = (uint32_t)((8u - ((uintptr_t)d & 7u)) & 7u);
-    if (head > n) head = n;
-    uint64_t cur = nw ? get(0u) : 0ull;
-    for (uint32_t b = 0; b < head; b++) d[b] = (uint8_t)(cur >> (8u * b));
-    const uint32_t sh = 8u * head, nfull = (n - head) >> 3;
-    uint64_t* dw = (uint64_t*)(d + head);
-    for (uint32_t q = 0; q < nfull; q++) {
-        const uint64_t next = q + 1u < nw ? get(q + 1u) : 0ull;
-        dw[q] = sh ? (cur >> sh) | (next << (64u - sh)) : cur;
-        cur = next;
-    }
-    for (uint32_t b = head + 8u * nfull; b < n; b++) d[b] = (uint8_t)(get(b >> 3) >> (8u * (b & 7u)));
-}
-
-// Per scan tile: the delta boundaries below the first stream element the tile resolves (its
-// predecessor; tile 0: its first element).  One thread per tile, so the binary searches of all tiles
-// run side by side instead of one per workgroup at the head of its tile.
-__global__ __launch_bounds__(kBlock) void k_export_tile_starts(ExportArgs a) {
-    const int64_t tile = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t m_lo = a.words[kXwLo], n = a.words[kXwHi] - m_lo;
-    const int64_t ntiles = n > 0 ? (n + kScanTile - 1) / kScanTile : 1;
-    if (tile >= ntiles) return;
-    const int64_t mfirst = m_lo + tile * kScanTile - (tile > 0 ? 1 : 0);
-    int64_t tb = 0, th = a.nd;
-    while (tb < th) {
-        const int64_t mid = tb + (th - tb) / 2;
-        if (a.d_pos[mid] < mfirst)
-            tb = mid + 1;
-        else
-            th = mid;
-    }
-    a.tile_tb[tile] = tb;
-}
-
-constexpr int kExpWin = kScanTile + 2;  // delta boundaries a tile and its predecessor can meet, and one past
-
-struct ExportScan {
-    ExportArgs a;
-    const int64_t* s_val;  // LDS: clamped value of the tile's predecessor, then of its elements
-    const int64_t* s_src;  // LDS: source of each element: base boundary i, or ~j for delta boundary j
-    int64_t tile0;         // the tile's first element
-    int* err;              // the export's error word
-    __device__ bool keep(int e) const { return s_val[e + 1] != s_val[e]; }
-    __device__ void load(int64_t i, uint32_t (&v)[3]) const {
-        const int e = (int)(i - tile0);
-        uint32_t len = 0;
-        const bool kp = keep(e);
-        if (kp) {
-            const int64_t src = s_src[e];
-            len = src >= 0 ? a.base.lt[src].x : a.delta.lt[~src].x;
-        }
-        v[0] = kp ? 1u : 0u;
-        v[1] = len;
-        v[2] = len >> 3;
-    }
-    __device__ void store(int64_t i, const uint32_t (&ex)[3]) const {
-        const int e = (int)(i - tile0);
-        if (!keep(e)) return;
-        const int64_t o = ex[0], P = export_prefix64(ex[1], ex[2]);
-        const int64_t src = s_src[e];
-        const Hist& h = src >= 0 ? a.base : a.delta;
-        const int64_t p = src >= 0 ? src : ~src;
-        const ulonglong2 k = h.key[p];
-        const uint2 lt = h.lt[p];
-        a.versions[o] = s_val[e + 1];
-        a.offsets[o] = P;
-        if (P + (int64_t)lt.x > a.bytes_cap) {  // never past the result buffer (the host sized it for every key)
-            atomicOr(err, 8);
-            return;
-        }
-        // the prefix words are big-endian: swapped back, the key's first byte is the lowest
-        const uint64_t w0 = __builtin_bswap64(k.x), w1 = __builtin_bswap64(k.y);
-        const uint64_t* tw = (const uint64_t*)hist_tail(a.htail, lt.x > 16u ? lt.y : 0u);
-        export_put_key(a.bytes + P, lt.x, (lt.x + 7u) >> 3,
-                       [&](uint32_t q) { return q == 0u ? w0 : q == 1u ? w1 : tw[q - 2u]; });
-    }
-    __device__ void finish(const uint32_t (&tot)[3]) const {
-        const int64_t P = export_prefix64(tot[1], tot[2]);
-        a.words[kXwN] = tot[0];
-        a.words[kXwBytes] = P;
-        a.offsets[tot[0]] = P;
-    }
-};
-
-__global__ __launch_bounds__(kScanThreads) void k_export_scan(ExportArgs a, ScanState st) {
-    __shared__ uint32_t sv[3][kScanPad];
-    __shared__ uint32_t swave[3][kScanThreads / 64];
-    __shared__ uint32_t sbase[3];
-    __shared__ int s_tile;
-    __shared__ int64_t s_pos[kExpWin];
-    __shared__ int64_t s_val[kScanTile + 1];
-    __shared__ int64_t s_src[kScanTile];
-    const int64_t m_lo = a.words[kXwLo], n = a.words[kXwHi] - m_lo;
-    if (threadIdx.x == 0) s_tile = atomicAdd(st.counter, 1);
-    __syncthreads();
-    const int tile = s_tile;
-    const int64_t ntiles = n > 0 ? (n + kScanTile - 1) / kScanTile : 1;
-    if (tile >= ntiles) return;
-    const int64_t tile0 = (int64_t)tile * kScanTile;
-    // stream elements resolved here: the tile's, and before them its predecessor (tile 0: the header)
-    const int pre = tile > 0 ? 1 : 0;
-    const int64_t mfirst = m_lo + tile0 - pre;
-    int64_t rest = n - tile0;
-    const int cnt = (int)(rest < kScanTile ? rest : kScanTile) + pre;
-    // delta boundaries below the first element (k_export_tile_starts); the next kExpWin positions cover
-    // every element's search: positions ascend strictly, so window entry q lies at mfirst + q or later
-    const int64_t tb = a.tile_tb[tile];
-    for (int q = threadIdx.x; q < kExpWin; q += kScanThreads) s_pos[q] = tb + q < a.nd ? a.d_pos[tb + q] : LLONG_MAX;
-    __syncthreads();
-    for (int k = threadIdx.x; k < cnt; k += kScanThreads) {
-        const int64_t m = mfirst + k;
-        int l = 0, h = kExpWin;  // window entries at or below m
-        while (l < h) {
-            const int mid = (l + h) >> 1;
-            if (s_pos[mid] <= m)
-                l = mid + 1;
-            else
-                h = mid;
-        }
-        const int64_t t = tb + l;  // delta boundaries at or below element m: t - 1 covers it
-        int64_t v, src;
-        if (l > 0 && s_pos[l - 1] == m) {
-            src = ~(t - 1);
-            v = a.d_val[t - 1];
-        } else {
-            src = m - t;
-            if (src < 0 || src >= a.nb) {  // positions out of order: never index past the tier
-                atomicOr(st.error, 4);
-                src = a.nb > 0 ? 0 : ~(int64_t)0;
-            }
-            const int64_t dv = t > 0 ? a.delta.ver[t - 1] : kHole;
-            v = dv != kHole ? dv : src >= 0 ? a.base.ver[src] : a.hdr;
-        }
-        const int slot = k + 1 - pre;
-        s_val[slot] = export_clamp(v, a.floor);
-        if (slot > 0) s_src[slot - 1] = src;
-    }
-    if (tile == 0 && threadIdx.x == 0) s_val[0] = a.words[kXwHeader];
-    __syncthreads();
-    const ExportScan f{a, s_val, s_src, tile0, st.error};
-    scan_tile<3>(f, n, tile, ntiles, st, sv, swave, sbase);
-}
-
-int64_t export_tiles(int64_t n) { return n > 0 ? (n + kScanTile - 1) / kScanTile : 1; }
-
-void launch_export(hipStream_t s, const ExportArgs& a, const MaxLevels& basem, uint64_t* granules, int mode) {
-    if (a.nd > 0) {
-        const dim3 grid((unsigned)((a.nd + kBlock - 1) / kBlock));
-        if (mode == 1)
-            fdb_launch(k_export_search<1>, grid, dim3(kBlock), 0, s, a.base, basem, a.delta, a.htail, a.nb, a.nd, a.hdr,
-                       a.d_pos, a.d_val);
-        else
-            fdb_launch(k_export_search<2>, grid, dim3(kBlock), 0, s, a.base, basem, a.delta, a.htail, a.nb, a.nd, a.hdr,
-                       a.d_pos, a.d_val);
-    }
-    fdb_launch(k_export_bounds, dim3(1), dim3(64), 0, s, a);
-    const int64_t tiles = export_tiles(a.nb + a.nd);
-    fdb_launch(k_export_tile_starts, dim3((unsigned)((tiles + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, a);
-    ScanState st;
-    st.granules = granules;
-    st.counter = (int*)&a.words[kXwScan];
-    st.error = st.counter + 1;
-    fdb_launch(k_export_scan, dim3((unsigned)tiles), dim3(kScanThreads), 0, s, a, st);
-}
-
-// ------------------------------------------------------------------ iops sample
-//
-// The resolver's iopsSample (Resolver.actor.cpp:178-192) of a routed batch: the begin key of every
-// range the resolver kept, TooOld sub-transactions' included, is rolled with
-// TransientStorageMetricSample::add's odds (StorageMetrics.actor.h: metric / metricUnitsPerSample,
-// a metric at or above the unit always) and the sampled ones are handed to the host.  The roll is a
-// counter-based one, so that the host can restate it bit for bit (balancing.iops_roll): range i
-// (read r: r, write w: R + w) under the caller's seed takes the top 32 bits u of splitmix64's
-// finalizer over seed + 0x9E3779B97F4A7C15 (i + 1) and is sampled iff u * units < metric << 32.
-// One launch: a look-back scan with one element per thread (a kept element's store is a chain of
-// dependent loads, as the other gather scans') over two counters, the kept ranges and their key
-// bytes (32-bit: the host refuses capacities whose keys could pass 2^32 bytes).  R and W come from
-// the routing's device result; the grid is sized by the capacities, spare tiles leave at once.
-
-__device__ __forceinline__ uint32_t iops_mix(uint64_t seed, uint64_t i) {
-    uint64_t z = seed + 0x9E3779B97F4A7C15ull * (i + 1);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z = z ^ (z >> 31);
-    return (uint32_t)(z >> 32);
-}
-
-struct IopsScan {
-    IopsArgs a;
-    int* err;
-    static constexpr bool kOwn = true;
-    // [0] sampled ranges, [1] their begin keys' bytes
-    __device__ void load(int64_t i, uint32_t (&v)[2]) const {
-        const uint32_t len = a.keys[2 * i].len;
-        const uint64_t metric = kIopsOffsetPerKey + (uint64_t)len;
-        const bool hit = metric >= a.units || (uint64_t)iops_mix(a.seed, (uint64_t)i) * a.units < (metric << 32);
-        v[0] = hit ? 1u : 0u;
-        v[1] = hit ? len : 0u;
-    }
-    __device__ void store(int64_t i, const uint32_t (&ex)[2], const uint32_t (&own)[2]) const {
-        if (!own[0]) return;
-        const int64_t o = ex[0], P = ex[1];
-        const DKey k = a.keys[2 * i];
-        const uint64_t metric = kIopsOffsetPerKey + (uint64_t)k.len;
-        a.metrics[o] = (int32_t)(metric >= a.units ? metric : a.units);
-        a.index[o] = (int32_t)i;
-        a.key_offsets[o] = P;
-        if (P + (int64_t)k.len > a.bytes_cap) {  // never past the result buffer (the host sized it for every key)
-            atomicOr(err, 8);
-            return;
-        }
-        // the prefix words are big-endian: swapped back, the key's first byte is the lowest; the
-        // tail starts at any byte of the batch's arena (k_route_write packs them), so a tail word is
-        // cut from the two aligned words that hold it (the arena's slack covers the second)
-        const uint64_t w0 = __builtin_bswap64(k.hi), w1 = __builtin_bswap64(k.lo);
-        const uint8_t* tp = a.tail + (k.len > 16u ? k.tail : 0u);
-        export_put_key(a.bytes + P, k.len, (k.len + 7u) >> 3, [&](uint32_t q) {
-            if (q == 0u) return w0;
-            if (q == 1u) return w1;
-            const uintptr_t p = (uintptr_t)(tp + 8u * (q - 2u));
-            const uint64_t* w = (const uint64_t*)(p & ~(uintptr_t)7);
-            const uint32_t sh = (uint32_t)(p & 7u) * 8u;
-            const uint64_t x = w[0], y = w[1];
-            return sh ? (x >> sh) | (y << (64u - sh)) : x;
-        });
-    }
-    __device__ void finish(const uint32_t (&tot)[2]) const {
-        a.key_offsets[tot[0]] = tot[1];
-        a.totals->n = tot[0];
-        a.totals->key_bytes = tot[1];
-    }
-};
-
-__global__ __launch_bounds__(kScanThreads) void k_iops_sample(IopsArgs a, ScanState st) {
-    __shared__ uint32_t sv[2][scan_pad(kIopsScanP)];
-    __shared__ uint32_t swave[2][kScanThreads / 64];
-    __shared__ uint32_t sbase[2];
-    __shared__ int s_tile;
-    // a routing that reported an error placed nothing usable: an empty sample
-    const RouteResult res = *a.dres;
-    int64_t n = res.error ? 0 : (int64_t)res.R + res.W;
-    if (n > a.cap) n = a.cap;  // (the routing reports an error past the capacities: never taken)
-    if (threadIdx.x == 0) s_tile = atomicAdd(st.counter, 1);
-    __syncthreads();
-    const int tile = s_tile;
-    const int64_t ntiles = n > 0 ? (n + kIopsTile - 1) / kIopsTile : 1;
-    if (tile >= ntiles) return;  // spare tile of the capacity-sized launch: nobody waits on it
-    const IopsScan f{a, st.error};
-    scan_tile<2, IopsScan, kIopsScanP>(f, n, tile, ntiles, st, sv, swave, sbase);
-}
-
-int64_t iops_scan_words(int64_t cap) { return 8 + scan_granules(cap, 2, kIopsScanP); }
-
-void launch_iops_sample(hipStream_t s, const IopsArgs& a, ScanState st) {
-    const int64_t tiles = std::max<int64_t>(1, (a.cap + kIopsTile - 1) / kIopsTile);
-    fdb_launch(k_iops_sample, dim3((unsigned)tiles), dim3(kScanThreads), 0, s, a, st);
-}
-
-// ------------------------------------------------------------------ history import
-//
-// H'(k) = max(H(k), I(k)) for lo <= k < hi and H(k) elsewhere, I the step function of the imported
-// arrays (the export's layout).  The import becomes a third stream shaped like the delta tier, the
-// overlay: a boundary at lo carrying I(lo), the imported boundaries inside (lo, hi), a boundary at
-// hi carrying kHole (no lo: the overlay's header is the imported header; no hi: no closing hole).
-// With H the two tiers' value, H' = overlay == kHole ? H : max(H, overlay) at every key.
-//   k_import_check      one lane per imported boundary: offsets inside the byte array, lengths not
-//                       negative, neighbours strictly ascending (full byte compare) -> error word
-//   k_import_bounds     imported boundaries <= lo and < hi (plain binary searches), overlay size
-//   k_import_normalize  one lane per overlay boundary: big-endian prefix words, (len, tail unit),
-//                       version, and the bytes past 16 as zero-padded 8-byte words (the inverse of
-//                       export_put_key; source keys start at any byte).  Tail units need no scan:
-//                       imported boundary j owns unit (offsets[j] >> 3) + j, which never overlaps
-//                       its neighbours' and wastes at most 15 bytes per key of scratch.
-//   k_import_rank<S>    one lane per element of stream S inside an ImportWindow (this import: the
-//                       whole streams, no closing boundary): its lower bounds in the other two's
-//                       windows give its position in the merged order (on equal keys delta,
-//                       overlay, base) and all three streams' values at its key, hence H'.  Values
-//                       come from the whole tiers (the boundary covering a window's first key may
-//                       lie before it); the searches are plain binary searches over the windows.
-//                       Later elements of a tie repeat their predecessor's value, so no case is
-//                       special.  The element's prefix words, (len, tail unit) and H' go to its
-//                       merged position.  Base boundaries (S = 0, launched last) search no keys:
-//                       their ranks follow from the lower bounds the other two streams' elements
-//                       found in the base.
-//   k_scan<ImportFold>  flags value changes along the merged stream, scans (kept, tail units) with
-//                       the look-back and writes the kept boundaries into the non-current base
-//                       buffer, their tails packed into the non-current arena; every read of the
-//                       merged stream is coalesced.
-// Nothing current is written: the host switches buffers after reading the result words.
-
-__device__ __forceinline__ uint64_t import_load8(const uint8_t* p) {  // bytes p[0..8), p[0] lowest
-    const uintptr_t a = (uintptr_t)p;
-    const uint64_t* w = (const uint64_t*)(a & ~(uintptr_t)7);
-    const uint32_t sh = (uint32_t)(a & 7u) * 8u;
-    const uint64_t x = w[0];
-    return sh ? (x >> sh) | (w[1] << (64u - sh)) : x;
-}
-
-// memcmp-then-length order of two byte strings at any alignment, 8 bytes per step.
-__device__ __forceinline__ int import_cmp(const uint8_t* a, uint32_t al, const uint8_t* b, uint32_t bl) {
-    const uint32_t n = al < bl ? al : bl;
-    uint32_t i = 0;
-    for (; i + 8u <= n; i += 8u) {
-        const uint64_t x = __builtin_bswap64(import_load8(a + i)), y = __builtin_bswap64(import_load8(b + i));
-        if (x != y) return x < y ? -1 : 1;
-    }
-    if (i < n) {
-        const uint64_t msk = ~0ull << (64u - 8u * (n - i));
-        const uint64_t x = __builtin_bswap64(import_load8(a + i)) & msk, y = __builtin_bswap64(import_load8(b + i)) & msk;
-        if (x != y) return x < y ? -1 : 1;
-    }
-    return (al > bl) - (al < bl);
-}
-
-// Imported boundary j's bytes; false (and an empty key) unless its offsets lie inside the byte array.
-__device__ __forceinline__ bool import_key(const ImportArgs& a, int64_t j, const uint8_t*& p, uint32_t& len) {
-    const int64_t o0 = a.offsets[j], o1 = a.offsets[j + 1];
-    p = a.bytes;
-    len = 0;
-    if (o0 < 0 || o1 < o0 || o1 > a.nbytes || o1 - o0 > (int64_t)INT32_MAX) return false;
-    p = a.bytes + o0;
-    len = (uint32_t)(o1 - o0);
-    return true;
-}
-
-__global__ __launch_bounds__(kBlock) void k_import_check(ImportArgs a) {
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= a.n) return;
-    const uint8_t *p, *q;
-    uint32_t pl, ql;
-    bool ok = import_key(a, j, p, pl);
-    if (j == 0) {
-        ok = ok && a.offsets[0] == 0;
-    } else if (ok) {
-        ok = import_key(a, j - 1, q, ql) && import_cmp(q, ql, p, pl) < 0;
-    }
-    if (!ok) atomicOr((int*)&a.words[kIwError], 1);
-}
-
-__global__ __launch_bounds__(64) void k_import_bounds(ImportArgs a) {
-    __shared__ int64_t r[2];  // imported boundaries <= lo, < hi
-    const int t = threadIdx.x;
-    if (t < 2) {
-        const bool is_hi = t == 1;
-        int64_t lo = 0, hi = a.n;
-        if (!(is_hi ? a.has_hi : a.has_lo)) {
-            lo = is_hi ? a.n : 0;
-        } else {
-            const uint8_t* b = a.bnd + (is_hi ? a.bnd_hi : 0);
-            const uint32_t bl = (uint32_t)(is_hi ? a.hi_len : a.lo_len);
-            while (lo < hi) {
-                const int64_t mid = lo + (hi - lo) / 2;
-                const uint8_t* p;
-                uint32_t pl;
-                import_key(a, mid, p, pl);
-                const int c = import_cmp(p, pl, b, bl);
-                if (c < 0 || (!is_hi && c == 0))
-                    lo = mid + 1;
-                else
-                    hi = mid;
-            }
-        }
-        r[t] = lo;
-    }
-    __syncthreads();
-    if (t != 0) return;
-    const int64_t inner = r[1] > r[0] ? r[1] - r[0] : 0;
-    a.words[kIwJlo] = r[0];
-    a.words[kIwM] = (a.has_lo ? 1 : 0) + inner + (a.has_hi ? 1 : 0);
-}
-
-__global__ __launch_bounds__(kBlock) void k_import_normalize(ImportArgs a) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t m = a.words[kIwM], jlo = a.words[kIwJlo];
-    if (e >= m || e >= a.n + 2) return;
-    const uint8_t* p;
-    uint32_t len;
-    int64_t ver, unit;
-    if (a.has_lo && e == 0) {  // the range's first boundary carries I(lo)
-        p = a.bnd;
-        len = (uint32_t)a.lo_len;
-        ver = jlo > 0 ? a.versions[jlo - 1] : a.ihdr;
-        unit = a.otail_lo;
-    } else if (a.has_hi && e == m - 1) {  // the synthetic boundary that closes the range
-        p = a.bnd + a.bnd_hi;
-        len = (uint32_t)a.hi_len;
-        ver = kHole;
-        unit = a.otail_hi;
-    } else {
-        const int64_t j = jlo + e - (a.has_lo ? 1 : 0);
-        if (j < 0 || j >= a.n || !import_key(a, j, p, len)) {
-            atomicOr((int*)&a.words[kIwError], 1);
-            return;
-        }
-        ver = a.versions[j];
-        unit = (a.offsets[j] >> 3) + j;
-    }
-    uint64_t w0 = len ? import_load8(p) : 0ull, w1 = len > 8u ? import_load8(p + 8) : 0ull;
-    if (len < 8u) w0 &= (1ull << (8u * len)) - 1ull;
-    if (len < 16u) w1 &= len > 8u ? (1ull << (8u * (len - 8u))) - 1ull : 0ull;
-    // the first key byte is the lowest of the loaded word and the highest of the prefix word
-    a.ov.key[e] = make_ulonglong2(__builtin_bswap64(w0), __builtin_bswap64(w1));
-    a.ov.lt[e] = make_uint2(len, len > 16u ? (uint32_t)unit : 0u);
-    a.ov.ver[e] = ver;
-    if (len > 16u) {
-        const uint32_t nt = len - 16u, nu = (nt + 7u) >> 3;
-        uint64_t* d = (uint64_t*)hist_tail(a.otail, (uint32_t)unit);
-        for (uint32_t u = 0; u < nu; u++) {
-            uint64_t w = import_load8(p + 16u + 8u * u);
-            const uint32_t left = nt - 8u * u;
-            if (left < 8u) w &= (1ull << (8u * left)) - 1ull;  // zero padded
-            d[u] = w;
-        }
-    }
-}
-
-// Boundary i of a stream as a search key; its tail starts at qtail.
-__device__ __forceinline__ void impd_key(const Hist& h, int64_t i, const uint8_t* arena, DKey& q,
-                                         const uint8_t*& qtail) {
-    const ulonglong2 k = h.key[i];
-    const uint2 lt = h.lt[i];
-    q.hi = k.x;
-    q.lo = k.y;
-    q.len = lt.x;
-    q.tail = 0;  // the query's tail starts at qtail
-    qtail = hist_tail(arena, lt.x > 16u ? lt.y : 0u);
-}
-
-// Boundaries of h[lo, hi) below q counted from 0 (the answer lies in [lo, hi]), and whether the
-// next one equals it.
-__device__ __forceinline__ int64_t impd_lower(const Hist& h, int64_t lo, int64_t hi, const uint8_t* arena,
-                                              const DKey& q, const uint8_t* qtail, bool& exact) {
-    const int64_t end = hi;
-    while (lo < hi) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (hist_cmp(h, mid, arena, q, qtail) < 0)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    exact = lo < end && hist_cmp(h, lo, arena, q, qtail) == 0;
-    return lo;
-}
-
-// Entries of the ascending array x[0..n) that are <= v.
-__device__ __forceinline__ int64_t import_count_le(const int64_t* x, int64_t n, int64_t v) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (x[mid] <= v)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    return lo;
-}
-
-constexpr uint32_t kImportOvTail = 1u << 31;  // ImportArgs::m_lt len bit: the tail is in the overlay's arena
-
-// S: the stream of this launch's elements (0 base, 1 delta, 2 overlay), one lane per boundary inside
-// the window; with a closing boundary the overlay's launch has one more lane for it.
-template <int S>
-__global__ __launch_bounds__(kBlock) void k_import_rank(ImportArgs a, ImportWindow w) {
-    const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t ndr = w.p_hi - w.p_lo, nbr = w.q_hi - w.q_lo;
-    if (i0 >= (S == 0 ? nbr : S == 1 ? ndr : w.mr + w.closing)) return;
-    if (S == 2 && i0 == w.mr) {  // the closing boundary: hi's key, the delta's old value there
-        const uint2 lt = a.ov.lt[i0];
-        a.m_val[w.R] = w.e_ver;
-        a.m_key[w.R] = a.ov.key[i0];
-        a.m_lt[w.R] = make_uint2(lt.x | kImportOvTail, lt.x > 16u ? lt.y : 0u);
-        return;
-    }
-    const int64_t i = i0 + (S == 0 ? w.q_lo : S == 1 ? w.p_lo : 0);
-    const Hist& h = S == 0 ? a.base : S == 1 ? a.delta : a.ov;
-    const ulonglong2 k = h.key[i];
-    const uint2 lt = h.lt[i];
-    DKey q;
-    const uint8_t* qtail;
-    impd_key(h, i, S == 2 ? a.otail : a.htail, q, qtail);
-    // boundaries below the key (lt) and at or below it (le) in each stream, counted over the whole stream
-    int64_t b_lt = i, b_le = i + 1, d_lt = i, d_le = i + 1, v_lt = i, v_le = i + 1;
-    [[maybe_unused]] bool ex;
-    if constexpr (S == 0) {
-        // a base boundary's ranks in the other two streams follow from their elements' lower bounds
-        // in the base (k_import_rank<1>, <2> ran first): the in-window delta boundaries at or below
-        // base key i are those with at most i base boundaries below them.  A search over a dense
-        // ascending array of integers, no key compares.
-        d_le = w.p_lo + import_count_le(a.d_blt + w.p_lo, ndr, i);
-        v_le = import_count_le(a.v_blt, w.mr, i);
-    } else {
-        b_lt = impd_lower(a.base, w.q_lo, w.q_hi, a.htail, q, qtail, ex);
-        b_le = b_lt + (ex ? 1 : 0);
-        (S == 1 ? a.d_blt : a.v_blt)[i] = b_lt;
-    }
-    if constexpr (S == 2) {
-        d_lt = impd_lower(a.delta, w.p_lo, w.p_hi, a.htail, q, qtail, ex);
-        d_le = d_lt + (ex ? 1 : 0);
-    }
-    if constexpr (S == 1) {
-        v_lt = impd_lower(a.ov, 0, w.mr, a.otail, q, qtail, ex);
-        v_le = v_lt + (ex ? 1 : 0);
-    }
-    // on equal keys: delta, then overlay, then base; positions count from the window's start
-    const int64_t pos = S == 1   ? (d_lt - w.p_lo) + v_lt + (b_lt - w.q_lo)
-                        : S == 2 ? v_lt + (d_le - w.p_lo) + (b_lt - w.q_lo)
-                                 : (b_lt - w.q_lo) + (d_le - w.p_lo) + v_le;
-    const int64_t dv = d_le > 0 ? a.delta.ver[d_le - 1] : kHole;
-    const int64_t bv = b_le > 0 ? a.base.ver[b_le - 1] : a.hdr;
-    const int64_t ov = v_le > 0 ? a.ov.ver[v_le - 1] : a.ovhdr;
-    int64_t v = dv != kHole ? dv : bv;
-    if (ov != kHole && ov > v) v = ov;
-    if (pos < 0 || pos >= w.R) {  // streams out of order: never index past the merged arrays
-        atomicOr(w.error, 4);
-        return;
-    }
-    a.m_val[pos] = v;
-    a.m_key[pos] = k;
-    a.m_lt[pos] = make_uint2(lt.x | (S == 2 ? kImportOvTail : 0u), lt.x > 16u ? lt.y : 0u);
-}
-
-struct ImportFold {
-    ImportArgs a;
-    __device__ bool keep(int64_t p) const { return a.m_val[p] != (p ? a.m_val[p - 1] : a.new_hdr); }
-    // [0] kept boundaries, [1] their tail units (offsets in the new arena)
-    __device__ void load(int64_t p, uint32_t (&x)[2]) const {
-        const bool kp = keep(p);
-        x[0] = kp ? 1u : 0u;
-        x[1] = kp ? tail_units(a.m_lt[p].x & ~kImportOvTail) : 0u;
-    }
-    __device__ void store(int64_t p, const uint32_t (&ex)[2]) const {
-        if (!keep(p)) return;
-        uint2 lt = a.m_lt[p];
-        const bool ovt = (lt.x & kImportOvTail) != 0;
-        lt.x &= ~kImportOvTail;
-        const int64_t o = ex[0], v = a.m_val[p];
-        const uint32_t nu = tail_units(lt.x);
-        if (o >= a.dst_cap || (int64_t)ex[1] + nu > a.tdst_units) {  // never past the buffers the host sized
-            atomicOr((int*)&a.words[kIwError], 8);
-            return;
-        }
-        if (nu) {
-            const uint8_t* arena = a.htail;
-            if (ovt) arena = a.otail;
-            const uint64_t* src = (const uint64_t*)hist_tail(arena, lt.y);
-            uint64_t* d = (uint64_t*)hist_tail(a.tdst, ex[1]);
-            for (uint32_t u = 0; u < nu; u++) d[u] = src[u];
-        }
-        lt.y = nu ? ex[1] : 0u;
-        a.dst.key[o] = a.m_key[p];
-        a.dst.lt[o] = lt;
-        a.dst.ver[o] = v;
-    }
-    __device__ void finish(const uint32_t (&tot)[2]) const {
-        a.words[kIwKept] = tot[0];
-        a.words[kIwTailUnits] = tot[1];
-    }
-};
-
-// The greatest version of a tier from the top level of its range-max hierarchy (every wave of the
-// rebuild raised one of its words; unused words hold LLONG_MIN), into *out by atomicMax.
-__global__ __launch_bounds__(kBlock) void k_import_max(const int64_t* lvl3, int64_t words, int64_t* out) {
-    long long x = LLONG_MIN;
-    for (int64_t i = threadIdx.x; i < words; i += blockDim.x) {
-        const long long y = lvl3[i * kL3Pad];
-        x = y > x ? y : x;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const long long y = __shfl_xor(x, o, 64);
-        x = y > x ? y : x;
-    }
-    if ((threadIdx.x & 63) == 0 && x != LLONG_MIN) atomicMax((long long*)out, x);
-}
-
-void launch_import_max(hipStream_t s, const MaxLevels& m, int64_t lvl3_n, int64_t* out) {
-    fdb_launch(k_import_max, dim3(1), dim3(kBlock), 0, s, (const int64_t*)m.lvl[3], lvl3_n * kL3Rep, out);
-}
-
-void launch_import_overlay(hipStream_t s, const ImportArgs& a) {
-    if (a.n > 0) fdb_launch(k_import_check, dim3((unsigned)((a.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, a);
-    fdb_launch(k_import_bounds, dim3(1), dim3(64), 0, s, a);
-    fdb_launch(k_import_normalize, dim3((unsigned)((a.n + 2 + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, a);
-}
-
-// The rank launches of either import: delta, overlay, then base (it reads d_blt, v_blt).
-static void launch_import_rank(hipStream_t s, const ImportArgs& a, const ImportWindow& w) {
-    auto grid = [](int64_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); };
-    const int64_t ndr = w.p_hi - w.p_lo, nv = w.mr + w.closing, nbr = w.q_hi - w.q_lo;
-    if (ndr > 0) fdb_launch(k_import_rank<1>, grid(ndr), dim3(kBlock), 0, s, a, w);
-    if (nv > 0) fdb_launch(k_import_rank<2>, grid(nv), dim3(kBlock), 0, s, a, w);
-    if (nbr > 0) fdb_launch(k_import_rank<0>, grid(nbr), dim3(kBlock), 0, s, a, w);
-}
-
-void launch_import_fold(hipStream_t s, const ImportArgs& a, int64_t m, uint64_t* granules) {
-    ImportWindow w{};  // the whole streams, no closing boundary
-    w.p_hi = a.nd;
-    w.q_hi = a.nb;
-    w.mr = m;
-    w.R = a.nb + a.nd + m;
-    w.error = (int*)&a.words[kIwError];
-    launch_import_rank(s, a, w);
-    ScanState st;
-    st.granules = granules;
-    st.counter = (int*)&a.words[kIwScan];
-    st.error = st.counter + 1;
-    launch_scan<2>(s, ImportFold{a}, (const int64_t*)nullptr, a.nb + a.nd + m, st);
-}
-
-// ------------------------------------------------------------------ history import into the delta tier
-//
-// The same H' as above, written as delta boundaries over [lo, hi) instead of a new base: the work is
-// O(boundaries of the three streams inside the range + size of the delta), whatever the base holds.
-// Inside the range the new delta carries H' at every key where a stream has a boundary, base
-// boundaries included (equal neighbours coalesced), so no delta entry at an imported version spans a
-// base boundary of a greater one (the delta invariant: a delta version is kHole or at least every
-// base version it covers).  The boundary at lo is always written; at hi a closing boundary carries
-// what the delta held there before (as the E of a batch merge), unless the delta has a boundary at
-// hi.  Outside the range the delta is copied as it is.
-//   k_impd_bounds     positions of lo and hi in the base and in the delta (plain binary searches,
-//                     full key compare), the delta's value at hi
-//   k_import_rank<S>  the fold's kernel over the windows k_impd_bounds found: one lane per boundary of
-//                     stream S inside the range, log2(range) search steps instead of log2(tier)
-//                     (the base's directory, lane_lower_bound, is not used: an in-range search is
-//                     already short).  The overlay's launch has one more lane, which puts the
-//                     closing boundary at position R.
-//   k_scan<ImportDeltaFold>  flags value changes along the in-range stream, scans (kept, tail units
-//                     of kept overlay keys) on granules of the import's own and writes the kept
-//                     boundaries into the non-current delta buffer from p_lo on, one lane each.
-//                     Base and delta boundaries keep their tail offsets (the arena is shared);
-//                     kept overlay keys longer than 16 bytes append theirs past tail_used.
-//   k_impd_copy       the delta's prefix [0, p_lo) as it is and its suffix [p_hi, nd) shifted behind
-//                     the kept boundaries, grid-stride.
-// The greatest version is read off the rebuilt delta's top level (k_import_max), never per element.
-
-__global__ __launch_bounds__(64) void k_impd_bounds(ImportDeltaArgs d) {
-    const ImportArgs& a = d.a;
-    __shared__ int64_t r[4];  // boundaries below lo in base, delta; below hi in base, delta
-    const int t = threadIdx.x;
-    const int64_t m = a.words[kIwM];
-    // an invalid import leaves nothing to place (the host refuses it after reading the words)
-    const bool ok = a.words[kIwError] == 0 && m >= (a.has_lo ? 1 : 0) + (a.has_hi ? 1 : 0) && m <= a.n + 2;
-    if (t < 4) {
-        const bool is_hi = t >= 2, is_delta = t & 1;
-        const int64_t n = is_delta ? a.nd : a.nb;
-        int64_t x = is_hi ? n : 0;
-        if (ok && (is_hi ? a.has_hi : a.has_lo)) {
-            DKey q;
-            const uint8_t* qtail;
-            impd_key(a.ov, is_hi ? m - 1 : 0, a.otail, q, qtail);
-            x = export_bound(is_delta ? a.delta : a.base, n, a.htail, q, qtail, false);
-        }
-        r[t] = x;
-    }
-    __syncthreads();
-    if (t != 0) return;
-    const int64_t q_lo = r[0], p_lo = r[1], q_hi = r[2] > r[0] ? r[2] : r[0], p_hi = r[3] > r[1] ? r[3] : r[1];
-    int64_t skip = 0;
-    if (ok && a.has_hi && p_hi < a.nd) {
-        DKey q;
-        const uint8_t* qtail;
-        impd_key(a.ov, m - 1, a.otail, q, qtail);
-        skip = hist_cmp(a.delta, p_hi, a.htail, q, qtail) == 0 ? 1 : 0;
-    }
-    d.dwords[kIdPlo] = p_lo;
-    d.dwords[kIdPhi] = p_hi;
-    d.dwords[kIdQlo] = q_lo;
-    d.dwords[kIdQhi] = q_hi;
-    d.dwords[kIdEver] = p_hi > 0 ? a.delta.ver[p_hi - 1] : kHole;
-    d.dwords[kIdEskip] = skip;
-}
-
-struct ImportDeltaFold {
-    ImportDeltaArgs d;
-    __device__ bool keep(int64_t p) const {
-        const ImportArgs& a = d.a;
-        if (p == d.w.R && d.e_skip) return false;  // the delta's own boundary at hi follows
-        // the boundary at lo always stands; without a lower bound the delta's implicit header is a hole
-        if (p == 0) return a.has_lo || a.m_val[0] != kHole;
-        return a.m_val[p] != a.m_val[p - 1];
-    }
-    // [0] kept boundaries, [1] tail units appended to the arena (kept overlay keys only)
-    __device__ void load(int64_t p, uint32_t (&x)[2]) const {
-        const bool kp = keep(p);
-        const uint32_t len = d.a.m_lt[p].x;
-        x[0] = kp ? 1u : 0u;
-        x[1] = kp && (len & kImportOvTail) ? tail_units(len & ~kImportOvTail) : 0u;
-    }
-    __device__ void store(int64_t p, const uint32_t (&ex)[2]) const {
-        if (!keep(p)) return;
-        const ImportArgs& a = d.a;
-        uint2 lt = a.m_lt[p];
-        const bool ovt = (lt.x & kImportOvTail) != 0;
-        lt.x &= ~kImportOvTail;
-        const int64_t o = d.w.p_lo + (int64_t)ex[0];
-        const uint32_t nu = ovt ? tail_units(lt.x) : 0u;
-        const int64_t unit = d.tail_base + (int64_t)ex[1];
-        if (o >= a.dst_cap || unit + nu > a.tdst_units) {  // never past the buffers the host sized
-            atomicOr((int*)&d.dwords[kIdError], 8);
-            return;
-        }
-        if (nu) {  // past tail_used: invisible until the host raises it
-            const uint64_t* src = (const uint64_t*)hist_tail(a.otail, lt.y);
-            uint64_t* dst = (uint64_t*)(a.tdst + 8 * (size_t)unit);
-            for (uint32_t u = 0; u < nu; u++) dst[u] = src[u];
-            lt.y = (uint32_t)unit;
-        }
-        a.dst.key[o] = a.m_key[p];
-        a.dst.lt[o] = lt;
-        a.dst.ver[o] = a.m_val[p];
-    }
-    __device__ void finish(const uint32_t (&tot)[2]) const {
-        d.dwords[kIdKept] = tot[0];
-        d.dwords[kIdTailUnits] = tot[1];
-    }
-};
-
-__global__ __launch_bounds__(kBlock) void k_impd_copy(ImportDeltaArgs d) {
-    const ImportArgs& a = d.a;
-    const int64_t kept = d.dwords[kIdKept];
-    const int64_t n = a.nd - (d.w.p_hi - d.w.p_lo);  // boundaries outside the range
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const bool pre = i < d.w.p_lo;
-        const int64_t src = pre ? i : d.w.p_hi + (i - d.w.p_lo), dst = pre ? i : i + kept;
-        if (dst < 0 || dst >= a.dst_cap) {
-            atomicOr((int*)&d.dwords[kIdError], 8);
-            continue;
-        }
-        a.dst.key[dst] = a.delta.key[src];
-        a.dst.lt[dst] = a.delta.lt[src];
-        a.dst.ver[dst] = a.delta.ver[src];
-    }
-}
-
-void launch_import_delta_bounds(hipStream_t s, const ImportDeltaArgs& d) {
-    fdb_launch(k_impd_bounds, dim3(1), dim3(64), 0, s, d);
-}
-
-void launch_import_delta_merge(hipStream_t s, const ImportDeltaArgs& d, uint64_t* granules) {
-    ImportWindow w = d.w;
-    w.error = (int*)&d.dwords[kIdError];
-    launch_import_rank(s, d.a, w);
-    ScanState st;
-    st.granules = granules;
-    st.counter = (int*)&d.dwords[kIdScan];
-    st.error = st.counter + 1;
-    const int64_t total = w.R + w.closing;
-    if (total > 0) launch_scan<2>(s, ImportDeltaFold{d}, (const int64_t*)nullptr, total, st);
-    const int64_t outside = d.a.nd - (w.p_hi - w.p_lo);
-    if (outside > 0) {
-        const int64_t g = (outside + kBlock - 1) / kBlock;
-        fdb_launch(k_impd_copy, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(kBlock), 0, s, d);
-    }
 }
 
 }  // namespace fdbcs

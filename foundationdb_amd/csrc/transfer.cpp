@@ -1,0 +1,616 @@
+// transfer.cpp — the maintenance entry points of the C-ABI (include/fdb_conflict_set.h): history
+// export, the two history imports and the resolver's iops sample.  They work on an idle set (or,
+// for the sample, off the detect stream) through the state and helpers of engine_impl.h and launch
+// the kernels of transfer.hip; the detect pipeline's host side is engine.cpp.
+#include "engine_impl.h"
+#include "transfer.h"
+
+// The bounds of a key range as the entry points take them (a length below 0: no bound).
+static int import_bounds_ok(const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key, int32_t hi_len) {
+    if ((lo_len > 0 && !lo_key) || (hi_len > 0 && !hi_key)) return FDBCS_E_INVALID;
+    if (lo_len >= 0 && hi_len >= 0 && cmp_bytes(lo_key, lo_len, hi_key, hi_len) > 0) return FDBCS_E_INVALID;
+    return FDBCS_OK;
+}
+
+// A keyed result back to the host: n items of item_bytes each, n + 1 key offsets and the key bytes.
+static int copy_keyed_result(int64_t n, int64_t nbytes, void* items, const void* d_items, size_t item_bytes,
+                             int64_t* key_offsets, const void* d_offsets, uint8_t* key_bytes, const void* d_bytes) {
+    if (n) HIPOK(hipMemcpy(items, d_items, item_bytes * (size_t)n, hipMemcpyDeviceToHost));
+    HIPOK(hipMemcpy(key_offsets, d_offsets, 8 * (size_t)(n + 1), hipMemcpyDeviceToHost));
+    if (nbytes) HIPOK(hipMemcpy(key_bytes, d_bytes, (size_t)nbytes, hipMemcpyDeviceToHost));
+    return FDBCS_OK;
+}
+
+extern "C" {
+
+int fdbcs_history_export(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key,
+                         int32_t hi_len, int64_t floor_version, int64_t* n_out, int64_t* key_bytes_out,
+                         int64_t* header_version_out) {
+    if (!cs || !n_out || !key_bytes_out || !header_version_out) return FDBCS_E_INVALID;
+    if (int rc = import_bounds_ok(lo_key, lo_len, hi_key, hi_len)) return rc;
+    if (cs->inflight) return FDBCS_E_STATE;
+    HIPOK(hipSetDevice(cs->device));
+    if (int rc = sync_all(cs)) return rc;
+    cs->x_valid = false;
+    Scalars sc;
+    HIPOK(hipMemcpy(&sc, cs->scal.p, sizeof(sc), hipMemcpyDeviceToHost));
+    ExportArgs a{};
+    a.nb = sc.n;
+    a.nd = sc.ndb[cs->dcur];
+    const int64_t total = a.nb + a.nd;
+    // the byte scan's exact range (transfer.hip, history export): refuse rather than wrap
+    if (total >= ((int64_t)1 << 29) || 16 * total + sc.tail_used >= ((int64_t)1 << 35)) return FDBCS_E_NOMEM;
+    a.base = hist_of(cs, cs->cur);
+    a.delta = delta_of(cs, cs->dcur);
+    a.htail = (const uint8_t*)cs->htail[cs->tcur].p;
+    a.hdr = cs->header_version;
+    a.floor = floor_version;
+    // lo / hi as RouteArgs::lo / hi: DKey + tail bytes in a small device buffer
+    std::vector<uint8_t> bt;
+    auto norm = [&](const uint8_t* p, int32_t len, DKey& k) {
+        dkey_prefix(p, (uint32_t)len, &k.hi, &k.lo);
+        k.len = (uint32_t)len;
+        k.tail = (uint32_t)bt.size();
+        if (len > 16) bt.insert(bt.end(), p + 16, p + len);
+    };
+    a.has_lo = lo_len >= 0;
+    a.has_hi = hi_len >= 0;
+    if (a.has_lo) norm(lo_key, lo_len, a.lo);
+    if (a.has_hi) norm(hi_key, hi_len, a.hi);
+    const int64_t tiles = export_tiles(total);
+    int rc;
+    if ((rc = cs->x_btail.ensure(bt.size() + kTailSlack))) return rc;
+    if ((rc = cs->x_pos.ensure(8 * (size_t)(a.nd + 1)))) return rc;
+    if ((rc = cs->x_val.ensure(8 * (size_t)(a.nd + 1)))) return rc;
+    if ((rc = cs->x_state.ensure(8 * (size_t)(kXwWords + 4 * tiles)))) return rc;
+    if ((rc = cs->x_ver.ensure(8 * (size_t)(total + 1)))) return rc;
+    if ((rc = cs->x_off.ensure(8 * (size_t)(total + 1)))) return rc;
+    if ((rc = cs->x_bytes.ensure((size_t)(16 * total + sc.tail_used + 64)))) return rc;
+    if (!cs->x_ev0) HIPOK(hipEventCreate(&cs->x_ev0));
+    if (!cs->x_ev1) HIPOK(hipEventCreate(&cs->x_ev1));
+    a.btail = (const uint8_t*)cs->x_btail.p;
+    a.d_pos = (int64_t*)cs->x_pos.p;
+    a.d_val = (int64_t*)cs->x_val.p;
+    a.words = (int64_t*)cs->x_state.p;
+    a.tile_tb = a.words + kXwWords + 3 * tiles;  // after the scan's granules
+    a.versions = (int64_t*)cs->x_ver.p;
+    a.offsets = (int64_t*)cs->x_off.p;
+    a.bytes = (uint8_t*)cs->x_bytes.p;
+    a.bytes_cap = (int64_t)cs->x_bytes.cap;
+    hipStream_t s = cs->stream;
+    if (!bt.empty()) HIPOK(hipMemcpyAsync(cs->x_btail.p, bt.data(), bt.size(), hipMemcpyHostToDevice, s));
+    HIPOK(hipMemsetAsync(cs->x_state.p, 0, 8 * (size_t)(kXwWords + 3 * tiles), s));
+    HIPOK(hipEventRecord(cs->x_ev0, s));
+    launch_export(s, a, levels_of(cs, cs->cur), (uint64_t*)cs->x_state.p + kXwWords, sc.tail_used > 0 ? 2 : 1);
+    HIPOK(take_launch_error());
+    HIPOK(hipEventRecord(cs->x_ev1, s));
+    int64_t words[kXwWords];
+    HIPOK(hipMemcpyAsync(words, cs->x_state.p, sizeof(words), hipMemcpyDeviceToHost, s));
+    HIPOK(hipStreamSynchronize(s));
+    cs->x_ms_kernels = ev_ms(cs->x_ev0, cs->x_ev1);
+    cs->x_ms_d2h = 0;
+    if (((const int32_t*)&words[kXwScan])[1]) return FDBCS_E_DEVICE;  // look-back bound, positions out of order, key buffer
+    cs->x_n = words[kXwN];
+    cs->x_nbytes = words[kXwBytes];
+    cs->x_hdr = words[kXwHeader];
+    cs->x_valid = true;
+    *n_out = cs->x_n;
+    *key_bytes_out = cs->x_nbytes;
+    *header_version_out = words[kXwHeader];
+    return FDBCS_OK;
+}
+
+int fdbcs_history_export_read(fdbcs_conflict_set* cs, uint8_t* key_bytes, int64_t key_bytes_cap, int64_t* key_offsets,
+                              int64_t* versions, int64_t cap) {
+    if (!cs || key_bytes_cap < 0 || cap < 0 || !key_offsets) return FDBCS_E_INVALID;
+    if (!cs->x_valid) return FDBCS_E_STATE;
+    if (cap < cs->x_n || key_bytes_cap < cs->x_nbytes) return FDBCS_E_NOMEM;
+    if ((cs->x_n && !versions) || (cs->x_nbytes && !key_bytes)) return FDBCS_E_INVALID;
+    HIPOK(hipSetDevice(cs->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    if (int rc = copy_keyed_result(cs->x_n, cs->x_nbytes, versions, cs->x_ver.p, 8, key_offsets, cs->x_off.p, key_bytes,
+                                   cs->x_bytes.p))
+        return rc;
+    cs->x_ms_d2h = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    cs->x_valid = false;
+    return FDBCS_OK;
+}
+
+int fdbcs_history_export_timing(fdbcs_conflict_set* cs, double* ms_kernels, double* ms_d2h) {
+    if (!cs || !ms_kernels || !ms_d2h) return FDBCS_E_INVALID;
+    *ms_kernels = cs->x_ms_kernels;
+    *ms_d2h = cs->x_ms_d2h;
+    return FDBCS_OK;
+}
+
+// What the last successful import did (fdbcs_history_import_info).
+static void import_note(fdbcs_conflict_set* cs, int32_t path, int64_t base, int64_t delta_before, int64_t delta_after) {
+    cs->i_path = path;
+    cs->i_info_base = base;
+    cs->i_info_before = delta_before;
+    cs->i_info_after = delta_after;
+}
+
+// What phase 1 of an import leaves for its continuation.
+struct ImportPlan {
+    Scalars sc;            // the set's scalars before the import
+    int64_t m;             // overlay boundaries
+    int64_t u_end;         // 8-byte units of the overlay's tail arena
+    ImportDeltaArgs d;     // d.a: the arguments both imports share; the rest is the delta import's
+    int64_t dw[kIdWords];  // what k_impd_bounds found (to_delta only)
+};
+
+// The tier pointers of an import's arguments (again after a capacity change: the buffers may have
+// moved).  The fold writes the non-current base buffer and arena, the delta import the non-current
+// delta buffer and the current arena.
+static void import_tiers(fdbcs_conflict_set* cs, ImportArgs& a, bool to_delta) {
+    a.base = hist_of(cs, cs->cur);
+    a.delta = delta_of(cs, cs->dcur);
+    a.htail = (const uint8_t*)cs->htail[cs->tcur].p;
+    a.dst = to_delta ? delta_of(cs, cs->dcur ^ 1) : hist_of(cs, cs->cur ^ 1);
+    a.tdst = (uint8_t*)cs->htail[to_delta ? cs->tcur : cs->tcur ^ 1].p;
+    a.dst_cap = to_delta ? cs->delta_cap : cs->hist_cap;
+    a.tdst_units = cs->tail_cap / 8;
+}
+
+// The merged arrays of phase 2, for `total` positions.
+static int import_merged(fdbcs_conflict_set* cs, ImportArgs& a, int64_t total) {
+    int rc;
+    if ((rc = cs->i_mval.ensure(8 * (size_t)total))) return rc;
+    if ((rc = cs->i_mkey.ensure(16 * (size_t)total))) return rc;
+    if ((rc = cs->i_mlt.ensure(8 * (size_t)total))) return rc;
+    if ((rc = cs->i_dblt.ensure(8 * (size_t)(a.nd + 1)))) return rc;
+    a.m_val = (int64_t*)cs->i_mval.p;
+    a.m_key = (ulonglong2*)cs->i_mkey.p;
+    a.m_lt = (uint2*)cs->i_mlt.p;
+    a.d_blt = (int64_t*)cs->i_dblt.p;
+    return FDBCS_OK;
+}
+
+// Phase 1 of both imports, on device arrays.  The set is idle, its streams drained; d_bytes is
+// 8-byte aligned with >= 16 readable bytes past nbytes.  The host does no per-boundary work: it
+// sizes the overlay from n and nbytes, launches the validation and the overlay's build (to_delta:
+// and the search that places lo and hi in both tiers) and reads the words back once.  *done: the
+// import is over (an empty range: validated, nothing to do).
+static int import_phase1(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key,
+                         int32_t hi_len, int64_t n, const uint8_t* d_bytes, int64_t nbytes, const int64_t* d_off,
+                         const int64_t* d_ver, int64_t ihdr, int64_t* boundaries_out, bool to_delta, ImportPlan& pl,
+                         bool* done) {
+    *done = false;
+    Scalars& sc = pl.sc;
+    HIPOK(hipMemcpy(&sc, cs->scal.p, sizeof(sc), hipMemcpyDeviceToHost));
+    const int64_t nb = sc.n, nd = sc.ndb[cs->dcur];
+    if (nb + nd + n + 2 >= ((int64_t)1 << 31)) return FDBCS_E_NOMEM;  // the fold's 32-bit scan components
+    const bool has_lo = lo_len >= 0, has_hi = hi_len >= 0;
+    const int64_t ll = has_lo ? lo_len : 0, hl = has_hi ? hi_len : 0;
+    // overlay tails, in 8-byte units: imported boundary j at (offset_j >> 3) + j, then lo's and hi's
+    const int64_t u_lo = ((nbytes + 7) >> 3) + n + 1, u_hi = u_lo + ((ll + 7) >> 3) + 1, u_end = u_hi + ((hl + 7) >> 3) + 1;
+    // the fold packs at most that many units behind the arena's bytes, the delta import appends
+    // them from the next whole unit on
+    const int64_t tail_base = (sc.tail_used + 7) >> 3;
+    const int64_t tail_need = to_delta ? 8 * (tail_base + u_end) : sc.tail_used + 8 * u_end;
+    if (tail_need + 1 >= kTailLimit) return FDBCS_E_NOMEM;
+    int rc;
+    const int64_t bnd_hi = (ll + 7) / 8 * 8 + 16;
+    if ((rc = cs->i_bnd.ensure((size_t)(bnd_hi + hl + 64)))) return rc;
+    if ((rc = cs->i_okey.ensure(16 * (size_t)(n + 2)))) return rc;
+    if ((rc = cs->i_olt.ensure(8 * (size_t)(n + 2)))) return rc;
+    if ((rc = cs->i_over.ensure(8 * (size_t)(n + 2)))) return rc;
+    if ((rc = cs->i_otail.ensure(8 * (size_t)u_end + kTailSlack))) return rc;
+    if ((rc = cs->i_vblt.ensure(8 * (size_t)(n + 2)))) return rc;
+    if ((rc = cs->i_state.ensure(8 * (size_t)kIwWords))) return rc;
+    if (to_delta && (rc = cs->i_dstate.ensure(8 * (size_t)kIdWords))) return rc;
+    for (hipEvent_t& e : cs->i_ev)
+        if (!e) HIPOK(hipEventCreate(&e));
+    pl.u_end = u_end;
+    pl.d = ImportDeltaArgs{};
+    ImportArgs& a = pl.d.a;
+    import_tiers(cs, a, to_delta);
+    a.nb = nb;
+    a.nd = nd;
+    a.hdr = cs->header_version;
+    a.n = n;
+    a.bytes = d_bytes;
+    a.nbytes = nbytes;
+    a.offsets = d_off;
+    a.versions = d_ver;
+    a.ihdr = ihdr;
+    a.has_lo = has_lo;
+    a.has_hi = has_hi;
+    a.lo_len = (int32_t)ll;
+    a.hi_len = (int32_t)hl;
+    a.bnd = (const uint8_t*)cs->i_bnd.p;
+    a.bnd_hi = bnd_hi;
+    a.ov.key = (ulonglong2*)cs->i_okey.p;
+    a.ov.lt = (uint2*)cs->i_olt.p;
+    a.ov.ver = (int64_t*)cs->i_over.p;
+    a.otail = (uint8_t*)cs->i_otail.p;
+    a.otail_lo = u_lo;
+    a.otail_hi = u_hi;
+    a.ovhdr = has_lo ? kHole : ihdr;
+    a.words = (int64_t*)cs->i_state.p;
+    a.v_blt = (int64_t*)cs->i_vblt.p;
+    a.new_hdr = has_lo ? cs->header_version : std::max(cs->header_version, ihdr);
+    pl.d.dwords = (int64_t*)cs->i_dstate.p;
+    pl.d.tail_base = tail_base;
+    hipStream_t s = cs->stream;
+    if (ll) HIPOK(hipMemcpyAsync(cs->i_bnd.p, lo_key, (size_t)ll, hipMemcpyHostToDevice, s));
+    if (hl) HIPOK(hipMemcpyAsync((uint8_t*)cs->i_bnd.p + bnd_hi, hi_key, (size_t)hl, hipMemcpyHostToDevice, s));
+    HIPOK(hipMemsetAsync(cs->i_state.p, 0, 8 * (size_t)kIwWords, s));
+    if (to_delta) HIPOK(hipMemsetAsync(cs->i_dstate.p, 0, 8 * (size_t)kIdWords, s));
+    const int64_t none = kHole;
+    HIPOK(hipMemcpyAsync(&a.words[kIwMaxVer], &none, 8, hipMemcpyHostToDevice, s));
+    int64_t words[kIwWords];
+    HIPOK(hipEventRecord(cs->i_ev[0], s));
+    launch_import_overlay(s, a);
+    if (to_delta) launch_import_delta_bounds(s, pl.d);
+    HIPOK(take_launch_error());
+    HIPOK(hipEventRecord(cs->i_ev[1], s));
+    HIPOK(hipMemcpyAsync(words, cs->i_state.p, sizeof(words), hipMemcpyDeviceToHost, s));
+    if (to_delta) HIPOK(hipMemcpyAsync(pl.dw, cs->i_dstate.p, sizeof(pl.dw), hipMemcpyDeviceToHost, s));
+    HIPOK(hipStreamSynchronize(s));
+    cs->i_ms_kernels = ev_ms(cs->i_ev[0], cs->i_ev[1]);
+    if ((int32_t)words[kIwError] & 1) return FDBCS_E_INVALID;
+    if (words[kIwError]) return FDBCS_E_DEVICE;
+    if (has_lo && has_hi && cmp_bytes(lo_key, lo_len, hi_key, hi_len) == 0) {
+        *boundaries_out = nb + nd;
+        import_note(cs, to_delta ? 1 : 0, nb, nd, nd);
+        *done = true;
+        return FDBCS_OK;
+    }
+    pl.m = words[kIwM];
+    if (pl.m < (has_lo ? 1 : 0) + (has_hi ? 1 : 0) || pl.m > n + 2) return FDBCS_E_DEVICE;
+    return FDBCS_OK;
+}
+
+// The end both imports share, once the device scalars hold the new sizes: rebuild the range-max
+// levels of the tier that changed (n_new boundaries), read its greatest version off their top and
+// raise the set's header and greatest written version.
+static int import_finish(fdbcs_conflict_set* cs, const ImportArgs& a, bool delta_tier, int64_t n_new) {
+    hipStream_t s = cs->stream;
+    Scalars* dsc = (Scalars*)cs->scal.p;
+    const MaxLevels lv = delta_tier ? dlevels_of(cs, cs->dcur) : levels_of(cs, cs->cur);
+    const int64_t lvl3_n = delta_tier ? cs->dlvl3_n : cs->lvl3_n, lvl2_n = delta_tier ? cs->dlvl2_n : cs->lvl2_n;
+    HIPOK(hipEventRecord(cs->i_ev[4], s));
+    launch_rangemax(s, lv, dsc, delta_tier ? &dsc->ndb[cs->dcur] : &dsc->n, lvl3_n, lvl2_n,
+                    std::max<int64_t>(n_new, 1));
+    // the top of the rebuilt levels (holes are INT64_MIN), never a pass over the elements
+    launch_import_max(s, lv, lvl3_n, &a.words[kIwMaxVer]);
+    HIPOK(take_launch_error());
+    HIPOK(hipEventRecord(cs->i_ev[5], s));
+    int64_t max_ver;
+    HIPOK(hipMemcpyAsync(&max_ver, &a.words[kIwMaxVer], 8, hipMemcpyDeviceToHost, s));
+    HIPOK(hipStreamSynchronize(s));
+    cs->i_ms_kernels += ev_ms(cs->i_ev[4], cs->i_ev[5]);
+    cs->header_version = a.new_hdr;
+    cs->max_written = std::max({cs->max_written, a.new_hdr, max_ver});
+    cs->ddir_epoch[0] = cs->ddir_epoch[1] = 0;  // the delta's directory: not trusted until an epilogue refills it
+    cs->prev_segs = false;
+    return FDBCS_OK;
+}
+
+// Phase 2 of the fold, from a finished phase 1 of either import: merges the three streams into the
+// non-current base buffer and tail arena and, on success, switches to them with an empty delta.
+static int import_fold(fdbcs_conflict_set* cs, ImportPlan& pl, int64_t* boundaries_out) {
+    ImportArgs& a = pl.d.a;
+    const int64_t nb = a.nb, nd = a.nd, m = pl.m;
+    const int64_t total_ub = nb + nd + a.n + 2;
+    const int64_t tail_need = pl.sc.tail_used + 8 * pl.u_end;
+    int rc;
+    if ((rc = ensure_history(cs, total_ub + 1, tail_need + 1))) return rc;
+    if ((rc = import_merged(cs, a, total_ub))) return rc;
+    // the scan's granules have a buffer of their own: the words of phase 1 stay where they are
+    const size_t gran = 8 * (size_t)scan_granules(total_ub, 2);
+    if ((rc = cs->i_gran.ensure(gran))) return rc;
+    import_tiers(cs, a, false);
+    hipStream_t s = cs->stream;
+    HIPOK(hipMemsetAsync(cs->i_gran.p, 0, gran, s));
+    HIPOK(hipEventRecord(cs->i_ev[2], s));
+    HIPOK(hipMemsetAsync(cs->i_mlt.p, 0, 8 * (size_t)(nb + nd + m), s));
+    launch_import_fold(s, a, m, (uint64_t*)cs->i_gran.p);
+    HIPOK(take_launch_error());
+    HIPOK(hipEventRecord(cs->i_ev[3], s));
+    int64_t words[kIwWords];
+    HIPOK(hipMemcpyAsync(words, cs->i_state.p, sizeof(words), hipMemcpyDeviceToHost, s));
+    HIPOK(hipStreamSynchronize(s));
+    cs->i_ms_kernels += ev_ms(cs->i_ev[2], cs->i_ev[3]);
+    if ((int32_t)words[kIwError] & 8) return FDBCS_E_NOMEM;
+    if (words[kIwError] || ((const int32_t*)&words[kIwScan])[1]) return FDBCS_E_DEVICE;
+    // success: the buffers the fold filled become current, the delta is empty
+    const int64_t kept = words[kIwKept], tail_used = 8 * words[kIwTailUnits];
+    cs->cur ^= 1;
+    cs->tcur ^= 1;
+    Scalars ns{};
+    ns.n = kept;
+    ns.tail_used = tail_used;
+    HIPOK(hipMemcpyAsync(cs->scal.p, &ns, sizeof(ns), hipMemcpyHostToDevice, s));
+    if ((rc = import_finish(cs, a, false, kept))) return rc;
+    cs->n_ub = kept;
+    cs->nd_ub = 0;
+    cs->tail_ub = tail_used;
+    *boundaries_out = kept;
+    import_note(cs, 0, kept, nd, 0);
+    return FDBCS_OK;
+}
+
+// The import that folds into a new base (both of its entry points end here).
+static int import_device(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key,
+                         int32_t hi_len, int64_t n, const uint8_t* d_bytes, int64_t nbytes, const int64_t* d_off,
+                         const int64_t* d_ver, int64_t ihdr, int64_t* boundaries_out) {
+    ImportPlan pl;
+    bool done;
+    const int rc = import_phase1(cs, lo_key, lo_len, hi_key, hi_len, n, d_bytes, nbytes, d_off, d_ver, ihdr,
+                                 boundaries_out, false, pl, &done);
+    return rc || done ? rc : import_fold(cs, pl, boundaries_out);
+}
+
+// The import into the delta tier (same contract).  After phase 1 the host knows an upper bound of
+// the delta afterwards and either goes on (phase 2 writes the non-current delta buffer and arena
+// bytes past tail_used, and the host switches to them after reading the result words) or goes on
+// with the fold's phase 2 on the overlay it has, which leaves an empty delta.
+static int import_delta_device(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key,
+                               int32_t hi_len, int64_t n, const uint8_t* d_bytes, int64_t nbytes, const int64_t* d_off,
+                               const int64_t* d_ver, int64_t ihdr, int64_t* boundaries_out) {
+    ImportPlan pl;
+    bool done;
+    int rc = import_phase1(cs, lo_key, lo_len, hi_key, hi_len, n, d_bytes, nbytes, d_off, d_ver, ihdr, boundaries_out,
+                           true, pl, &done);
+    if (rc || done) return rc;
+    ImportDeltaArgs& d = pl.d;
+    ImportArgs& a = d.a;
+    ImportWindow& w = d.w;
+    Scalars& sc = pl.sc;
+    const int64_t nb = a.nb, nd = a.nd, m = pl.m;
+    const int64_t* dw = pl.dw;
+    w.p_lo = dw[kIdPlo];
+    w.p_hi = dw[kIdPhi];
+    w.q_lo = dw[kIdQlo];
+    w.q_hi = dw[kIdQhi];
+    w.e_ver = dw[kIdEver];
+    d.e_skip = dw[kIdEskip] ? 1 : 0;
+    if (w.p_lo < 0 || w.p_lo > w.p_hi || w.p_hi > nd || w.q_lo < 0 || w.q_lo > w.q_hi || w.q_hi > nb) return FDBCS_E_DEVICE;
+    const int64_t nbr = w.q_hi - w.q_lo;
+    w.closing = a.has_hi ? 1 : 0;
+    w.mr = m - w.closing;
+    w.R = (w.p_hi - w.p_lo) + nbr + w.mr;
+    // the delta afterwards holds at most its boundaries outside the range, the range's and the closing one
+    const int64_t nd_bound = nd + nbr + m + 2;
+    bool fold = nd_bound > delta_limit_for(cs, cs->n_ub);
+    if (!fold) {
+        rc = ensure_delta(cs, nd_bound);
+        if (rc == FDBCS_E_NOMEM)
+            fold = true;
+        else if (rc)
+            return rc;
+    }
+    // the fold takes every range the delta cannot hold: exact, with an empty delta
+    if (fold) return import_fold(cs, pl, boundaries_out);
+    if ((rc = ensure_history(cs, cs->hist_cap, 8 * (d.tail_base + pl.u_end) + 1))) return rc;
+    const int64_t total = w.R + w.closing;
+    const int64_t gran = scan_granules(total, 2);
+    if ((rc = import_merged(cs, a, total + 1))) return rc;
+    if ((rc = cs->i_dstate.ensure(8 * (size_t)(kIdWords + gran)))) return rc;
+    import_tiers(cs, a, true);
+    d.dwords = (int64_t*)cs->i_dstate.p;
+    hipStream_t s = cs->stream;
+    HIPOK(hipMemsetAsync(cs->i_dstate.p, 0, 8 * (size_t)(kIdWords + gran), s));
+    HIPOK(hipEventRecord(cs->i_ev[2], s));
+    HIPOK(hipMemsetAsync(cs->i_mlt.p, 0, 8 * (size_t)(total + 1), s));
+    launch_import_delta_merge(s, d, (uint64_t*)cs->i_dstate.p + kIdWords);
+    HIPOK(take_launch_error());
+    HIPOK(hipEventRecord(cs->i_ev[3], s));
+    HIPOK(hipMemcpyAsync(pl.dw, cs->i_dstate.p, sizeof(pl.dw), hipMemcpyDeviceToHost, s));
+    HIPOK(hipStreamSynchronize(s));
+    cs->i_ms_kernels += ev_ms(cs->i_ev[2], cs->i_ev[3]);
+    if ((int32_t)dw[kIdError] & 8) return FDBCS_E_NOMEM;
+    if (dw[kIdError] || ((const int32_t*)&dw[kIdScan])[1]) return FDBCS_E_DEVICE;
+    const int64_t kept = dw[kIdKept], units = dw[kIdTailUnits];
+    const int64_t nd_new = w.p_lo + kept + (nd - w.p_hi);
+    if (kept < 0 || kept > total || nd_new > cs->delta_cap || units < 0 || units > pl.u_end) return FDBCS_E_DEVICE;
+    // success: the delta buffer the kernels filled becomes current, the appended tails count
+    const int64_t tail_used = units ? 8 * (d.tail_base + units) : sc.tail_used;
+    cs->dcur ^= 1;
+    sc.nd = nd_new;
+    sc.ndb[cs->dcur] = nd_new;
+    sc.tail_used = tail_used;
+    HIPOK(hipMemcpyAsync(cs->scal.p, &sc, sizeof(sc), hipMemcpyHostToDevice, s));
+    if ((rc = import_finish(cs, a, true, nd_new))) return rc;
+    cs->nd_ub = nd_new;  // exact: the next batch's compaction trigger counts the import
+    cs->tail_ub = tail_used;
+    *boundaries_out = nb + nd_new;
+    import_note(cs, 1, nb, nd, nd_new);
+    return FDBCS_OK;
+}
+
+static int import_arrays(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key,
+                         int32_t hi_len, int64_t n, const uint8_t* key_bytes, const int64_t* key_offsets,
+                         const int64_t* versions, int64_t header_version, int64_t* boundaries_out, bool to_delta) {
+    if (!cs || !boundaries_out || n < 0 || (n > 0 && (!key_offsets || !versions))) return FDBCS_E_INVALID;
+    if (int rc = import_bounds_ok(lo_key, lo_len, hi_key, hi_len)) return rc;
+    const int64_t nbytes = n ? key_offsets[n] : 0;
+    if (nbytes < 0 || (nbytes > 0 && !key_bytes)) return FDBCS_E_INVALID;
+    if (cs->inflight) return FDBCS_E_STATE;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPOK(hipSetDevice(cs->device));
+    if (int rc = sync_all(cs)) return rc;
+    cs->x_valid = false;
+    // the three arrays go up as they are
+    int rc;
+    if ((rc = cs->i_bytes.ensure((size_t)nbytes + 64))) return rc;
+    if ((rc = cs->i_off.ensure(8 * (size_t)(n + 1)))) return rc;
+    if ((rc = cs->i_ver.ensure(8 * (size_t)(n + 1)))) return rc;
+    hipStream_t s = cs->stream;
+    if (nbytes) HIPOK(hipMemcpyAsync(cs->i_bytes.p, key_bytes, (size_t)nbytes, hipMemcpyHostToDevice, s));
+    if (n) {
+        HIPOK(hipMemcpyAsync(cs->i_off.p, key_offsets, 8 * (size_t)(n + 1), hipMemcpyHostToDevice, s));
+        HIPOK(hipMemcpyAsync(cs->i_ver.p, versions, 8 * (size_t)n, hipMemcpyHostToDevice, s));
+    }
+    rc = (to_delta ? import_delta_device : import_device)(
+        cs, lo_key, lo_len, hi_key, hi_len, n, (const uint8_t*)cs->i_bytes.p, nbytes, (const int64_t*)cs->i_off.p,
+        (const int64_t*)cs->i_ver.p, header_version, boundaries_out);
+    cs->i_ms_host = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return rc;
+}
+
+static int import_pending(fdbcs_conflict_set* dst, fdbcs_conflict_set* src, const uint8_t* lo_key, int32_t lo_len,
+                          const uint8_t* hi_key, int32_t hi_len, int64_t* boundaries_out, bool to_delta) {
+    if (!dst || !src || src == dst || !boundaries_out || src->device != dst->device) return FDBCS_E_INVALID;
+    if (int rc = import_bounds_ok(lo_key, lo_len, hi_key, hi_len)) return rc;
+    if (dst->inflight || src->inflight || !src->x_valid) return FDBCS_E_STATE;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPOK(hipSetDevice(dst->device));
+    if (int rc = sync_all(dst)) return rc;
+    dst->x_valid = false;
+    // src's export finished on its own stream before fdbcs_history_export returned: its result
+    // arrays are read in place, and stay pending
+    const int rc = (to_delta ? import_delta_device : import_device)(
+        dst, lo_key, lo_len, hi_key, hi_len, src->x_n, (const uint8_t*)src->x_bytes.p, src->x_nbytes,
+        (const int64_t*)src->x_off.p, (const int64_t*)src->x_ver.p, src->x_hdr, boundaries_out);
+    dst->i_ms_host = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return rc;
+}
+
+int fdbcs_history_import(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key,
+                         int32_t hi_len, int64_t n, const uint8_t* key_bytes, const int64_t* key_offsets,
+                         const int64_t* versions, int64_t header_version, int64_t* boundaries_out) {
+    return import_arrays(cs, lo_key, lo_len, hi_key, hi_len, n, key_bytes, key_offsets, versions, header_version,
+                         boundaries_out, false);
+}
+
+int fdbcs_history_import_pending(fdbcs_conflict_set* dst, fdbcs_conflict_set* src, const uint8_t* lo_key, int32_t lo_len,
+                                 const uint8_t* hi_key, int32_t hi_len, int64_t* boundaries_out) {
+    return import_pending(dst, src, lo_key, lo_len, hi_key, hi_len, boundaries_out, false);
+}
+
+int fdbcs_history_import_delta(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key,
+                               int32_t hi_len, int64_t n, const uint8_t* key_bytes, const int64_t* key_offsets,
+                               const int64_t* versions, int64_t header_version, int64_t* boundaries_out) {
+    return import_arrays(cs, lo_key, lo_len, hi_key, hi_len, n, key_bytes, key_offsets, versions, header_version,
+                         boundaries_out, true);
+}
+
+int fdbcs_history_import_delta_pending(fdbcs_conflict_set* dst, fdbcs_conflict_set* src, const uint8_t* lo_key,
+                                       int32_t lo_len, const uint8_t* hi_key, int32_t hi_len, int64_t* boundaries_out) {
+    return import_pending(dst, src, lo_key, lo_len, hi_key, hi_len, boundaries_out, true);
+}
+
+int fdbcs_history_import_info(fdbcs_conflict_set* cs, int32_t* path, int64_t* base_boundaries, int64_t* delta_before,
+                              int64_t* delta_after) {
+    if (!cs || !path || !base_boundaries || !delta_before || !delta_after) return FDBCS_E_INVALID;
+    *path = cs->i_path;
+    *base_boundaries = cs->i_info_base;
+    *delta_before = cs->i_info_before;
+    *delta_after = cs->i_info_after;
+    return FDBCS_OK;
+}
+
+int fdbcs_history_import_timing(fdbcs_conflict_set* cs, double* ms_kernels, double* ms_host) {
+    if (!cs || !ms_kernels || !ms_host) return FDBCS_E_INVALID;
+    *ms_kernels = cs->i_ms_kernels;
+    *ms_host = cs->i_ms_host;
+    return FDBCS_OK;
+}
+
+// ---- the resolver's iops sample of a routed batch (Resolver.actor.cpp:178-192)
+
+int fdbcs_batch_set_iops_sample(fdbcs_batch* b, int32_t units, uint64_t seed) {
+    if (!b || units < 1) return FDBCS_E_INVALID;
+    if (!b->cs || !b->routed || b->state >= 2) return FDBCS_E_STATE;
+    // the scan counts key bytes in 32 bits: every begin key's 16 prefix bytes and the whole tail arena bound them
+    const int64_t cap = b->r_cap_ranges, bytes_cap = 16 * cap + b->r_cap_tail;
+    if (bytes_cap >= ((int64_t)1 << 32)) return FDBCS_E_NOMEM;
+    fdbcs_conflict_set* cs = b->cs;
+    HIPOK(hipSetDevice(cs->device));
+    BatchSlot* sl = b->slot;
+    if (sl->is_inflight) {  // a request replaced: its kernel is over before its buffers are touched
+        HIPOK(hipEventSynchronize(sl->ev_is1));
+        sl->is_inflight = false;
+    }
+    b->is_req = b->is_done = false;
+    int rc;
+    const size_t state_bytes = 8 * (size_t)iops_scan_words(cap);
+    if ((rc = sl->is_state.ensure(state_bytes))) return rc;
+    if ((rc = sl->is_met.ensure(4 * (size_t)(cap + 1)))) return rc;
+    if ((rc = sl->is_idx.ensure(4 * (size_t)(cap + 1)))) return rc;
+    if ((rc = sl->is_off.ensure(8 * (size_t)(cap + 1)))) return rc;
+    if ((rc = sl->is_bytes.ensure((size_t)bytes_cap + 64))) return rc;
+    if ((rc = sl->is_tot.ensure(sizeof(IopsTotals), true))) return rc;
+    if (!sl->ev_is0) HIPOK(hipEventCreate(&sl->ev_is0));
+    if (!sl->ev_is1) HIPOK(hipEventCreate(&sl->ev_is1));
+    IopsArgs a{};
+    a.keys = b->bd.keys;
+    a.tail = b->bd.tail;
+    a.dres = (const RouteResult*)sl->rt_dres.p;
+    a.units = (uint32_t)units;
+    a.seed = seed;
+    a.cap = cap;
+    a.bytes_cap = bytes_cap;
+    a.metrics = (int32_t*)sl->is_met.p;
+    a.index = (int32_t*)sl->is_idx.p;
+    a.key_offsets = (int64_t*)sl->is_off.p;
+    a.bytes = (uint8_t*)sl->is_bytes.p;
+    a.totals = (IopsTotals*)sl->is_tot.dp;
+    ((IopsTotals*)sl->is_tot.p)->n = -1;  // not written yet
+    // behind the routing kernels and the ev_up record on their stream: the detect pipeline waits
+    // for ev_up only, so it never waits for the sample
+    hipStream_t us = cs->ustream;
+    HIPOK(hipMemsetAsync(sl->is_state.p, 0, state_bytes, us));
+    uint64_t* sw = (uint64_t*)sl->is_state.p;
+    ScanState st{sw + 8, (int*)sw, (int*)(sw + 1)};
+    t_record = nullptr;
+    HIPOK(hipEventRecord(sl->ev_is0, us));
+    launch_iops_sample(us, a, st);
+    HIPOK(take_launch_error());
+    HIPOK(hipEventRecord(sl->ev_is1, us));
+    sl->is_inflight = true;
+    b->is_req = true;
+    return FDBCS_OK;
+}
+
+int fdbcs_batch_iops_sample(fdbcs_batch* b, int64_t* n_out, int64_t* key_bytes_out) {
+    if (!b || !n_out || !key_bytes_out) return FDBCS_E_INVALID;
+    if (!b->cs) return FDBCS_E_STATE;
+    HIPOK(hipSetDevice(b->cs->device));
+    if (int rc = finish_route(b)) return rc;  // the routing's error first (the request went with the batch)
+    if (!b->is_req) return FDBCS_E_STATE;
+    BatchSlot* sl = b->slot;
+    if (!b->is_done) {
+        HIPOK(hipEventSynchronize(sl->ev_is1));
+        sl->is_inflight = false;
+        std::atomic_thread_fence(std::memory_order_acquire);
+        IopsTotals t;
+        memcpy(&t, (const void*)sl->is_tot.p, sizeof(t));
+        int32_t words[4];  // the scan's counter and error words
+        HIPOK(hipMemcpy(words, sl->is_state.p, sizeof(words), hipMemcpyDeviceToHost));
+        if (words[2] || t.n < 0) return FDBCS_E_DEVICE;  // look-back bound, key buffer
+        b->is_n = t.n;
+        b->is_nbytes = t.key_bytes;
+        b->is_ms = ev_ms(sl->ev_is0, sl->ev_is1);
+        b->is_done = true;
+    }
+    *n_out = b->is_n;
+    *key_bytes_out = b->is_nbytes;
+    return FDBCS_OK;
+}
+
+int fdbcs_batch_iops_sample_read(fdbcs_batch* b, uint8_t* key_bytes, int64_t key_bytes_cap, int64_t* key_offsets,
+                                 int32_t* metrics, int32_t* index, int64_t cap) {
+    if (!b || key_bytes_cap < 0 || cap < 0 || !key_offsets) return FDBCS_E_INVALID;
+    if (!b->cs || !b->is_req || !b->is_done) return FDBCS_E_STATE;
+    if (cap < b->is_n || key_bytes_cap < b->is_nbytes) return FDBCS_E_NOMEM;
+    if ((b->is_n && !metrics) || (b->is_nbytes && !key_bytes)) return FDBCS_E_INVALID;
+    HIPOK(hipSetDevice(b->cs->device));
+    const BatchSlot* sl = b->slot;
+    if (b->is_n && index) HIPOK(hipMemcpy(index, sl->is_idx.p, 4 * (size_t)b->is_n, hipMemcpyDeviceToHost));
+    return copy_keyed_result(b->is_n, b->is_nbytes, metrics, sl->is_met.p, 4, key_offsets, sl->is_off.p, key_bytes,
+                             sl->is_bytes.p);
+}
+
+int fdbcs_batch_iops_sample_timing(fdbcs_batch* b, double* ms_kernels) {
+    if (!b || !ms_kernels) return FDBCS_E_INVALID;
+    if (!b->is_req || !b->is_done) return FDBCS_E_STATE;
+    *ms_kernels = b->is_ms;
+    return FDBCS_OK;
+}
+
+}  // extern "C"

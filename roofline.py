@@ -26,6 +26,8 @@ import json
 import math
 import os
 
+from foundationdb_amd import build as _build
+
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak (MI355X_MICROARCH.md, chip-level parameters)
 P, V, D, I = 16, 8, 24, 32
 NODE = 128
@@ -210,10 +212,8 @@ def sort_phase(table: dict) -> dict | None:
 
 # Sources whose content defines the kernels a profile measured: a profile whose build id differs
 # from the running tree's describes other code and is not used.
-BUILD_SOURCES = ("foundationdb_amd/csrc/kernels.hip", "foundationdb_amd/csrc/engine.cpp",
-                 "foundationdb_amd/csrc/engine.h", "foundationdb_amd/csrc/scan.h", "foundationdb_amd/csrc/launch.h",
-                 "foundationdb_amd/csrc/dkey.h", "foundationdb_amd/csrc/lane_xor.h",
-                 "include/fdb_conflict_set.h")
+# foundationdb_amd/build.py owns the list of engine sources.
+BUILD_SOURCES = tuple(f"foundationdb_amd/csrc/{f}" for f in _build.SOURCES + _build.HEADERS) + (_build.PUBLIC_HEADER,)
 
 
 def build_id(root: str) -> str:

@@ -3,7 +3,7 @@ or a write's key over a tier's boundaries) held to the key-space model (tests/ke
 keys of different lengths.  Built on the CPU from the model alone; every count a family is meant to
 reach is asserted here while the plan is built, and the engine is never consulted for it.
 
-The engine has four forms of the search (foundationdb_amd/csrc/kernels.hip): lane_lower_bound (A),
+The engine has four forms of the search (foundationdb_amd/csrc/search.h): lane_lower_bound (A),
 lane_lower_bound_long with lane_sample_range / lane_prefix_run / load_qtail and the run search (B, a
 batch with a key over 24 bytes), group_lower_bound (C, the merge of a short-key batch below
 kSegWideMinW = 24576 writes) and prev_seg_hit_quad (D, the previous batch's union segments).  A read

@@ -15,7 +15,7 @@ from tests.route_map_helpers import MapRouted, gather, moves_recipe, tx
 
 pytestmark = pytest.mark.gpu
 
-TILE = 256  # engine.h kIopsTile: ranges per workgroup of the sample's scan (one per thread)
+TILE = 256  # transfer.h kIopsTile: ranges per workgroup of the sample's scan (one per thread)
 
 
 def want_of(sub, units, seed):
