@@ -21,7 +21,7 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 
 from .balancing import KEY_BYTES_PER_SAMPLE
-from .packing import CommitTransaction, InvertedRange, PackedBatch, _CPackedBatch
+from .packing import CommitTransaction, DevicePackedBatch, InvertedRange, PackedBatch, _CPackedBatch, _CPackedBatchDev
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FDBCS_LIB") or os.path.join(_HERE, "libfdbcs.so")
@@ -183,6 +183,11 @@ SIGNATURES = {
     "fdbcs_batch_iops_sample": (ctypes.c_int, [_VP, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     "fdbcs_batch_iops_sample_read": (ctypes.c_int, [_VP, _VP, _I64, _VP, _VP, _VP, _I64]),
     "fdbcs_batch_iops_sample_timing": (ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_double)]),
+    "fdbcs_batch_add_packed_device": (ctypes.c_int, [_VP, ctypes.POINTER(_CPackedBatchDev), _VP, ctypes.c_uint32]),
+    "fdbcs_batch_device_add_info": (ctypes.c_int, [_VP, ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I32),
+                                                   ctypes.POINTER(_I64)]),
+    "fdbcs_batch_device_add_timing": (ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_double),
+                                                     ctypes.POINTER(ctypes.c_double)]),
     "fdbcs_debug_kernel_time": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
     "fdbcs_kernel_profile": (ctypes.c_int, [_VP, _I32, ctypes.c_char_p, _I32, ctypes.POINTER(_I64),
                                             ctypes.POINTER(ctypes.c_double)]),
@@ -575,6 +580,45 @@ class ConflictBatch:
             self._report.extend(bool(x) for x in pb.report)
             self._has_reads.extend((np.diff(pb.read_offsets) > 0).tolist())
 
+    def add_packed_device(self, dpb: DevicePackedBatch, ready_ptr: int = 0, ready_value: int = 0) -> None:
+        """fdbcs_batch_add_packed_device: addTransaction of every transaction of a packed batch whose
+        arrays are in device memory, on a new batch; validated and normalized by kernels, which run
+        once the uint32 at device address `ready_ptr` equals `ready_value` (0: the arrays are
+        complete).  The host reads none of the arrays; they stay untouched until device_add_info()
+        or detect has returned.  TooOld is judged at detect, as for a routed batch.  Any error
+        status raises FdbcsError; a violation the kernels find comes from device_add_info() or
+        detect (FDBCS_E_INVALID), and leaves the batch empty."""
+        c = dpb.c_struct()
+        rc = load_library().fdbcs_batch_add_packed_device(self._h, ctypes.byref(c), _VP(ready_ptr or None),
+                                                          int(ready_value) & 0xFFFFFFFF)
+        if rc != FDBCS_OK:
+            raise FdbcsError(rc, "addPackedDevice")
+        self.transaction_count = int(dpb.n_txn)
+        self._dev_added = True
+
+    def device_add_info(self) -> Tuple[int, int, int, int]:
+        """fdbcs_batch_device_add_info: blocks until the add kernels have run; (transactions, reads,
+        writes, tail bytes) of the device-added batch, or their error (FdbcsError; the batch is then
+        empty again)."""
+        T, R, W, tb = _I32(), _I32(), _I32(), _I64()
+        rc = load_library().fdbcs_batch_device_add_info(self._h, ctypes.byref(T), ctypes.byref(R), ctypes.byref(W),
+                                                        ctypes.byref(tb))
+        if rc != FDBCS_OK:
+            if rc != FDBCS_E_STATE:
+                self.transaction_count = 0
+                self._dev_added = False
+            raise FdbcsError(rc, "deviceAddInfo")
+        return T.value, R.value, W.value, tb.value
+
+    def device_add_timing(self) -> Tuple[float, float]:
+        """Milliseconds of the add kernels (device) and inside the add call (host), once
+        device_add_info() or detect has returned."""
+        a, b = ctypes.c_double(), ctypes.c_double()
+        rc = load_library().fdbcs_batch_device_add_timing(self._h, ctypes.byref(a), ctypes.byref(b))
+        if rc != FDBCS_OK:
+            raise FdbcsError(rc, "deviceAddTiming")
+        return a.value, b.value
+
     def upload(self) -> None:
         _check(load_library().fdbcs_batch_upload(self._h), "upload")
 
@@ -748,9 +792,10 @@ class ConflictBatch:
         m = self.conflicting_key_range_map
         if m is None:
             return
-        if getattr(self, "_routed", False):
+        if getattr(self, "_routed", False) or getattr(self, "_dev_added", False):
             # a routed batch's sub-transactions were placed on the device: the engine says which
-            # have an entry; the indices are the sub-transaction's own (this resolver's map)
+            # have an entry; the indices are the sub-transaction's own (this resolver's map).  A
+            # device-added batch's flags and offsets were never on the host either
             for t in np.flatnonzero(self.report_entries()).tolist():
                 entry = m.setdefault(t, [])
                 if self.verdicts[t] == TransactionConflict:

@@ -485,6 +485,11 @@ void release_slot(BatchSlot* sl) {
     if (sl->ev_rt1) (void)hipEventDestroy(sl->ev_rt1);
     if (sl->ev_is0) (void)hipEventDestroy(sl->ev_is0);
     if (sl->ev_is1) (void)hipEventDestroy(sl->ev_is1);
+    if (sl->ev_da0) (void)hipEventDestroy(sl->ev_da0);
+    if (sl->ev_da1) (void)hipEventDestroy(sl->ev_da1);
+    sl->da_scan.release();
+    sl->da_dres.release();
+    sl->da_res.release();
     sl->is_state.release();
     sl->is_met.release();
     sl->is_idx.release();
@@ -509,12 +514,9 @@ void release_slot(BatchSlot* sl) {
     delete sl;
 }
 
-// Layout of a batch in pin_in / dev: [keys | rowner | wowner | snap | roff | woff | flags | tail].
+// Layout of a batch in pin_in / dev (UploadLayout, engine_impl.h).
 // add_packed normalizes keys, owners and tails in place; the tail region is last so a capacity
 // sized for an upper bound of the tail bytes costs no upload.
-struct UploadLayout {
-    size_t keys, rown, wown, snap, roff, woff, flags, tail, total;
-};
 UploadLayout upload_layout(size_t T, size_t R, size_t W, size_t tail_bytes) {
     UploadLayout L;
     size_t off = 0;
@@ -1928,6 +1930,7 @@ int fdbcs_batch_add_routed_map(fdbcs_batch* b, const void* shares, int64_t strid
 // Sizes of a routed batch, once its route kernels are done (blocks until then).
 extern "C++" int fdbcs::impl::finish_route(fdbcs_batch* b) {
     if (!b->route_pending) return FDBCS_OK;
+    if (b->dev_added) return finish_device_add(b);
     BatchSlot* sl = b->slot;
     HIPOK(hipEventSynchronize(sl->ev_up));
     std::atomic_thread_fence(std::memory_order_acquire);
@@ -1970,7 +1973,7 @@ extern "C++" int fdbcs::impl::finish_route(fdbcs_batch* b) {
 
 int fdbcs_batch_routed_info(fdbcs_batch* b, int32_t* T, int32_t* R, int32_t* W, void** inv_dev, void** read_ids_dev) {
     if (!b) return FDBCS_E_INVALID;
-    if (!b->routed) return FDBCS_E_STATE;
+    if (!b->routed || b->dev_added) return FDBCS_E_STATE;
     if (int rc = finish_route(b)) return rc;
     if (T) *T = b->rT;
     if (R) *R = b->rR;
@@ -2120,7 +2123,7 @@ static int detect_bind_results(fdbcs_conflict_set* cs, fdbcs_batch* b, DetectPla
     b->h_roff = b->routed ? (const int32_t*)(ho + RL.ro) : b->roff.data();
     b->h_flags = b->routed ? (const uint8_t*)(ho + RL.fg) : b->flags.data();
     if ((rc = sl->dverdict.ensure(T + 64))) return rc;
-    if (b->out_dev && b->out_n > 0 && !b->routed) {
+    if (b->out_dev && b->out_n > 0 && (!b->routed || b->dev_added)) {  // (a device-added batch: host txn_ids)
         // global -> batch transaction map, read by k_conflict_output straight from host-mapped
         // memory (n_global * 4 bytes; the slot's previous batch finished with it: its flag was seen)
         if ((int64_t)b->out_ids.size() != T) return FDBCS_E_STATE;  // transactions added after the call
@@ -2352,7 +2355,8 @@ static void record_half_x(fdbcs_conflict_set* cs, fdbcs_batch* b, DetectPlan& p)
     launch_resolve(s, bd, w, b->any_report, (uint8_t*)sl->pin_out.dp, p.sc);
     w.vdev = nullptr;
     if (b->out_dev && b->out_n > 0)  // multi-resolver combine input, final before the completion flag
-        launch_conflict_output(s, bd, w, b->routed ? (const int32_t*)sl->rt_inv.p : (const int32_t*)sl->pin_inv.dp,
+        launch_conflict_output(s, bd, w,
+                               b->routed && !b->dev_added ? (const int32_t*)sl->rt_inv.p : (const int32_t*)sl->pin_inv.dp,
                                b->out_n, b->out_dev);
     if (b->any_report) {  // before the epilogue re-zeroes hist_conf (into the host-mapped results)
         char* hdv = (char*)sl->pin_out.dp;
@@ -2749,7 +2753,7 @@ static int account_stats(fdbcs_conflict_set* cs, fdbcs_batch* b) {
     }
     st.gc_runs += b->gc_ran ? 1 : 0;
     st.sort_big_buckets += b->h_scal->sort_big;
-    if (b->routed && b->slot->rt_timed) {
+    if (b->routed && !b->dev_added && b->slot->rt_timed) {
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, b->slot->ev_rt0, b->slot->ev_rt1) == hipSuccess) st.ms_route_kernels += ms;
         st.routed_batches += 1;
@@ -2865,7 +2869,7 @@ int fdbcs_batch_set_conflict_output(fdbcs_batch* b, const int32_t* txn_ids, int3
 
 int fdbcs_batch_set_report_output(fdbcs_batch* b, uint8_t* dev_out, int64_t n_global_reads) {
     if (!b || !dev_out || n_global_reads < 0) return FDBCS_E_INVALID;
-    if (!b->cs || !b->routed || !b->report_enabled || b->state >= 2) return FDBCS_E_STATE;
+    if (!b->cs || !b->routed || b->dev_added || !b->report_enabled || b->state >= 2) return FDBCS_E_STATE;
     // the size is compared with the shares' reads at detect, once the routing kernels have run
     b->rep_dev = dev_out;
     b->rep_n = n_global_reads;

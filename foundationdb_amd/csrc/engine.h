@@ -1,6 +1,7 @@
 // engine.h — internal interface between the host engine (engine.cpp) and the
 // gfx950 kernels of the detect pipeline (kernels.hip).  Not part of the public C-ABI.  The maintenance
-// side (history export and import, the iops sample) has its own: transfer.h.
+// side (history export and import, the iops sample) has its own, transfer.h, and so has the add of
+// whole batches from device memory: ingest.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,5 +1,6 @@
 // engine_impl.h — the host engine's state, shared by engine.cpp (the detect pipeline and the C-ABI's
-// lifecycle calls) and transfer.cpp (history export and import, the iops sample): the buffer types,
+// lifecycle calls), transfer.cpp (history export and import, the iops sample) and ingest.cpp (whole
+// batches added from device memory): the buffer types,
 // the definitions of the conflict set, the batch and its staging slot, and the helpers of engine.cpp
 // that the maintenance entry points call.  Internal: nothing outside csrc/ includes it.
 #pragma once
@@ -452,6 +453,11 @@ struct BatchSlot {
     HBuf is_tot;
     hipEvent_t ev_is0 = nullptr, ev_is1 = nullptr;
     bool is_inflight = false;
+    // fdbcs_batch_add_packed_device: scan state, the device and host-mapped totals and the events
+    // around the add kernels, all allocated by the slot's first device-added batch
+    DBuf da_scan, da_dres;
+    HBuf da_res;
+    hipEvent_t ev_da0 = nullptr, ev_da1 = nullptr;
     // per-kernel events of the batch (timing level 3, or the timed kernel at level 1)
     std::vector<hipEvent_t> prof_pool;
     size_t prof_next = 0;
@@ -518,6 +524,12 @@ struct fdbcs_batch {
     // (the wait-time report loop reads them; other batches read the host vectors above)
     const int32_t* h_roff = nullptr;
     const uint8_t* h_flags = nullptr;
+    // device-added batch (fdbcs_batch_add_packed_device): built on the device like a routed one, so
+    // it is `routed` too (sizes in rT / rR / rW, known at the call; TooOld judged at detect; roff |
+    // flags copied into the result buffer) and this flag tells it apart: no global map, no read
+    // ids, no sample, and its conflict output takes the host txn_ids
+    bool dev_added = false;
+    double da_ms_host = 0, da_ms_kernels = 0;  // of its add call / add kernels (fdbcs_batch_device_add_timing)
 
     int32_t T() const { return routed ? rT : (int32_t)snap.size(); }
     int32_t R() const { return routed ? rR : roff.back(); }
@@ -540,4 +552,16 @@ int ensure_history(fdbcs_conflict_set* cs, int64_t need, int64_t tail_need);
 int64_t delta_limit_for(const fdbcs_conflict_set* cs, int64_t n_base);  // delta size that triggers a compaction
 double ev_ms(hipEvent_t a, hipEvent_t b);
 int finish_route(fdbcs_batch* b);  // wait for a routed batch's routing and take its sizes and error
+// Its sibling for a device-added batch (ingest.cpp; finish_route hands such a batch over): wait for
+// the add kernels and take the totals; on an error the batch is empty again.
+int finish_device_add(fdbcs_batch* b);
+// Layout of a batch in pin_in / dev: [keys | rowner | wowner | snap | roff | woff | flags | tail].
+struct UploadLayout {
+    size_t keys, rown, wown, snap, roff, woff, flags, tail, total;
+};
+UploadLayout upload_layout(size_t T, size_t R, size_t W, size_t tail_bytes);
+// Every allocation a batch of this shape needs (device copy, pinned results, device verdicts), and
+// the slot's phase and upload events.
+int ensure_slot(BatchSlot* sl, size_t upload_bytes, size_t T, size_t R);
+int make_slot_events(BatchSlot* sl);
 }  // namespace fdbcs::impl

@@ -515,7 +515,7 @@ int fdbcs_history_import_timing(fdbcs_conflict_set* cs, double* ms_kernels, doub
 
 int fdbcs_batch_set_iops_sample(fdbcs_batch* b, int32_t units, uint64_t seed) {
     if (!b || units < 1) return FDBCS_E_INVALID;
-    if (!b->cs || !b->routed || b->state >= 2) return FDBCS_E_STATE;
+    if (!b->cs || !b->routed || b->dev_added || b->state >= 2) return FDBCS_E_STATE;
     // the scan counts key bytes in 32 bits: every begin key's 16 prefix bytes and the whole tail arena bound them
     const int64_t cap = b->r_cap_ranges, bytes_cap = 16 * cap + b->r_cap_tail;
     if (bytes_cap >= ((int64_t)1 << 32)) return FDBCS_E_NOMEM;

@@ -210,6 +210,46 @@ class PackedBatch:
         return PackedBatch(read_snapshot, report, read_offsets, write_offsets, kb, koff)
 
 
+class _CPackedBatchDev(ctypes.Structure):
+    """fdbcs_packed_batch_dev."""
+    _fields_ = [
+        ("n_txn", ctypes.c_int32),
+        ("n_reads", ctypes.c_int32),
+        ("n_writes", ctypes.c_int32),
+        ("key_bytes_len", ctypes.c_int64),
+        ("read_snapshot", ctypes.c_void_p),
+        ("report_conflicting_keys", ctypes.c_void_p),
+        ("read_offsets", ctypes.c_void_p),
+        ("write_offsets", ctypes.c_void_p),
+        ("key_bytes", ctypes.c_void_p),
+        ("key_offsets", ctypes.c_void_p),
+    ]
+
+
+@dataclass
+class DevicePackedBatch:
+    """A packed batch whose six arrays live in device memory (``fdbcs_packed_batch_dev``): device
+    addresses and sizes only.  Whoever owns the memory (torch tensors, another allocator) keeps it
+    alive and unchanged until ``ConflictBatch.device_add_info()`` or detect has returned; `report`
+    may be 0 (no transaction reports)."""
+
+    n_txn: int
+    n_reads: int
+    n_writes: int
+    key_bytes_len: int
+    read_snapshot: int  # int64[T]
+    report: int  # uint8[T] or 0
+    read_offsets: int  # int32[T+1]
+    write_offsets: int  # int32[T+1]
+    key_bytes: int  # uint8[key_bytes_len], any alignment
+    key_offsets: int  # int64[2(R+W)+1]
+
+    def c_struct(self) -> _CPackedBatchDev:
+        return _CPackedBatchDev(int(self.n_txn), int(self.n_reads), int(self.n_writes), int(self.key_bytes_len),
+                                *[int(p) or None for p in (self.read_snapshot, self.report, self.read_offsets,
+                                                           self.write_offsets, self.key_bytes, self.key_offsets)])
+
+
 def pack_keys(keys: Sequence[bytes]):
     """(key_bytes, key_offsets) for a list of keys, e.g. a sorted history to bulk-load."""
     lens = np.array([len(k) for k in keys], dtype=np.int64)

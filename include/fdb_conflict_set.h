@@ -312,8 +312,8 @@ int fdbcs_batch_conflicting_reads(fdbcs_batch* b, int32_t txn, int32_t* idx_out,
  * so far whose add-time TooOld test held (read_snapshot < oldestVersion with at least one read,
  * SkipList.cpp:770), ascending; valid right after the adds, before detect, as in the reference.
  * Writes at most cap indices (idx_out may be NULL to count).  A routed batch
- * (fdbcs_batch_add_routed) is judged at detect on the device: FDBCS_E_STATE (read its verdict
- * bytes instead). */
+ * (fdbcs_batch_add_routed) or a device-added one (fdbcs_batch_add_packed_device) is judged at
+ * detect on the device: FDBCS_E_STATE (read its verdict bytes instead). */
 int fdbcs_batch_too_old(fdbcs_batch* b, int32_t* idx_out, int32_t cap, int32_t* n_out);
 /* Device pointer to the batch's per-transaction verdict bytes (valid after
  * detect until the batch is destroyed) for on-device combine (RCCL). */
@@ -470,6 +470,66 @@ int fdbcs_batch_iops_sample(fdbcs_batch* b, int64_t* n_out, int64_t* key_bytes_o
 int fdbcs_batch_iops_sample_read(fdbcs_batch* b, uint8_t* key_bytes, int64_t key_bytes_cap, int64_t* key_offsets,
                                  int32_t* metrics, int32_t* index /* may be NULL */, int64_t cap);
 int fdbcs_batch_iops_sample_timing(fdbcs_batch* b, double* ms_kernels);
+
+/* A whole batch from device memory, normalized on the GPU.  The six arrays of fdbcs_packed_batch,
+ * same meaning and layout, in DEVICE memory of the set's GPU (any allocator), with the sizes the
+ * host knows anyway (they are message sizes): T = n_txn, R = n_reads, W = n_writes and the bytes of
+ * key_bytes.  key_bytes may start at any byte and needs no slack after its last byte;
+ * report_conflicting_keys may be NULL (= all false). */
+typedef struct fdbcs_packed_batch_dev {
+    int32_t n_txn, n_reads, n_writes;
+    int64_t key_bytes_len;
+    const int64_t* read_snapshot;           /* [n_txn] */
+    const uint8_t* report_conflicting_keys; /* [n_txn] or NULL */
+    const int32_t* read_offsets;            /* [n_txn+1] */
+    const int32_t* write_offsets;           /* [n_txn+1] */
+    const uint8_t* key_bytes;               /* [key_bytes_len] */
+    const int64_t* key_offsets;             /* [2*(R+W)+1] */
+} fdbcs_packed_batch_dev;
+/* fdbcs_batch_add_packed_device: on a new, empty batch, addTransaction (SkipList.cpp:763-794) of
+ *     every transaction of the arrays, in order.  FDBCS_E_STATE on a batch that holds anything, is
+ *     routed or is detected, and from every add call made after it on the same batch; n_txn == 0 is
+ *     FDBCS_OK and the batch stays empty.  The host does no work per transaction, range or key and
+ *     reads none of the arrays: it sizes the batch's buffers from T, R, W and key_bytes_len,
+ *     enqueues the add kernels and returns.  They run once the device word *ready_flag equals
+ *     ready_value (as for fdbcs_batch_add_routed; NULL: the arrays are complete), on the stream the
+ *     routing kernels use, off the detect pipeline's chains; the wait is bounded by
+ *     FDBCS_ROUTE_TIMEOUT_MS (FDBCS_E_TIMEOUT past it).  The arrays must stay unchanged until
+ *     fdbcs_batch_device_add_info or detect has returned (both block until the add kernels have
+ *     run); after that they may be reused: keys are copied.
+ *     Every range is kept, in input order: read r of the arrays is the batch's read r, write w its
+ *     write w.  The TooOld test (SkipList.cpp:770) is made when the batch is detected, by the routed
+ *     batch's rule, against the oldest version every earlier detect of the set left: the value
+ *     addTransaction sees in the Resolver's order (Resolver.actor.cpp:139-150, 179-194).  A TooOld
+ *     transaction keeps its ranges, which are inert.  This differs from fdbcs_batch_add_packed,
+ *     which tests at the call, only for a batch added ahead of an earlier batch's detect;
+ *     fdbcs_batch_too_old is FDBCS_E_STATE (read the verdict bytes), as for a routed batch.
+ *     Refused by the host before anything is enqueued: FDBCS_E_INVALID for a NULL pointer where a
+ *     size says the array is read, a negative size or n_txn over the engine's batch limit (49152);
+ *     FDBCS_E_NOMEM for key_bytes_len >= 2^32, R + W >= 2^28 or a capacity failure.  Everything else
+ *     is validated on the device: read_offsets[0] == write_offsets[0] == 0, both non-decreasing,
+ *     read_offsets[T] == n_reads, write_offsets[T] == n_writes, key_offsets non-decreasing inside
+ *     [0, key_bytes_len], and no inverted range (FDBTypes.h:288-291) in the full byte order, tails
+ *     and the ranges of TooOld transactions included.  No address is formed from a value of the
+ *     arrays before it is checked.  A violation surfaces as FDBCS_E_INVALID from
+ *     fdbcs_batch_device_add_info or detect; the batch is then empty again and can be added anew,
+ *     and the set is exactly as before.
+ *     Afterwards fdbcs_batch_set_conflict_output (with its host txn_ids), sync and async detect,
+ *     fdbcs_batch_conflicting_reads, fdbcs_batch_report_entries and fdbcs_batch_device_verdicts work
+ *     as after fdbcs_batch_add_packed (the report flags count only on a batch created with
+ *     report_keys), and fdbcs_batch_upload is a no-op.  fdbcs_batch_routed_info,
+ *     fdbcs_batch_set_report_output and fdbcs_batch_set_iops_sample stay with routed batches:
+ *     FDBCS_E_STATE.  Host-mapped pinned input pointers are not supported.
+ *   fdbcs_batch_device_add_info: blocks until the add kernels have run; their error, or the batch's
+ *     sizes and the bytes its key tails take (each padded to 8).  Outputs may be NULL.
+ *     FDBCS_E_STATE on a batch that is not device-added.
+ *   fdbcs_batch_device_add_timing: device time of the add kernels and host time inside the add call
+ *     (ms), valid once fdbcs_batch_device_add_info or detect returned FDBCS_OK. */
+int fdbcs_batch_add_packed_device(fdbcs_batch* b, const fdbcs_packed_batch_dev* pb, const uint32_t* ready_flag,
+                                  uint32_t ready_value);
+int fdbcs_batch_device_add_info(fdbcs_batch* b, int32_t* n_txn, int32_t* n_reads, int32_t* n_writes,
+                                int64_t* tail_bytes);
+int fdbcs_batch_device_add_timing(fdbcs_batch* b, double* ms_kernels, double* ms_host);
 
 /* Diagnostics (tuning, not part of the ConflictSet contract): average device time of one launch
  * of a pipeline kernel over `reps` back-to-back launches on the uploaded batch `b` against the
