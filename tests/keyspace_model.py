@@ -20,7 +20,10 @@ bytes); everything below works on universe indices and packs keys through pack_k
 The batch-order half (TxnBatch, resolve, batch_facts, below): multi-range transactions walked in
 batch order over a bool array `dirty[U]` marked by the writes of the transactions that committed
 earlier in the batch, and the facts about the batch's candidate edges that key geometry alone gives.
+resolve_moved re-resolves a batch with one endpoint index moved by one: what an endpoint sorted one
+place off comes to (tests/sort_plan.py proves with it that a wrong endpoint order cannot pass).
 """
+import copy
 from types import SimpleNamespace
 
 import numpy as np
@@ -605,3 +608,34 @@ def resolve(model, tb, now, oldest, facts=True):
     adm = admitted_arrays(A, too_old)
     return SimpleNamespace(verdicts=verdicts, reports=reports, arrays=A, admitted=adm, first_intra=first_intra,
                            facts=batch_facts(adm, verdicts, dead) if facts else None)
+
+
+ENDS = ("ra", "re", "wa", "we")
+
+
+def outcome(model, res):
+    """What a batch leaves for anyone to see: verdicts, reports and the model's versions (their
+    run-length encoding is the stored state), in a form that compares with ==."""
+    return res.verdicts.tobytes(), tuple(sorted((t, tuple(x)) for t, x in res.reports.items())), model.ver.tobytes()
+
+
+def resolve_moved(model, tb, now, oldest, which, r, d):
+    """resolve() of the batch with one endpoint index moved by d = +-1: `which` of ENDS, range r of
+    that kind.  In index space this is the endpoint sorted one distinct key too late or too early,
+    and, between endpoints at one key, what a class-order error does (the class order ReadEnd <
+    WriteEnd < WriteBegin < ReadBegin makes a range that ends at a key lie wholly before one that
+    begins there).  A range that becomes inverted counts as empty.  The model is a copy: the caller's
+    stays as it is.  Returns (the copy, its resolve()), or None when the index would leave the universe."""
+    A = tb.arrays() if isinstance(tb, TxnBatch) else tb
+    x = getattr(A, which).copy()
+    x[r] += d
+    if x[r] < 0 or x[r] >= model.U:
+        return None
+    other = getattr(A, {"ra": "re", "re": "ra", "wa": "we", "we": "wa"}[which])
+    if (which[1] == "a" and x[r] > other[r]) or (which[1] == "e" and x[r] < other[r]):
+        x[r] = other[r]
+    B = SimpleNamespace(**vars(A))
+    setattr(B, which, x)
+    m = copy.copy(model)
+    m.ver, m._tab = model.ver.copy(), None
+    return m, resolve(m, B, now, oldest, facts=False)

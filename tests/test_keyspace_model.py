@@ -328,3 +328,118 @@ def test_search_universe_is_sorted_in_the_reference_order(oracle_built, search_p
     assert u[0] == b"" and len(set(u)) == len(u)
     for a, b in zip(u, u[1:]):
         assert oracle_built.point_compare(a, True, False, b, True, False) < 0, (a, b)
+
+
+# ---- the batch sort's plan (tests/sort_plan.py)
+
+SORT_KINDS = ["single-long", "single-short", "cold-64", "cold-8", "warm"] + [f"halves-{t}" for t in (1, 100, 200, 400, 800, 1600)]
+
+
+@pytest.fixture(scope="module")
+def sort_plans():
+    """Every plan of tests/sort_plan.py, built once (building asserts the coverage of each: positions
+    reached, run lengths, c values, bucket sizes)."""
+    from tests import sort_plan as SP
+
+    return {kind: SP.build(kind) for kind in SORT_KINDS}
+
+
+def test_resolve_moved_moves_one_endpoint():
+    """K.resolve_moved: one endpoint index of one range moves by one, an inverted range counts as empty,
+    a move out of the universe is None, and the caller's model stays as it was."""
+    model = K.KeyspaceModel(K.var_universe([b"a", b"b", b"c", b"d"]), 5)
+    tb = K.TxnBatch()
+    tb.add(writes=[(1, 2)], snap=9)
+    tb.add(reads=[(0, 1)], snap=9, report=True)
+    base = K.resolve(model, tb, 10, 1, facts=False)
+    assert base.verdicts.tolist() == [K.COMMITTED, K.COMMITTED] and model.ver.tolist() == [5, 10, 5, 5]
+    fresh = K.KeyspaceModel(K.var_universe([b"a", b"b", b"c", b"d"]), 5)
+    m, res = K.resolve_moved(fresh, tb, 10, 1, "re", 0, 1)  # the read now holds the written key
+    assert res.verdicts.tolist() == [K.COMMITTED, K.CONFLICT] and res.reports == {1: [0]}
+    m, res = K.resolve_moved(fresh, tb, 10, 1, "wa", 0, -1)  # the write begins one key earlier
+    assert res.verdicts.tolist() == [K.COMMITTED, K.CONFLICT] and m.ver.tolist() == [10, 10, 5, 5]
+    m, res = K.resolve_moved(fresh, tb, 10, 1, "wa", 0, 1)  # the write becomes empty
+    assert m.ver.tolist() == [5, 5, 5, 5] and K.outcome(m, res) != K.outcome(model, base)
+    m, res = K.resolve_moved(fresh, tb, 10, 1, "we", 0, -1)
+    assert m.ver.tolist() == [5, 5, 5, 5]
+    assert K.resolve_moved(fresh, tb, 10, 1, "ra", 0, -1) is None and fresh.ver.tolist() == [5, 5, 5, 5]
+
+
+def test_sort_plan_wrong_order_cannot_pass(sort_plans):
+    """Every step of every plan re-resolved with one endpoint index moved by one (what an endpoint
+    sorted one key off, or a class-order error at an equal key, comes to): each of the two moves of
+    every endpoint at a directed key changes a verdict, a report or the state in at least one parity.
+    The exempt moves are counted by reason: the extras, empty ranges, the pair families' outward moves
+    and the endpoints whose neighbour in the direction of the move is no chain key."""
+    proved = {}
+    for kind, p in sort_plans.items():
+        p.prove()
+        proved[kind] = sum(p.proved.values())
+        for name, ex in p.exempt.items():
+            # nothing but the ends of the chain (of the pair families) is exempt for its place in the universe
+            assert ex["edge"] <= 7, (kind, name, ex)
+            assert ex["outward"] == 0 and ex["empty"] == 0 or name == "pairs", (kind, name, ex)
+    assert proved["single-long"] >= 2000 and proved["cold-64"] >= 2000 and proved["cold-8"] >= 4000, proved
+    assert min(proved.values()) >= 4, proved
+    assert sort_plans["single-long"].proved["pairs"] == 8  # begin + 1 and end - 1 of the two pairs and the two triples
+
+
+def test_sort_plan_conditions(sort_plans):
+    """The plans' own conditions, from the model alone: conflicts and commits are each at least 0.3 of
+    every step; the one-bucket plans reach every batch size, register width, tile count, run length and
+    placement; the cold plans every c, the clamp under each, len - c = 18 | 19 | 20 and one bucket past
+    256 from keys tied on the whole window; the two-bucket plans every odd size; the warm plan its
+    table hand-overs.  (Each builder asserts the details; here what the GPU test relies on.)"""
+    from tests import sort_plan as SP
+
+    for kind, p in sort_plans.items():
+        assert all(min(s.shares) >= 0.3 for s in p.steps), kind
+        assert all(b.T == b.pb.n_txn == len(b.want) <= 8192 for b in p.batches), kind
+        assert max(b.facts.nb for b in p.batches) <= 257 and max(b.facts.E for b in p.batches) <= 4 * 8192
+    t = sort_plans["single-long"].tokens
+    assert {("E", n) for n in SP.SIZES} <= t and SP.PLACEMENTS <= t
+    assert {("run-keys", d) for d in SP.RUN_KEYS} <= t and {("run-endpoints", n) for n in SP.RUN_ENDPOINTS} <= t
+    assert {("path", x) for x in ("pair", "simple", "pfall", "slow", "mlong")} <= t
+    assert not any(x[0] == "path" for x in sort_plans["single-short"].tokens)
+    for kind in ("cold-64", "cold-8"):
+        t = sort_plans[kind].tokens
+        assert {("c", c) for c in SP.COLD_C + (64,)} <= t and {("clamp", c) for c in SP.COLD_C} <= t
+        assert {("len-c", n) for n in (0, 18, 19, 20)} <= t
+        assert sum(b.big for b in sort_plans[kind].batches) == 2
+    sizes = set().union(*(sort_plans[f"halves-{x}"].tokens for x in SP.HALVES))
+    assert {("bucket", n) for n in SP.HALF_SIZES + (1025,)} <= sizes
+    assert [b.big for b in sort_plans["warm"].batches] == [0, 0, 0, 0, 1, 0, 1, 1, 1, 1, 1, 0, 1, 0]
+
+
+@pytest.mark.parametrize("kind", SORT_KINDS)
+def test_sort_plan_matches_semantic_oracle(oracle_built, sort_plans, kind):
+    """Every batch of the sort's plans against the semantic oracle: verdicts, reports and the state."""
+    from tests import sort_plan as SP
+
+    p = sort_plans[kind]
+    o = oracle_built.OracleConflictSet()
+    o.load_history(*p.loaded)
+    o.set_oldest_version(SP.OLDEST)
+    for b in p.batches:
+        got, conf = o.detect(b.pb, b.now, SP.OLDEST)
+        assert (got == b.want).all(), (b.name, np.flatnonzero(got != b.want)[:10])
+        assert {t: sorted(x) for t, x in conf.items()} == b.reports, b.name
+        keys, vers = o.dump_history()
+        assert _rle_lists(b.state, None) == canon(keys, vers, SP.HEADER, NO_FLOOR), b.name
+
+
+def test_sort_plan_orders_like_the_reference(oracle_built, sort_plans):
+    """The plan's total order (key, class, endpoint id, Python's order of bytes) through the oracle's
+    point comparison, on the batches with the longest tie runs: neighbours in the order never compare
+    the other way round."""
+    from tests import sort_plan as SP
+
+    cls_flags = {SP.RB: (True, False), SP.RE: (False, False), SP.WB: (True, True), SP.WE: (False, True)}
+    p = sort_plans["single-long"]
+    for b in p.batches:
+        if b.step not in ("tails", "ladder", "long", "pairs", "cap19"):
+            continue
+        tb_keys, cls = SP.endpoint_table(b.arrays, p.ukeys)
+        order = SP.total_order(tb_keys, cls)
+        for x, y in zip(order, order[1:]):
+            assert oracle_built.point_compare(tb_keys[x], *cls_flags[cls[x]], tb_keys[y], *cls_flags[cls[y]]) <= 0, (b.name, x, y)
