@@ -188,6 +188,13 @@ SIGNATURES = {
                                                    ctypes.POINTER(_I64)]),
     "fdbcs_batch_device_add_timing": (ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_double),
                                                      ctypes.POINTER(ctypes.c_double)]),
+    "fdbcs_share_bytes_bound": (ctypes.c_int, [_I32, _I32, _I32, _I64, ctypes.POINTER(_I64)]),
+    "fdbcs_batch_share_pack_device": (ctypes.c_int, [_VP, ctypes.POINTER(_CPackedBatchDev), _VP, _I64, _VP,
+                                                     ctypes.c_uint32]),
+    "fdbcs_batch_share_pack_info": (ctypes.c_int, [_VP, ctypes.POINTER(_I64), ctypes.POINTER(_I32), ctypes.POINTER(_I32),
+                                                   ctypes.POINTER(_I32), ctypes.POINTER(_I64)]),
+    "fdbcs_batch_share_pack_timing": (ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_double),
+                                                     ctypes.POINTER(ctypes.c_double)]),
     "fdbcs_debug_kernel_time": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
     "fdbcs_kernel_profile": (ctypes.c_int, [_VP, _I32, ctypes.c_char_p, _I32, ctypes.POINTER(_I64),
                                             ctypes.POINTER(ctypes.c_double)]),
@@ -229,6 +236,18 @@ def share_pack(pb: PackedBatch, out: Optional[np.ndarray] = None) -> np.ndarray:
     used = _I64()
     _check(L.fdbcs_share_pack(ctypes.byref(cs), _VP(out.ctypes.data), out.nbytes, ctypes.byref(used)), "sharePack")
     return out[: used.value]
+
+
+def share_bytes_bound(n_txn: int, n_reads: int, n_writes: int, key_bytes_len: int) -> int:
+    """fdbcs_share_bytes_bound: the wire layout's size for these sizes with every key byte a tail
+    byte; at least the exact size of any valid batch of those sizes (the all-gather stride of a
+    caller that holds only device arrays)."""
+    n = _I64()
+    rc = load_library().fdbcs_share_bytes_bound(int(n_txn), int(n_reads), int(n_writes), int(key_bytes_len),
+                                                ctypes.byref(n))
+    if rc != FDBCS_OK:
+        raise FdbcsError(rc, "shareBytesBound")
+    return n.value
 
 
 def _key_resolvers_struct(kr):
@@ -617,6 +636,41 @@ class ConflictBatch:
         rc = load_library().fdbcs_batch_device_add_timing(self._h, ctypes.byref(a), ctypes.byref(b))
         if rc != FDBCS_OK:
             raise FdbcsError(rc, "deviceAddTiming")
+        return a.value, b.value
+
+    def share_pack_device(self, dpb: DevicePackedBatch, out_ptr: int, cap: int, ready_ptr: int = 0,
+                          ready_value: int = 0) -> None:
+        """fdbcs_batch_share_pack_device: the proxy share of a packed batch whose arrays are in
+        device memory, written by kernels into the `cap` bytes of device memory at `out_ptr`
+        (64-byte aligned; e.g. this rank's slot of the all-gather buffer), byte for byte what
+        share_pack() gives.  On a new, empty batch, which stays empty: afterwards it takes
+        share_pack_info() / share_pack_timing(), add_routed() / add_routed_map(), a further pack and
+        close().  The kernels run once the uint32 at `ready_ptr` equals `ready_value` (0: the arrays
+        are complete).  A violation the kernels find comes from share_pack_info() or the routed add
+        and leaves the empty share at `out_ptr`."""
+        c = dpb.c_struct()
+        rc = load_library().fdbcs_batch_share_pack_device(self._h, ctypes.byref(c), _VP(out_ptr or None), int(cap),
+                                                          _VP(ready_ptr or None), int(ready_value) & 0xFFFFFFFF)
+        if rc != FDBCS_OK:
+            raise FdbcsError(rc, "sharePackDevice")
+
+    def share_pack_info(self) -> Tuple[int, int, int, int, int]:
+        """fdbcs_batch_share_pack_info: blocks until the pack kernels have run; (bytes, transactions,
+        reads, writes, tail bytes) of the share's header, or the pack's error (FdbcsError)."""
+        n, T, R, W, tb = _I64(), _I32(), _I32(), _I32(), _I64()
+        rc = load_library().fdbcs_batch_share_pack_info(self._h, ctypes.byref(n), ctypes.byref(T), ctypes.byref(R),
+                                                        ctypes.byref(W), ctypes.byref(tb))
+        if rc != FDBCS_OK:
+            raise FdbcsError(rc, "sharePackInfo")
+        return n.value, T.value, R.value, W.value, tb.value
+
+    def share_pack_timing(self) -> Tuple[float, float]:
+        """Milliseconds of the pack kernels (device) and inside the pack call (host), once the pack
+        has been waited for (share_pack_info() or a routed add)."""
+        a, b = ctypes.c_double(), ctypes.c_double()
+        rc = load_library().fdbcs_batch_share_pack_timing(self._h, ctypes.byref(a), ctypes.byref(b))
+        if rc != FDBCS_OK:
+            raise FdbcsError(rc, "sharePackTiming")
         return a.value, b.value
 
     def upload(self) -> None:

@@ -488,6 +488,7 @@ void release_slot(BatchSlot* sl) {
     if (sl->ev_da0) (void)hipEventDestroy(sl->ev_da0);
     if (sl->ev_da1) (void)hipEventDestroy(sl->ev_da1);
     sl->da_scan.release();
+    sl->sp_toff.release();
     sl->da_dres.release();
     sl->da_res.release();
     sl->is_state.release();
@@ -1209,6 +1210,10 @@ void fdbcs_batch_destroy(fdbcs_batch* b) {
         (void)hipStreamSynchronize(b->cs->ustream);
         (void)hipStreamSynchronize(b->cs->astream);
     }
+    if (b->sp_pending) {  // a share pack nobody waited for: it uses the slot's scan state
+        (void)hipSetDevice(b->cs->device);
+        (void)finish_share_pack(b);
+    }
     // a sample runs behind the routing, off the detect pipeline: the slot's device copy and the
     // sample's own buffers are the next batch's only once it is over
     if (b->slot && b->slot->is_inflight) {
@@ -1233,7 +1238,7 @@ int fdbcs_batch_add_transaction(fdbcs_batch* b, int64_t read_snapshot, int repor
                                 const uint8_t* const* write_begin, const int32_t* write_begin_len,
                                 const uint8_t* const* write_end, const int32_t* write_end_len) {
     if (!b || n_reads < 0 || n_writes < 0) return FDBCS_E_INVALID;
-    if (b->state != 0 || !b->cs) return FDBCS_E_STATE;
+    if (b->state != 0 || !b->cs || b->share_packed) return FDBCS_E_STATE;  // (a batch that packed a share takes routed adds only)
     if ((n_reads && (!read_begin || !read_end || !read_begin_len || !read_end_len)) ||
         (n_writes && (!write_begin || !write_end || !write_begin_len || !write_end_len)))
         return FDBCS_E_INVALID;
@@ -1493,7 +1498,7 @@ int fdbcs_batch_add_packed(fdbcs_batch* b, const fdbcs_packed_batch* pb) {
 
 static int add_packed_impl(fdbcs_batch* b, const fdbcs_packed_batch* pb) {
     if (!b || !pb || pb->n_txn < 0) return FDBCS_E_INVALID;
-    if (b->state != 0 || !b->cs) return FDBCS_E_STATE;
+    if (b->state != 0 || !b->cs || b->share_packed) return FDBCS_E_STATE;  // (a batch that packed a share takes routed adds only)
     const int32_t T = pb->n_txn;
     if (T == 0) return FDBCS_OK;
     if (!pb->read_snapshot || !pb->read_offsets || !pb->write_offsets || !pb->key_offsets) return FDBCS_E_INVALID;
@@ -1555,7 +1560,9 @@ static int add_packed_impl(fdbcs_batch* b, const fdbcs_packed_batch* pb) {
 
 // ---- multi-resolver routing: proxy shares (engine.h ShareHeader) and the device split
 
-static size_t share_layout(int32_t T, int64_t R, int64_t W, int64_t tail, ShareHeader* h) {
+// (C++ linkage inside the C-ABI block, as finish_route below: ingest.cpp's share pack calls it,
+// declared in engine_impl.h)
+extern "C++" size_t fdbcs::impl::share_layout(int32_t T, int64_t R, int64_t W, int64_t tail, ShareHeader* h) {
     size_t off = sizeof(ShareHeader);
     h->T = T;
     h->R = (int32_t)R;
@@ -1758,6 +1765,11 @@ static int add_routed_impl(fdbcs_batch* b, const void* shares, int64_t stride, i
         return FDBCS_E_INVALID;
     if (!b->cs || b->state != 0 || b->T() != 0 || b->direct) return FDBCS_E_STATE;
     if ((int64_t)cap_txns > kMaxTxnLds) return FDBCS_E_INVALID;
+    // the batch's own share may still be packing (fdbcs_batch_share_pack_device): its error comes first
+    if (b->sp_pending) {
+        HIPOK(hipSetDevice(b->cs->device));
+        if (int rc = finish_share_pack(b)) return rc;
+    }
     if (lo_len >= 0 && hi_len >= 0 && cmp_bytes(lo_key, lo_len, hi_key, hi_len) >= 0) return FDBCS_E_INVALID;
     fdbcs_conflict_set* cs = b->cs;
     HIPOK(hipSetDevice(cs->device));

@@ -458,6 +458,9 @@ struct BatchSlot {
     DBuf da_scan, da_dres;
     HBuf da_res;
     hipEvent_t ev_da0 = nullptr, ev_da1 = nullptr;
+    // fdbcs_batch_share_pack_device shares them (a batch does one or the other) and adds each key's
+    // place in the share's tail region, the scan's store
+    DBuf sp_toff;
     // per-kernel events of the batch (timing level 3, or the timed kernel at level 1)
     std::vector<hipEvent_t> prof_pool;
     size_t prof_next = 0;
@@ -531,6 +534,14 @@ struct fdbcs_batch {
     bool dev_added = false;
     double da_ms_host = 0, da_ms_kernels = 0;  // of its add call / add kernels (fdbcs_batch_device_add_timing)
 
+    // fdbcs_batch_share_pack_device: the batch packed a share (it stays empty, and takes no add but a
+    // routed one from then on); the pack's kernels are not waited for yet; its outcome and times
+    bool share_packed = false, sp_pending = false;
+    int sp_rc = 0;
+    int32_t sp_T = 0, sp_R = 0, sp_W = 0;
+    int64_t sp_bytes = 0, sp_tail = 0;
+    double sp_ms_host = 0, sp_ms_kernels = 0;
+
     int32_t T() const { return routed ? rT : (int32_t)snap.size(); }
     int32_t R() const { return routed ? rR : roff.back(); }
     int32_t W() const { return routed ? rW : woff.back(); }
@@ -555,6 +566,11 @@ int finish_route(fdbcs_batch* b);  // wait for a routed batch's routing and take
 // Its sibling for a device-added batch (ingest.cpp; finish_route hands such a batch over): wait for
 // the add kernels and take the totals; on an error the batch is empty again.
 int finish_device_add(fdbcs_batch* b);
+// And for a batch that packed a share (ingest.cpp): wait for the pack kernels and take their outcome;
+// the pack's status, which fdbcs_batch_share_pack_info repeats.
+int finish_share_pack(fdbcs_batch* b);
+// The wire layout of a share (engine.h ShareHeader) into *h; its size.
+size_t share_layout(int32_t T, int64_t R, int64_t W, int64_t tail, ShareHeader* h);
 // Layout of a batch in pin_in / dev: [keys | rowner | wowner | snap | roff | woff | flags | tail].
 struct UploadLayout {
     size_t keys, rown, wown, snap, roff, woff, flags, tail, total;

@@ -3,7 +3,9 @@
 // of it.  The call sizes the batch's slot from the sizes it is given, enqueues the kernels of
 // ingest.hip on the stream the routing kernels use (off the detect pipeline's chains) and returns;
 // the batch then is what a routed batch is to the detect steps (engine.cpp), told apart by
-// fdbcs_batch::dev_added.
+// fdbcs_batch::dev_added.  fdbcs_batch_share_pack_device takes the same arrays through the same
+// checks and writes them as the proxy share fdbcs_share_pack would (engine.h ShareHeader) into the
+// caller's device buffer; the batch stays empty.
 #include "engine_impl.h"
 #include "ingest.h"
 
@@ -42,14 +44,150 @@ int fdbcs::impl::finish_device_add(fdbcs_batch* b) {
     return FDBCS_OK;
 }
 
+// Wait for the pack kernels and take their outcome.  The batch was empty and stays so; on an error
+// the kernels left the empty share in the caller's buffer.
+int fdbcs::impl::finish_share_pack(fdbcs_batch* b) {
+    if (!b->sp_pending) return b->sp_rc;
+    BatchSlot* sl = b->slot;
+    b->sp_pending = false;
+    b->sp_rc = FDBCS_E_DEVICE;
+    HIPOK(hipEventSynchronize(sl->ev_da1));
+    std::atomic_thread_fence(std::memory_order_acquire);
+    ShareResult r;
+    memcpy(&r, (const void*)sl->da_res.p, sizeof(r));
+    b->sp_ms_kernels = ev_ms(sl->ev_da0, sl->ev_da1);
+    b->sp_bytes = r.bytes;
+    b->sp_tail = r.tail_bytes;
+    if (r.error != 0) {
+        // 1: the arrays break the layout or hold an inverted range; 2: the ready flag was never set;
+        // 3: the share with its tails passes cap; 4 (or a block never written): the scan gave up
+        if (r.error == 2) fprintf(stderr, "fdbcs: share pack: the arrays' ready flag was never set\n");
+        b->sp_T = b->sp_R = b->sp_W = 0;
+        b->sp_rc = r.error == 1 ? FDBCS_E_INVALID : r.error == 2 ? FDBCS_E_TIMEOUT : r.error == 3 ? FDBCS_E_NOMEM : FDBCS_E_DEVICE;
+        return b->sp_rc;
+    }
+    b->sp_rc = FDBCS_OK;
+    return FDBCS_OK;
+}
+
 extern "C" {
+
+int fdbcs_share_bytes_bound(int32_t n_txn, int32_t n_reads, int32_t n_writes, int64_t key_bytes_len, int64_t* bytes) {
+    if (!bytes || n_txn < 0 || n_reads < 0 || n_writes < 0 || key_bytes_len < 0) return FDBCS_E_INVALID;
+    ShareHeader h{};
+    *bytes = (int64_t)share_layout(n_txn, n_reads, n_writes, key_bytes_len, &h);
+    return FDBCS_OK;
+}
+
+int fdbcs_batch_share_pack_device(fdbcs_batch* b, const fdbcs_packed_batch_dev* pb, void* out_dev, int64_t cap,
+                                  const uint32_t* ready_flag, uint32_t ready_value) {
+    const auto t_host = std::chrono::steady_clock::now();
+    if (!b || !pb || pb->n_txn < 0 || pb->n_reads < 0 || pb->n_writes < 0 || pb->key_bytes_len < 0 || cap < 0)
+        return FDBCS_E_INVALID;
+    if (!b->cs || b->state != 0 || b->T() != 0 || b->direct || b->routed || b->sp_pending) return FDBCS_E_STATE;
+    // the empty share reads no array: its sizes are all zero
+    const int32_t T = pb->n_txn, R = T ? pb->n_reads : 0, W = T ? pb->n_writes : 0;
+    const int64_t nbytes = T ? pb->key_bytes_len : 0;
+    const int64_t nk = 2 * ((int64_t)R + W);
+    if (T && (!pb->read_snapshot || !pb->read_offsets || !pb->write_offsets || (nk && !pb->key_offsets) ||
+              (nk && nbytes && !pb->key_bytes)))
+        return FDBCS_E_INVALID;
+    if ((int64_t)T > kMaxTxnLds) return FDBCS_E_INVALID;
+    if (!out_dev || ((uintptr_t)out_dev & 63)) return FDBCS_E_INVALID;
+    // tail offsets and the scan's sums are 32-bit; a range id takes 29 bits of a sort item
+    if (nbytes >= ((int64_t)1 << 32) || (int64_t)R + W >= ((int64_t)1 << 28)) return FDBCS_E_NOMEM;
+    ShareHeader hdr{}, empty{};
+    // every region but the tail's end is placed by T, R and W alone
+    if (cap < (int64_t)share_layout(T, R, W, 0, &hdr)) return FDBCS_E_NOMEM;
+    // the empty share's header, for an error (its 320 bytes, kShareEmptyBytes, are a constant of the
+    // layout that tests/test_share_pack_device_abi.py pins)
+    share_layout(0, 0, 0, 0, &empty);
+    fdbcs_conflict_set* cs = b->cs;
+    HIPOK(hipSetDevice(cs->device));
+    BatchSlot* sl = b->slot;
+    int rc;
+    const int64_t n_elems = ingest_elems(T, nk);
+    const size_t scan_bytes = align_up(8 * (size_t)share_scan_words(n_elems), 16);
+    if ((rc = sl->da_scan.ensure(scan_bytes))) return rc;
+    if ((rc = sl->da_dres.ensure(sizeof(ShareResult)))) return rc;
+    if ((rc = sl->da_res.ensure(sizeof(ShareResult), true))) return rc;
+    if ((rc = sl->sp_toff.ensure(4 * (size_t)std::max<int64_t>(nk, 1)))) return rc;
+    if (!sl->ev_da0) HIPOK(hipEventCreate(&sl->ev_da0));
+    if (!sl->ev_da1) HIPOK(hipEventCreate(&sl->ev_da1));
+    ShareArgs a{};
+    a.in.T = T;
+    a.in.R = R;
+    a.in.W = W;
+    a.in.nk = nk;
+    a.in.nbytes = nbytes;
+    a.in.snap = pb->read_snapshot;
+    a.in.report = pb->report_conflicting_keys;
+    a.in.roff = pb->read_offsets;
+    a.in.woff = pb->write_offsets;
+    a.in.kbytes = pb->key_bytes;
+    a.in.koff = pb->key_offsets;
+    a.in.ready = ready_flag;
+    a.in.ready_value = ready_value;
+    a.in.wait_ticks = (uint64_t)cs->route_timeout_ms * 100000ull;  // 100 MHz wall clock
+    uint64_t* sw = (uint64_t*)sl->da_scan.p;
+    a.in.wait_err = (uint32_t*)(sw + 2);
+    a.out = (uint8_t*)out_dev;
+    a.cap = cap;
+    static_assert(sizeof(a.hdr) == sizeof(ShareHeader) && sizeof(a.empty) == sizeof(ShareHeader), "header words");
+    memcpy(a.hdr, &hdr, sizeof(hdr));
+    memcpy(a.empty, &empty, sizeof(empty));
+    a.toff = (uint32_t*)sl->sp_toff.p;
+    a.res = (ShareResult*)sl->da_res.dp;
+    a.dres = (ShareResult*)sl->da_dres.p;
+    ((ShareResult*)sl->da_res.p)->error = -1;  // not written yet
+    // the stream of the routing kernels: a routed add of the same handle runs behind the pack
+    hipStream_t us = cs->ustream;
+    HIPOK(hipMemsetAsync(sl->da_scan.p, 0, scan_bytes, us));
+    ScanState st{sw + 8, (int*)sw, (int*)(sw + 1)};
+    t_record = nullptr;
+    HIPOK(hipEventRecord(sl->ev_da0, us));
+    launch_share_pack(us, a, st);
+    HIPOK(take_launch_error());
+    HIPOK(hipEventRecord(sl->ev_da1, us));
+    b->share_packed = b->sp_pending = true;
+    b->sp_rc = FDBCS_OK;
+    b->sp_T = T;
+    b->sp_R = R;
+    b->sp_W = W;
+    b->sp_bytes = b->sp_tail = 0;
+    b->sp_ms_kernels = 0;
+    b->sp_ms_host = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host).count();
+    return FDBCS_OK;
+}
+
+int fdbcs_batch_share_pack_info(fdbcs_batch* b, int64_t* bytes, int32_t* n_txn, int32_t* n_reads, int32_t* n_writes,
+                                int64_t* tail_bytes) {
+    if (!b) return FDBCS_E_INVALID;
+    if (!b->cs || !b->share_packed) return FDBCS_E_STATE;
+    HIPOK(hipSetDevice(b->cs->device));
+    if (int rc = finish_share_pack(b)) return rc;
+    if (bytes) *bytes = b->sp_bytes;
+    if (n_txn) *n_txn = b->sp_T;
+    if (n_reads) *n_reads = b->sp_R;
+    if (n_writes) *n_writes = b->sp_W;
+    if (tail_bytes) *tail_bytes = b->sp_tail;
+    return FDBCS_OK;
+}
+
+int fdbcs_batch_share_pack_timing(fdbcs_batch* b, double* ms_kernels, double* ms_host) {
+    if (!b || !ms_kernels || !ms_host) return FDBCS_E_INVALID;
+    if (!b->share_packed || b->sp_pending) return FDBCS_E_STATE;
+    *ms_kernels = b->sp_ms_kernels;
+    *ms_host = b->sp_ms_host;
+    return FDBCS_OK;
+}
 
 int fdbcs_batch_add_packed_device(fdbcs_batch* b, const fdbcs_packed_batch_dev* pb, const uint32_t* ready_flag,
                                   uint32_t ready_value) {
     const auto t_host = std::chrono::steady_clock::now();
     if (!b || !pb || pb->n_txn < 0 || pb->n_reads < 0 || pb->n_writes < 0 || pb->key_bytes_len < 0)
         return FDBCS_E_INVALID;
-    if (!b->cs || b->state != 0 || b->T() != 0 || b->direct || b->routed) return FDBCS_E_STATE;
+    if (!b->cs || b->state != 0 || b->T() != 0 || b->direct || b->routed || b->share_packed) return FDBCS_E_STATE;
     const int32_t T = pb->n_txn, R = pb->n_reads, W = pb->n_writes;
     if (T == 0) return FDBCS_OK;
     const int64_t nk = 2 * ((int64_t)R + W);

@@ -531,6 +531,66 @@ int fdbcs_batch_device_add_info(fdbcs_batch* b, int32_t* n_txn, int32_t* n_reads
                                 int64_t* tail_bytes);
 int fdbcs_batch_device_add_timing(fdbcs_batch* b, double* ms_kernels, double* ms_host);
 
+/* A proxy's share packed on the GPU from device-resident arrays: fdbcs_share_pack's output, byte
+ * for byte, written by kernels straight into the caller's gather buffer, so a rank whose batch
+ * arrived in device memory (fdbcs_packed_batch_dev) routes it without the host reading a key.
+ *   fdbcs_share_bytes_bound: host only (no device needed, like fdbcs_share_bytes).  The size of the
+ *     wire layout of a share of T transactions, R reads and W writes whose key tails take
+ *     key_bytes_len bytes: at least fdbcs_share_bytes of every valid batch of those sizes (a key's
+ *     tail is shorter than the key), and what a caller that holds only device arrays sizes its
+ *     all-gather stride with (the exact size needs key_offsets).  (0, 0, 0, 0) gives the empty
+ *     share's 320 bytes.  FDBCS_E_INVALID for a negative size or a NULL `bytes`.
+ *   fdbcs_batch_share_pack_device: on a new, empty batch of the set whose GPU holds the arrays and
+ *     out_dev.  FDBCS_E_STATE on a batch that holds anything, is routed, device-added or detected, or
+ *     whose previous pack has not been waited for.  The host reads none of the arrays and does no
+ *     work per transaction, range or key: it enqueues the pack kernels on the stream the routing
+ *     kernels use (off the detect pipeline's chains) and returns.  They run once the device word
+ *     *ready_flag equals ready_value (NULL: the arrays are complete), the wait bounded by
+ *     FDBCS_ROUTE_TIMEOUT_MS, exactly as for fdbcs_batch_add_packed_device.  out_dev: device memory
+ *     of the set's GPU (any allocator), 64-byte aligned, cap bytes.  The batch stays empty and the
+ *     set is never touched.  The only calls accepted on the batch afterwards are
+ *     fdbcs_batch_share_pack_info / _timing, fdbcs_batch_add_routed / _add_routed_map (they first
+ *     block for a pending pack and return its error if it had one, routing nothing; an error that
+ *     fdbcs_batch_share_pack_info has already returned is not returned again by them: the buffer
+ *     then holds the empty share, and they route what the gather buffer holds.  The typical use
+ *     packs the rank's share into its slot of the gather buffer, all-gathers after _info and
+ *     routes with the same handle), a further pack once _info has returned, and destroy; every other add is
+ *     FDBCS_E_STATE.
+ *     Refused by the host before anything is enqueued or written: FDBCS_E_INVALID for the NULL and
+ *     negative-size cases of the device add, n_txn over the batch limit (49152), out_dev NULL or
+ *     not 64-byte aligned; FDBCS_E_NOMEM for key_bytes_len >= 2^32, R + W >= 2^28, or cap below the
+ *     layout of (T, R, W) without tails (fdbcs_share_bytes_bound(T, R, W, 0); never below the empty
+ *     share's 320 bytes).  n_txn == 0 is FDBCS_OK and packs the empty share (no array is read).
+ *     Validated on the device, as by the device add: read_offsets[0] == write_offsets[0] == 0, both
+ *     non-decreasing, read_offsets[T] == n_reads, write_offsets[T] == n_writes, key_offsets
+ *     non-decreasing inside [0, key_bytes_len], no inverted range in the full byte order (tails
+ *     included); no address is formed from a value of the arrays before it is checked.  The exact
+ *     size is checked there too: the layout for the tail total the kernels found must fit cap.
+ *     On success out_dev[0, bytes) equals what fdbcs_share_pack writes into a zeroed buffer for the
+ *     same batch: the header (pads zero), the endpoint records (tail = the byte offset in the
+ *     share's tail region; tails byte-packed in key order, not padded), snapshots, offsets, the
+ *     report flags (zeros for a NULL array; copied whether or not the batch was created with
+ *     report_keys), owners, the tail bytes and 64 zero bytes after them; every alignment gap is
+ *     zero.  [bytes, cap) is unspecified, and nothing outside [out_dev, out_dev + cap) is written.
+ *     On any error found by the kernels nothing but out_dev[0, 320) is written, and it holds the
+ *     empty share (T = R = W = 0, bytes = 320): a gather buffer is always well formed, and a failed
+ *     pack routes as no transactions.
+ *   fdbcs_batch_share_pack_info: blocks until the pack kernels have run.  The header's bytes, T, R,
+ *     W and tail_bytes (outputs may be NULL), or FDBCS_E_INVALID for a violation, FDBCS_E_NOMEM when
+ *     the exact size passes cap, FDBCS_E_TIMEOUT for a ready flag never set; the same status again
+ *     on every later call until the next pack.  The arrays may be reused once it has returned.
+ *     FDBCS_E_STATE on a batch that never packed.
+ *   fdbcs_batch_share_pack_timing: device time of the pack kernels and host time inside the pack
+ *     call (ms), valid once the pack has been waited for.
+ * Not provided: a device-side completion signal for the caller's stream (the handshake is the
+ * blocking _info, as for fdbcs_batch_device_add_info), and host-mapped pinned input pointers. */
+int fdbcs_share_bytes_bound(int32_t n_txn, int32_t n_reads, int32_t n_writes, int64_t key_bytes_len, int64_t* bytes);
+int fdbcs_batch_share_pack_device(fdbcs_batch* b, const fdbcs_packed_batch_dev* pb, void* out_dev, int64_t cap,
+                                  const uint32_t* ready_flag, uint32_t ready_value);
+int fdbcs_batch_share_pack_info(fdbcs_batch* b, int64_t* bytes, int32_t* n_txn, int32_t* n_reads, int32_t* n_writes,
+                                int64_t* tail_bytes);
+int fdbcs_batch_share_pack_timing(fdbcs_batch* b, double* ms_kernels, double* ms_host);
+
 /* Diagnostics (tuning, not part of the ConflictSet contract): average device time of one launch
  * of a pipeline kernel over `reps` back-to-back launches on the uploaded batch `b` against the
  * current history, with no batch in flight.  which: 0 = the read check (D.CheckRead); 1-2 = the
