@@ -16,7 +16,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -106,6 +106,29 @@ class Stats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class _CDigest(ctypes.Structure):
+    """fdbcs_digest."""
+    _fields_ = [
+        ("n", ctypes.c_int64),
+        ("key_bytes", ctypes.c_int64),
+        ("header_version", ctypes.c_int64),
+        ("sum", ctypes.c_uint64 * 2),
+    ]
+
+
+class HistoryDigest(NamedTuple):
+    """fdbcs_digest: the digest of a canonical history (include/fdb_conflict_set.h has the
+    definition).  Two histories are taken as equal iff the tuples are."""
+    n: int
+    key_bytes: int
+    header_version: int
+    sum: Tuple[int, int]
+
+    @classmethod
+    def _of(cls, d: "_CDigest") -> "HistoryDigest":
+        return cls(int(d.n), int(d.key_bytes), int(d.header_version), (int(d.sum[0]), int(d.sum[1])))
+
+
 class _CKeyResolvers(ctypes.Structure):
     """fdbcs_key_resolvers."""
     _fields_ = [
@@ -133,6 +156,10 @@ SIGNATURES = {
                                             ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     "fdbcs_history_export_read": (ctypes.c_int, [_VP, _VP, _I64, _VP, _VP, _I64]),
     "fdbcs_history_export_timing": (ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_double),
+                                                   ctypes.POINTER(ctypes.c_double)]),
+    "fdbcs_history_digest": (ctypes.c_int, [_VP, _VP, _I32, _VP, _I32, _I64, ctypes.POINTER(_CDigest)]),
+    "fdbcs_history_digest_arrays": (ctypes.c_int, [_I64, _VP, _VP, _VP, _I64, ctypes.POINTER(_CDigest)]),
+    "fdbcs_history_digest_timing": (ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_double),
                                                    ctypes.POINTER(ctypes.c_double)]),
     "fdbcs_history_import": (ctypes.c_int, [_VP, _VP, _I32, _VP, _I32, _I64, _VP, _VP, _VP, _I64,
                                             ctypes.POINTER(_I64)]),
@@ -274,6 +301,21 @@ def route_map_pack(kr, resolver: int) -> Tuple[np.ndarray, np.ndarray]:
         raise FdbcsError(rc, "routeMapPack")
     del keep
     return own, until
+
+
+def digest_arrays(key_bytes, key_offsets, versions, header_version: int = 0) -> HistoryDigest:
+    """fdbcs_history_digest_arrays (host only): the digest of arrays in the layout dump_history
+    returns and load_history takes, exactly as given (nothing is canonicalised, key order is not
+    checked).  digest_arrays(*cs.dump_history(lo, hi, floor)) == cs.digest(lo, hi, floor)."""
+    kb = np.ascontiguousarray(key_bytes, np.uint8)
+    ko = np.ascontiguousarray(key_offsets, np.int64)
+    vv = np.ascontiguousarray(versions, np.int64)
+    d = _CDigest()
+    rc = load_library().fdbcs_history_digest_arrays(len(vv), _p(kb), _p(ko), _p(vv), int(header_version),
+                                                    ctypes.byref(d))
+    if rc != FDBCS_OK:
+        raise FdbcsError(rc, "historyDigestArrays")
+    return HistoryDigest._of(d)
 
 
 def strerror(status: int) -> str:
@@ -439,6 +481,26 @@ class ConflictSet:
         n, nb, hdr = self.export_history(lo, hi, floor)
         kb, ko, vv = self.read_export(n, nb)
         return kb, ko, vv, hdr
+
+    def digest(self, lo: Optional[bytes] = None, hi: Optional[bytes] = None,
+               floor: Optional[int] = None) -> HistoryDigest:
+        """fdbcs_history_digest: the digest of the canonical history over [lo, hi), what
+        dump_history(lo, hi, floor) would return, computed on the device without an export (`floor`
+        defaults to the oldest version, as there).  a.digest(lo, hi) == b.digest(lo, hi) checks a
+        hand-over or a restore across GPUs or processes; a pending export stays readable."""
+        if floor is None:
+            floor = self.oldest_version
+        kl, ll, kh, hl = self._bounds(lo, hi)
+        d = _CDigest()
+        _check(load_library().fdbcs_history_digest(self._h, _p(kl), ll, _p(kh), hl, floor, ctypes.byref(d)),
+               "historyDigest")
+        return HistoryDigest._of(d)
+
+    def digest_timing(self) -> Tuple[float, float]:
+        """Milliseconds of the last digest's kernels (device) and of the whole call (host)."""
+        a, b = ctypes.c_double(), ctypes.c_double()
+        _check(load_library().fdbcs_history_digest_timing(self._h, ctypes.byref(a), ctypes.byref(b)), "digestTiming")
+        return a.value, b.value
 
     @staticmethod
     def _bounds(lo: Optional[bytes], hi: Optional[bytes]):

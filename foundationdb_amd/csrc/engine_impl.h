@@ -408,6 +408,11 @@ struct fdbcs_conflict_set {
     hipEvent_t x_ev0 = nullptr, x_ev1 = nullptr;  // around the export's kernels
     double x_ms_kernels = 0, x_ms_d2h = 0;        // of the last export / read (fdbcs_history_export_timing)
     int64_t x_hdr = 0;                            // the pending result's header version
+    // fdbcs_history_digest: its own words and per-tile starts (a pending export's words stay as they
+    // are); x_pos, x_val and x_btail are shared with the export, which keeps no result in them
+    DBuf g_state;
+    hipEvent_t g_ev[2] = {};                      // around the digest's kernels
+    double g_ms_kernels = 0, g_ms_host = 0;       // of the last digest (fdbcs_history_digest_timing)
     // fdbcs_history_import: device copies of the imported arrays (host-array form), the bounds' bytes,
     // the overlay stream (keys, lt, versions, tails), the merged stream (value, key, lt) and the import
     // words; all allocated by the first import and freed with the set.

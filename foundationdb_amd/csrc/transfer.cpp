@@ -21,6 +21,52 @@ static int copy_keyed_result(int64_t n, int64_t nbytes, void* items, const void*
     return FDBCS_OK;
 }
 
+// What the export and the digest of an idle set read alike: the tiers as they stand, the floor and the
+// bounds (lo / hi as RouteArgs::lo / hi: DKey + tail bytes, bt, for a small device buffer).
+static int export_inputs(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key,
+                         int32_t hi_len, int64_t floor_version, ExportArgs& a, Scalars& sc, std::vector<uint8_t>& bt) {
+    HIPOK(hipMemcpy(&sc, cs->scal.p, sizeof(sc), hipMemcpyDeviceToHost));
+    a = ExportArgs{};
+    a.nb = sc.n;
+    a.nd = sc.ndb[cs->dcur];
+    a.base = hist_of(cs, cs->cur);
+    a.delta = delta_of(cs, cs->dcur);
+    a.htail = (const uint8_t*)cs->htail[cs->tcur].p;
+    a.hdr = cs->header_version;
+    a.floor = floor_version;
+    auto norm = [&](const uint8_t* p, int32_t len, DKey& k) {
+        dkey_prefix(p, (uint32_t)len, &k.hi, &k.lo);
+        k.len = (uint32_t)len;
+        k.tail = (uint32_t)bt.size();
+        if (len > 16) bt.insert(bt.end(), p + 16, p + len);
+    };
+    a.has_lo = lo_len >= 0;
+    a.has_hi = hi_len >= 0;
+    if (a.has_lo) norm(lo_key, lo_len, a.lo);
+    if (a.has_hi) norm(hi_key, hi_len, a.hi);
+    return FDBCS_OK;
+}
+
+// Their scratch: the bounds' tails and one position and one value per delta boundary.  Neither keeps
+// anything there past its own call.
+static int export_scratch(fdbcs_conflict_set* cs, ExportArgs& a, const std::vector<uint8_t>& bt) {
+    int rc;
+    if ((rc = cs->x_btail.ensure(bt.size() + kTailSlack))) return rc;
+    if ((rc = cs->x_pos.ensure(8 * (size_t)(a.nd + 1)))) return rc;
+    if ((rc = cs->x_val.ensure(8 * (size_t)(a.nd + 1)))) return rc;
+    a.btail = (const uint8_t*)cs->x_btail.p;
+    a.d_pos = (int64_t*)cs->x_pos.p;
+    a.d_val = (int64_t*)cs->x_val.p;
+    return FDBCS_OK;
+}
+
+// The words and chains of the digest (include/fdb_conflict_set.h), restated for host arrays.
+static inline uint64_t digest_mix(uint64_t z) {
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
 extern "C" {
 
 int fdbcs_history_export(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key,
@@ -33,44 +79,21 @@ int fdbcs_history_export(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t 
     if (int rc = sync_all(cs)) return rc;
     cs->x_valid = false;
     Scalars sc;
-    HIPOK(hipMemcpy(&sc, cs->scal.p, sizeof(sc), hipMemcpyDeviceToHost));
-    ExportArgs a{};
-    a.nb = sc.n;
-    a.nd = sc.ndb[cs->dcur];
+    ExportArgs a;
+    std::vector<uint8_t> bt;
+    int rc;
+    if ((rc = export_inputs(cs, lo_key, lo_len, hi_key, hi_len, floor_version, a, sc, bt))) return rc;
     const int64_t total = a.nb + a.nd;
     // the byte scan's exact range (transfer.hip, history export): refuse rather than wrap
     if (total >= ((int64_t)1 << 29) || 16 * total + sc.tail_used >= ((int64_t)1 << 35)) return FDBCS_E_NOMEM;
-    a.base = hist_of(cs, cs->cur);
-    a.delta = delta_of(cs, cs->dcur);
-    a.htail = (const uint8_t*)cs->htail[cs->tcur].p;
-    a.hdr = cs->header_version;
-    a.floor = floor_version;
-    // lo / hi as RouteArgs::lo / hi: DKey + tail bytes in a small device buffer
-    std::vector<uint8_t> bt;
-    auto norm = [&](const uint8_t* p, int32_t len, DKey& k) {
-        dkey_prefix(p, (uint32_t)len, &k.hi, &k.lo);
-        k.len = (uint32_t)len;
-        k.tail = (uint32_t)bt.size();
-        if (len > 16) bt.insert(bt.end(), p + 16, p + len);
-    };
-    a.has_lo = lo_len >= 0;
-    a.has_hi = hi_len >= 0;
-    if (a.has_lo) norm(lo_key, lo_len, a.lo);
-    if (a.has_hi) norm(hi_key, hi_len, a.hi);
     const int64_t tiles = export_tiles(total);
-    int rc;
-    if ((rc = cs->x_btail.ensure(bt.size() + kTailSlack))) return rc;
-    if ((rc = cs->x_pos.ensure(8 * (size_t)(a.nd + 1)))) return rc;
-    if ((rc = cs->x_val.ensure(8 * (size_t)(a.nd + 1)))) return rc;
+    if ((rc = export_scratch(cs, a, bt))) return rc;
     if ((rc = cs->x_state.ensure(8 * (size_t)(kXwWords + 4 * tiles)))) return rc;
     if ((rc = cs->x_ver.ensure(8 * (size_t)(total + 1)))) return rc;
     if ((rc = cs->x_off.ensure(8 * (size_t)(total + 1)))) return rc;
     if ((rc = cs->x_bytes.ensure((size_t)(16 * total + sc.tail_used + 64)))) return rc;
     if (!cs->x_ev0) HIPOK(hipEventCreate(&cs->x_ev0));
     if (!cs->x_ev1) HIPOK(hipEventCreate(&cs->x_ev1));
-    a.btail = (const uint8_t*)cs->x_btail.p;
-    a.d_pos = (int64_t*)cs->x_pos.p;
-    a.d_val = (int64_t*)cs->x_val.p;
     a.words = (int64_t*)cs->x_state.p;
     a.tile_tb = a.words + kXwWords + 3 * tiles;  // after the scan's granules
     a.versions = (int64_t*)cs->x_ver.p;
@@ -120,6 +143,84 @@ int fdbcs_history_export_timing(fdbcs_conflict_set* cs, double* ms_kernels, doub
     if (!cs || !ms_kernels || !ms_d2h) return FDBCS_E_INVALID;
     *ms_kernels = cs->x_ms_kernels;
     *ms_d2h = cs->x_ms_d2h;
+    return FDBCS_OK;
+}
+
+int fdbcs_history_digest(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key,
+                         int32_t hi_len, int64_t floor_version, fdbcs_digest* out) {
+    if (!cs || !out) return FDBCS_E_INVALID;
+    if (int rc = import_bounds_ok(lo_key, lo_len, hi_key, hi_len)) return rc;
+    if (cs->inflight) return FDBCS_E_STATE;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPOK(hipSetDevice(cs->device));
+    if (int rc = sync_all(cs)) return rc;
+    Scalars sc;
+    ExportArgs a;
+    std::vector<uint8_t> bt;
+    int rc;
+    if ((rc = export_inputs(cs, lo_key, lo_len, hi_key, hi_len, floor_version, a, sc, bt))) return rc;
+    // no result arrays and no scan: words, then one start per tile.  A pending export's words
+    // (x_state) and result arrays are not touched.
+    const int64_t tiles = export_tiles(a.nb + a.nd);
+    if ((rc = export_scratch(cs, a, bt))) return rc;
+    if ((rc = cs->g_state.ensure(8 * (size_t)(kXwWords + tiles)))) return rc;
+    for (hipEvent_t& e : cs->g_ev)
+        if (!e) HIPOK(hipEventCreate(&e));
+    a.words = (int64_t*)cs->g_state.p;
+    a.tile_tb = a.words + kXwWords;
+    hipStream_t s = cs->stream;
+    if (!bt.empty()) HIPOK(hipMemcpyAsync(cs->x_btail.p, bt.data(), bt.size(), hipMemcpyHostToDevice, s));
+    HIPOK(hipMemsetAsync(cs->g_state.p, 0, 8 * (size_t)kXwWords, s));
+    HIPOK(hipEventRecord(cs->g_ev[0], s));
+    launch_export_digest(s, a, levels_of(cs, cs->cur), sc.tail_used > 0 ? 2 : 1);
+    HIPOK(take_launch_error());
+    HIPOK(hipEventRecord(cs->g_ev[1], s));
+    int64_t words[kXwWords];
+    HIPOK(hipMemcpyAsync(words, cs->g_state.p, sizeof(words), hipMemcpyDeviceToHost, s));
+    HIPOK(hipStreamSynchronize(s));
+    cs->g_ms_kernels = ev_ms(cs->g_ev[0], cs->g_ev[1]);
+    cs->g_ms_host = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (((const int32_t*)&words[kXwScan])[1]) return FDBCS_E_DEVICE;  // positions out of order
+    out->n = words[kXwN];
+    out->key_bytes = words[kXwBytes];
+    out->header_version = words[kXwHeader];
+    out->sum[0] = (uint64_t)words[kDwSum0];
+    out->sum[1] = (uint64_t)words[kDwSum1];
+    return FDBCS_OK;
+}
+
+int fdbcs_history_digest_arrays(int64_t n, const uint8_t* key_bytes, const int64_t* key_offsets,
+                                const int64_t* versions, int64_t header_version, fdbcs_digest* out) {
+    if (!out || n < 0 || (n > 0 && (!key_offsets || !versions))) return FDBCS_E_INVALID;
+    if (n > 0 && key_offsets[0] != 0) return FDBCS_E_INVALID;
+    for (int64_t i = 0; i < n; i++)
+        if (key_offsets[i + 1] < key_offsets[i]) return FDBCS_E_INVALID;
+    if (n > 0 && key_offsets[n] > 0 && !key_bytes) return FDBCS_E_INVALID;
+    constexpr uint64_t G = 0x9E3779B97F4A7C15ull, S[2] = {0x243F6A8885A308D3ull, 0x13198A2E03707344ull};
+    uint64_t sum[2] = {0, 0};
+    for (int64_t i = 0; i < n; i++) {
+        const uint8_t* p = key_bytes + key_offsets[i];
+        const uint64_t len = (uint64_t)(key_offsets[i + 1] - key_offsets[i]);
+        uint64_t h[2] = {digest_mix(S[0] + len), digest_mix(S[1] + len)};
+        for (uint64_t o = 0; o < len; o += 8) {
+            uint64_t w = 0;  // bytes [o, o + 8) big-endian, zero past the key
+            for (uint64_t b = 0; b < 8; b++) w = (w << 8) | (o + b < len ? p[o + b] : 0);
+            for (uint64_t& x : h) x = digest_mix((x ^ w) + G);
+        }
+        for (int c = 0; c < 2; c++) sum[c] += digest_mix((h[c] ^ (uint64_t)versions[i]) + G);
+    }
+    out->n = n;
+    out->key_bytes = n > 0 ? key_offsets[n] : 0;
+    out->header_version = header_version;
+    out->sum[0] = sum[0];
+    out->sum[1] = sum[1];
+    return FDBCS_OK;
+}
+
+int fdbcs_history_digest_timing(fdbcs_conflict_set* cs, double* ms_kernels, double* ms_host) {
+    if (!cs || !ms_kernels || !ms_host) return FDBCS_E_INVALID;
+    *ms_kernels = cs->g_ms_kernels;
+    *ms_host = cs->g_ms_host;
     return FDBCS_OK;
 }
 

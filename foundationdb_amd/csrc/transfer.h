@@ -38,6 +38,15 @@ int64_t export_tiles(int64_t n);
 // mode: the compaction search's (1: lane_lower_bound, 2: the long-key form).
 void launch_export(hipStream_t s, const ExportArgs& a, const MaxLevels& basem, uint64_t* granules, int mode);
 
+// ---- history digest (fdbcs_history_digest): the export's searches, then one pass that hashes the
+// kept boundaries where they lie.  Takes an ExportArgs whose result pointers (versions, offsets,
+// bytes) are unused; its word block is the digest's own, zeroed before the launches: the export's
+// kXwLo, kXwHi and kXwHeader, kXwN and kXwBytes as sums over the kept boundaries, the error word of
+// kXwScan (bit 4 only: there is no scan) and the two lanes' sums below.
+enum DigestWord { kDwSum0 = 6, kDwSum1 = 7 };
+static_assert((int)kDwSum1 < (int)kXwWords && (int)kDwSum0 > (int)kXwScan, "the digest's sums lie in the export's spare words");
+void launch_export_digest(hipStream_t s, const ExportArgs& a, const MaxLevels& basem, int mode);
+
 // ---- history import (fdbcs_history_import / fdbcs_history_import_pending): folds an exported range
 // into both tiers, H'(k) = max(H(k), I(k)) over [lo, hi).  Reads the current buffers, writes only
 // scratch and the non-current base buffer and tail arena; the host switches to them on success.

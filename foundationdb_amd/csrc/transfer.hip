@@ -175,21 +175,13 @@ struct ExportScan {
     }
 };
 
-__global__ __launch_bounds__(kScanThreads) void k_export_scan(ExportArgs a, ScanState st) {
-    __shared__ uint32_t sv[3][kScanPad];
-    __shared__ uint32_t swave[3][kScanThreads / 64];
-    __shared__ uint32_t sbase[3];
-    __shared__ int s_tile;
-    __shared__ int64_t s_pos[kExpWin];
-    __shared__ int64_t s_val[kScanTile + 1];
-    __shared__ int64_t s_src[kScanTile];
-    const int64_t m_lo = a.words[kXwLo], n = a.words[kXwHi] - m_lo;
-    if (threadIdx.x == 0) s_tile = atomicAdd(st.counter, 1);
-    __syncthreads();
-    const int tile = s_tile;
-    const int64_t ntiles = n > 0 ? (n + kScanTile - 1) / kScanTile : 1;
-    if (tile >= ntiles) return;
-    const int64_t tile0 = (int64_t)tile * kScanTile;
+// The resolve step of one tile (k_export_scan, k_export_digest; the whole workgroup calls it): the
+// clamped value of the tile's predecessor and of each of its elements into s_val[0 .. cnt], each
+// element's source into s_src.  Ends with a barrier.
+__device__ __forceinline__ void export_resolve_tile(const ExportArgs& a, int64_t tile, int64_t m_lo, int64_t n,
+                                                    int64_t (&s_pos)[kExpWin], int64_t (&s_val)[kScanTile + 1],
+                                                    int64_t (&s_src)[kScanTile], int* err) {
+    const int64_t tile0 = tile * kScanTile;
     // stream elements resolved here: the tile's, and before them its predecessor (tile 0: the header)
     const int pre = tile > 0 ? 1 : 0;
     const int64_t mfirst = m_lo + tile0 - pre;
@@ -211,7 +203,7 @@ __global__ __launch_bounds__(kScanThreads) void k_export_scan(ExportArgs a, Scan
         } else {
             src = m - t;
             if (src < 0 || src >= a.nb) {  // positions out of order: never index past the tier
-                atomicOr(st.error, 4);
+                atomicOr(err, 4);
                 src = a.nb > 0 ? 0 : ~(int64_t)0;
             }
             const int64_t dv = t > 0 ? a.delta.ver[t - 1] : kHole;
@@ -223,13 +215,113 @@ __global__ __launch_bounds__(kScanThreads) void k_export_scan(ExportArgs a, Scan
     }
     if (tile == 0 && threadIdx.x == 0) s_val[0] = a.words[kXwHeader];
     __syncthreads();
-    const ExportScan f{a, s_val, s_src, tile0, st.error};
+}
+
+__global__ __launch_bounds__(kScanThreads) void k_export_scan(ExportArgs a, ScanState st) {
+    __shared__ uint32_t sv[3][kScanPad];
+    __shared__ uint32_t swave[3][kScanThreads / 64];
+    __shared__ uint32_t sbase[3];
+    __shared__ int s_tile;
+    __shared__ int64_t s_pos[kExpWin];
+    __shared__ int64_t s_val[kScanTile + 1];
+    __shared__ int64_t s_src[kScanTile];
+    const int64_t m_lo = a.words[kXwLo], n = a.words[kXwHi] - m_lo;
+    if (threadIdx.x == 0) s_tile = atomicAdd(st.counter, 1);
+    __syncthreads();
+    const int tile = s_tile;
+    const int64_t ntiles = n > 0 ? (n + kScanTile - 1) / kScanTile : 1;
+    if (tile >= ntiles) return;
+    export_resolve_tile(a, tile, m_lo, n, s_pos, s_val, s_src, st.error);
+    const ExportScan f{a, s_val, s_src, (int64_t)tile * kScanTile, st.error};
     scan_tile<3>(f, n, tile, ntiles, st, sv, swave, sbase);
+}
+
+// ---- history digest (fdbcs_history_digest; the definition is in include/fdb_conflict_set.h)
+//
+// The export's first three launches as they stand, then k_export_digest instead of k_export_scan: the
+// same tiles, resolved by the same helper, but a kept element's key is hashed where it lies instead of
+// being copied.  The four totals (kept boundaries, their key bytes, the two lanes' sums) are sums mod
+// 2^64 of per-element terms, so they need no scan, no tile order and no look-back: every workgroup
+// reduces its own and adds them to the digest's words (kXwN, kXwBytes, kDwSum0, kDwSum1).
+
+__device__ __forceinline__ uint64_t digest_mix(uint64_t z) {
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+constexpr uint64_t kDigestG = 0x9E3779B97F4A7C15ull;
+constexpr uint64_t kDigestS0 = 0x243F6A8885A308D3ull, kDigestS1 = 0x13198A2E03707344ull;
+
+__global__ __launch_bounds__(kScanThreads) void k_export_digest(ExportArgs a) {
+    __shared__ int64_t s_pos[kExpWin];
+    __shared__ int64_t s_val[kScanTile + 1];
+    __shared__ int64_t s_src[kScanTile];
+    __shared__ uint64_t s_part[kScanThreads / 64][4];
+    const int64_t m_lo = a.words[kXwLo], n = a.words[kXwHi] - m_lo;
+    const int64_t tile = blockIdx.x;
+    const int64_t ntiles = n > 0 ? (n + kScanTile - 1) / kScanTile : 1;
+    if (tile >= ntiles) return;  // spare tile of the launch sized by both tiers
+    export_resolve_tile(a, tile, m_lo, n, s_pos, s_val, s_src, (int*)&a.words[kXwScan] + 1);
+    const int64_t rest = n - tile * kScanTile;
+    const int cnt = (int)(rest < kScanTile ? rest : kScanTile);
+    uint64_t acc[4] = {0, 0, 0, 0};  // kept, key bytes, sum[0], sum[1]
+#pragma unroll
+    for (int k = 0; k < kScanPer; k++) {
+        const int e = k * kScanThreads + threadIdx.x;
+        if (e >= cnt || s_val[e + 1] == s_val[e]) continue;
+        const int64_t src = s_src[e];
+        const Hist& h = src >= 0 ? a.base : a.delta;
+        const int64_t p = src >= 0 ? src : ~src;
+        const ulonglong2 key = h.key[p];
+        const uint2 lt = h.lt[p];
+        const uint32_t len = lt.x, nw = (len + 7u) >> 3;
+        uint64_t h0 = digest_mix(kDigestS0 + len), h1 = digest_mix(kDigestS1 + len);
+        // the prefix words are the big-endian words of the definition, zero past the key
+        if (nw > 0u) h0 = digest_mix((h0 ^ key.x) + kDigestG), h1 = digest_mix((h1 ^ key.x) + kDigestG);
+        if (nw > 1u) h0 = digest_mix((h0 ^ key.y) + kDigestG), h1 = digest_mix((h1 ^ key.y) + kDigestG);
+        if (nw > 2u) {
+            // tail words hold the key's bytes lowest first; what the last one holds past the key is not read
+            const uint64_t* tw = (const uint64_t*)hist_tail(a.htail, lt.y);
+            const uint32_t last = nw - 3u, used = len & 7u;
+            for (uint32_t q = 0; q <= last; q++) {
+                uint64_t w = __builtin_bswap64(tw[q]);
+                if (q == last && used) w &= ~0ull << (64u - 8u * used);
+                h0 = digest_mix((h0 ^ w) + kDigestG);
+                h1 = digest_mix((h1 ^ w) + kDigestG);
+            }
+        }
+        const uint64_t v = (uint64_t)s_val[e + 1];
+        acc[0] += 1;
+        acc[1] += len;
+        acc[2] += digest_mix((h0 ^ v) + kDigestG);
+        acc[3] += digest_mix((h1 ^ v) + kDigestG);
+    }
+    // wave, then workgroup, then one atomic per total
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        unsigned long long x = acc[c];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+        if (lane == 0) s_part[wid][c] = x;
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        uint64_t x = 0, kept = 0;
+#pragma unroll
+        for (int q = 0; q < kScanThreads / 64; q++) x += s_part[q][threadIdx.x], kept += s_part[q][0];
+        if (kept != 0) {  // a tile that kept nothing adds nothing
+            const int word = threadIdx.x == 0 ? kXwN : threadIdx.x == 1 ? kXwBytes : threadIdx.x == 2 ? kDwSum0 : kDwSum1;
+            atomicAdd((unsigned long long*)&a.words[word], (unsigned long long)x);
+        }
+    }
 }
 
 int64_t export_tiles(int64_t n) { return n > 0 ? (n + kScanTile - 1) / kScanTile : 1; }
 
-void launch_export(hipStream_t s, const ExportArgs& a, const MaxLevels& basem, uint64_t* granules, int mode) {
+// The launches the export and the digest share: every delta boundary's stream position and value, the
+// stream positions of lo and hi with the header, and every tile's first delta boundary.
+static int64_t launch_export_head(hipStream_t s, const ExportArgs& a, const MaxLevels& basem, int mode) {
     if (a.nd > 0) {
         const dim3 grid((unsigned)((a.nd + kBlock - 1) / kBlock));
         fdb_launch(search_mode_kernel(mode, k_export_search<1>, k_export_search<2>), grid, dim3(kBlock), 0, s, a.base,
@@ -238,11 +330,21 @@ void launch_export(hipStream_t s, const ExportArgs& a, const MaxLevels& basem, u
     fdb_launch(k_export_bounds, dim3(1), dim3(64), 0, s, a);
     const int64_t tiles = export_tiles(a.nb + a.nd);
     fdb_launch(k_export_tile_starts, dim3((unsigned)((tiles + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, a);
+    return tiles;
+}
+
+void launch_export(hipStream_t s, const ExportArgs& a, const MaxLevels& basem, uint64_t* granules, int mode) {
+    const int64_t tiles = launch_export_head(s, a, basem, mode);
     ScanState st;
     st.granules = granules;
     st.counter = (int*)&a.words[kXwScan];
     st.error = st.counter + 1;
     fdb_launch(k_export_scan, dim3((unsigned)tiles), dim3(kScanThreads), 0, s, a, st);
+}
+
+void launch_export_digest(hipStream_t s, const ExportArgs& a, const MaxLevels& basem, int mode) {
+    const int64_t tiles = launch_export_head(s, a, basem, mode);
+    fdb_launch(k_export_digest, dim3((unsigned)tiles), dim3(kScanThreads), 0, s, a);
 }
 
 // ------------------------------------------------------------------ iops sample

@@ -182,6 +182,49 @@ int fdbcs_history_export_read(fdbcs_conflict_set* cs, uint8_t* key_bytes, int64_
                               int64_t* key_offsets, int64_t* versions, int64_t cap);
 /* Diagnostics: device time of the last export's kernels and host time of the last read's copies (ms). */
 int fdbcs_history_export_timing(fdbcs_conflict_set* cs, double* ms_kernels, double* ms_d2h);
+/* Digest of the canonical history over [lo, hi): 40 bytes that two holders of a range compare
+ * instead of two exports (a restored checkpoint against the set it was taken from, the two sides of
+ * a hand-over, two resolvers on different GPUs or in different processes, the device state against
+ * a host model).  No reference counterpart.  All integer, mod 2^64, restatable bit for bit on a host.
+ * The canonical history is exactly what fdbcs_history_export defines for the same arguments: the
+ * header H_f(lo) and the keys lo < k < hi where H_f changes, each with its new value v, equal
+ * neighbours coalesced (same clamp, same open bounds, INT64_MIN as floor: no clamp).
+ *   M(z):  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ *          z = z ^ (z >> 31)                 (splitmix64's finalizer, as the iops roll below)
+ *   G = 0x9E3779B97F4A7C15,  S_0 = 0x243F6A8885A308D3,  S_1 = 0x13198A2E03707344
+ * A key of L bytes is read as m = ceil(L / 8) words, w_j = bytes [8j, 8j + 8) big-endian, zero past
+ * L (the empty key has none).  For lane c in {0, 1}:
+ *   h = M(S_c + L);  for j in 0 .. m - 1: h = M((h ^ w_j) + G);  e_c(k, v) = M((h ^ (uint64)v) + G)
+ * and sum[c] is the sum of e_c over the canonical boundaries.  The length enters before any word, so
+ * "a" and "a\0" differ; the sums commute, so no order of keys, tiles or atomics matters.  Two digests
+ * are equal iff all five fields are.  Equal canonical histories always give equal digests; unequal
+ * ones collide only by hash accident (two independent 64-bit sums).  Not cryptographic: it detects
+ * divergence, it does not resist someone constructing a collision. */
+typedef struct fdbcs_digest {
+    int64_t n;              /* canonical boundaries */
+    int64_t key_bytes;      /* sum of their lengths */
+    int64_t header_version; /* H_f(lo) */
+    uint64_t sum[2];        /* sum[c] = sum of e_c(k_i, v_i) mod 2^64 */
+} fdbcs_digest;
+/* The digest of this set's canonical history over [lo, hi) under floor_version, computed on the
+ * device; the set is not modified.  n, key_bytes and header_version equal what fdbcs_history_export
+ * reports for the same arguments.  Status as the export's: FDBCS_E_STATE with batches in flight,
+ * FDBCS_E_INVALID for lo > hi or a NULL handle or out; lo == hi gives n = 0 and the header.  Unlike
+ * the export it stores no key: it allocates only one scratch pair per delta boundary, one word per
+ * 1024 boundaries and a word block (a set that was never exported is fine), it has no 2^29-boundary
+ * or 32 GiB limit, and a pending export result of the set stays pending and readable. */
+int fdbcs_history_digest(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, /* lo_len < 0: no lower bound */
+                         const uint8_t* hi_key, int32_t hi_len,                       /* hi_len < 0: no upper bound */
+                         int64_t floor_version, fdbcs_digest* out);
+/* Host only (no device is touched): the digest of arrays in the layout of fdbcs_load_history and
+ * fdbcs_history_export_read, exactly as given: nothing is canonicalised and key order is not
+ * checked.  How a checkpoint file, a host-side dump or a model's state is digested.
+ * FDBCS_E_INVALID for n < 0, a NULL array that n or the offsets say is read, key_offsets[0] != 0 or
+ * decreasing offsets. */
+int fdbcs_history_digest_arrays(int64_t n, const uint8_t* key_bytes, const int64_t* key_offsets,
+                                const int64_t* versions, int64_t header_version, fdbcs_digest* out);
+/* Diagnostics: device time of the last digest's kernels and host time of the whole call (ms). */
+int fdbcs_history_digest_timing(fdbcs_conflict_set* cs, double* ms_kernels, double* ms_host);
 /* Merge an exported history range into a live set, on the device: the receiving half of a range
  * hand-over.  No reference counterpart.  The arrays are in the layout of fdbcs_load_history and the
  * export and describe a step function I: I(k) is the version of the last imported boundary <= k,

@@ -6,12 +6,17 @@ read at set creation (directory slot budget, split check, stream layout, submitt
 compaction and GC cadence, and a sequence of batches whose snapshots straddle the oldest version; verdicts and
 conflicting-read reports must match oracle/skiplist_baseline.cpp batch by batch.
 
-    python3 scripts/stress_parity.py [seconds] [first_seed] [--state-every K] [--import-every K] [--import-into delta]
+    python3 scripts/stress_parity.py [seconds] [first_seed] [--state-every K] [--digest-every K]
+                                     [--import-every K] [--import-into delta]
 
 --state-every K (default off) also feeds the semantic oracle and compares the engine's exported
 history (ConflictSet.dump_history at floor = oldest version) with the canonical form of the oracle's
 step function every K batches: a wrong version or a lost boundary shows in the batch that made it,
 not when a later read happens to meet it.
+
+--digest-every K (default off) also feeds the semantic oracle and compares, every K batches, the
+engine's digest of its state (ConflictSet.digest at floor = oldest version: no export, no copy) with
+digest_arrays of the canonical form of the oracle's step function.
 
 --import-every K (default off; implies --state-every 1 unless given) merges, every K batches, a
 random key range of a second set's history into the engine (ConflictSet.merge_history, every other
@@ -39,6 +44,8 @@ from oracle import oracle  # noqa: E402
 from tests.export_helpers import canon, split_dump  # noqa: E402
 from tests.helpers import EngineDriver  # noqa: E402
 from tests.import_helpers import merge_max_fast, pack  # noqa: E402
+
+DIGESTS = [0]  # digests compared (--digest-every)
 
 KNOBS = {
     "FDBCS_DIR_BITS": ["0", "0", "16", "18"],
@@ -87,7 +94,7 @@ def merge_round(rng, e, o, so, key, hdr, now, pending, into="base"):
     return None, h
 
 
-def one(seed, state_every=0, import_every=0, import_into="base"):
+def one(seed, state_every=0, import_every=0, import_into="base", digest_every=0):
     rng = np.random.default_rng(seed)
     for k, vals in KNOBS.items():
         os.environ[k] = vals[int(rng.integers(0, len(vals)))]
@@ -124,7 +131,7 @@ def one(seed, state_every=0, import_every=0, import_into="base"):
     e.load_history(kb, ko, vers)
     o.load_history(kb, ko, vers)
     so = None
-    if state_every:  # the skip-list restatement has no dump: the semantic oracle holds the state
+    if state_every or digest_every:  # the skip-list restatement has no dump: the semantic oracle holds the state
         so = oracle.OracleConflictSet()
         so.load_history(kb, ko, vers)
     now, oldest, hdr, merges = 1000, 0, 0, 0
@@ -152,7 +159,14 @@ def one(seed, state_every=0, import_every=0, import_into="base"):
             return f"conflicting reads batch {i}"
         if so is not None:
             so.detect(pb, now, oldest)
-            if (i + 1) % state_every == 0:
+            if digest_every and (i + 1) % digest_every == 0:
+                keys, hv = so.dump_history()
+                want = C.digest_arrays(*pack(canon(keys, hv, hdr, so.oldest_version)))
+                got = e.cs.digest()
+                DIGESTS[0] += 1
+                if got != want:
+                    return f"digest batch {i}: {got}, oracle {want}"
+            if state_every and (i + 1) % state_every == 0:
                 keys, hv = so.dump_history()
                 want = canon(keys, hv, hdr, so.oldest_version)
                 got = split_dump(e.cs.dump_history())
@@ -174,6 +188,11 @@ def main():
         k = args.index("--state-every")
         state_every = int(args[k + 1])
         del args[k:k + 2]
+    digest_every = 0
+    if "--digest-every" in args:
+        k = args.index("--digest-every")
+        digest_every = int(args[k + 1])
+        del args[k:k + 2]
     import_every = 0
     if "--import-every" in args:
         k = args.index("--import-every")
@@ -191,7 +210,7 @@ def main():
     t0 = time.time()
     n = 0
     while time.time() - t0 < budget:
-        err = one(seed, state_every, import_every, import_into)
+        err = one(seed, state_every, import_every, import_into, digest_every)
         knobs = {k: os.environ[k] for k in KNOBS}
         if err:
             print(f"MISMATCH seed {seed} knobs {knobs}: {err}", flush=True)
@@ -201,6 +220,8 @@ def main():
             print(f"{n} rounds ok ({time.time() - t0:.0f} s), last seed {seed}", flush=True)
         seed += 1
     print(f"stress: {n} random rounds, every batch exact ({time.time() - t0:.0f} s)")
+    if digest_every:
+        print(f"stress: {DIGESTS[0]} digests equal to the oracle's")
     if import_every:
         print(f"stress: {PATHS[1]} merges into the delta, {PATHS[0]} folded into a new base")
 
