@@ -222,6 +222,10 @@ SIGNATURES = {
                                                    ctypes.POINTER(_I32), ctypes.POINTER(_I64)]),
     "fdbcs_batch_share_pack_timing": (ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_double),
                                                      ctypes.POINTER(ctypes.c_double)]),
+    "fdbcs_batch_read_versions": (ctypes.c_int, [_VP, _I64, _VP, _I64]),
+    "fdbcs_batch_read_versions_device": (ctypes.c_int, [_VP, _I64, _VP, _I64]),
+    "fdbcs_batch_read_versions_timing": (ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_double),
+                                                        ctypes.POINTER(ctypes.c_double)]),
     "fdbcs_debug_kernel_time": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
     "fdbcs_kernel_profile": (ctypes.c_int, [_VP, _I32, ctypes.c_char_p, _I32, ctypes.POINTER(_I64),
                                             ctypes.POINTER(ctypes.c_double)]),
@@ -502,6 +506,32 @@ class ConflictSet:
         _check(load_library().fdbcs_history_digest_timing(self._h, ctypes.byref(a), ctypes.byref(b)), "digestTiming")
         return a.value, b.value
 
+    def read_versions(self, ranges, floor: Optional[int] = None) -> np.ndarray:
+        """The history version each of `ranges` (a list of (begin, end) byte pairs, begin <= end) is
+        checked against, int64 per range: ConflictBatch.read_versions of one throw-away batch whose
+        reads they are.  `(r > V).any()` answers "did anything in these ranges change since version
+        V" without spending a transaction; a.read_versions(rs) == b.read_versions(rs) checks a
+        hand-over pointwise.  With no batch of the set in flight."""
+        ranges = [(bytes(b), bytes(e)) for b, e in ranges]
+        if not ranges:
+            return np.empty(0, np.int64)
+        keys = [k for r in ranges for k in r]
+        ko = np.zeros(len(keys) + 1, np.int64)
+        np.cumsum([len(k) for k in keys], out=ko[1:])
+        # one transaction no oldest version makes TooOld (a TooOld transaction carries no ranges)
+        pb = PackedBatch(np.full(1, (1 << 63) - 1, np.int64), np.zeros(1, np.uint8), np.array([0, len(ranges)], np.int32),
+                         np.zeros(2, np.int32), np.frombuffer(b"".join(keys), np.uint8), ko)
+        batch = ConflictBatch(self)
+        try:
+            batch.add_packed(pb)
+            return batch.read_versions(floor)
+        finally:
+            batch.close()
+
+    def version_at(self, key: bytes, floor: Optional[int] = None) -> int:
+        """The version a read of `key` sees: the read [key, key + b"\\x00")."""
+        return int(self.read_versions([(key, bytes(key) + b"\x00")], floor)[0])
+
     @staticmethod
     def _bounds(lo: Optional[bytes], hi: Optional[bytes]):
         kl = np.frombuffer(lo if lo is not None else b"", np.uint8)
@@ -600,6 +630,10 @@ class ConflictBatch:
         self.cs = cs
         self.conflicting_key_range_map = conflicting_key_range_map
         self.transaction_count = 0
+        self._n_reads = 0  # read ranges added
+        # per add call what tells the reads of each of its transactions: a count, or a packed batch's
+        # read_offsets as given (only read_versions looks at them, for a batch with TooOld transactions)
+        self._txn_reads: list = []
         self._report: List[bool] = []
         self._has_reads: List[bool] = []
         self._keep = []  # arrays that must outlive add calls (keys are copied by the library)
@@ -648,6 +682,8 @@ class ConflictBatch:
         )
         _check(rc, "addTransaction")
         self.transaction_count += 1
+        self._n_reads += len(tr.read_conflict_ranges)
+        self._txn_reads.append(len(tr.read_conflict_ranges))
         if self.conflicting_key_range_map is not None:
             self._report.append(bool(tr.report_conflicting_keys))
             self._has_reads.append(len(tr.read_conflict_ranges) > 0)
@@ -657,6 +693,8 @@ class ConflictBatch:
         cs = pb.c_struct()
         _check(load_library().fdbcs_batch_add_packed(self._h, ctypes.byref(cs)), "addTransaction(packed)")
         self.transaction_count += pb.n_txn
+        self._n_reads += pb.n_reads
+        self._txn_reads.append(pb.read_offsets)
         if self.conflicting_key_range_map is not None:  # per-transaction bookkeeping only for reports
             self._report.extend(bool(x) for x in pb.report)
             self._has_reads.extend((np.diff(pb.read_offsets) > 0).tolist())
@@ -675,6 +713,7 @@ class ConflictBatch:
         if rc != FDBCS_OK:
             raise FdbcsError(rc, "addPackedDevice")
         self.transaction_count = int(dpb.n_txn)
+        self._n_reads = int(dpb.n_reads)
         self._dev_added = True
 
     def device_add_info(self) -> Tuple[int, int, int, int]:
@@ -687,6 +726,7 @@ class ConflictBatch:
         if rc != FDBCS_OK:
             if rc != FDBCS_E_STATE:
                 self.transaction_count = 0
+                self._n_reads = 0
                 self._dev_added = False
             raise FdbcsError(rc, "deviceAddInfo")
         return T.value, R.value, W.value, tb.value
@@ -820,6 +860,62 @@ class ConflictBatch:
         us = ctypes.c_double()
         _check(load_library().fdbcs_debug_kernel_time(self._h, which, reps, ctypes.byref(us)), "debugKernelTime")
         return us.value
+
+    def _floor(self, floor: Optional[int]) -> int:
+        return self.cs.oldest_version if floor is None else int(floor)
+
+    def _read_versions_failed(self, rc: int, what: str):
+        # a violation the add kernels found surfaces here as it does from device_add_info()
+        if getattr(self, "_dev_added", False) and rc not in (FDBCS_E_STATE, FDBCS_E_NOMEM):
+            self.transaction_count = 0
+            self._n_reads = 0
+            self._dev_added = False
+        raise FdbcsError(rc, what)
+
+    def _held_reads(self) -> int:
+        """Reads the batch holds: a transaction that was TooOld when added carries no ranges
+        (SkipList.cpp:770-790); a device-added batch is judged at detect and holds them all."""
+        if getattr(self, "_dev_added", False) or not self._txn_reads:
+            return self._n_reads
+        too_old: List[int] = []
+        self.get_too_old_transactions(too_old)
+        if not too_old:
+            return self._n_reads
+        per_txn = np.concatenate([np.diff(x) if isinstance(x, np.ndarray) else [x] for x in self._txn_reads])
+        return self._n_reads - int(per_txn[too_old].sum())
+
+    def read_versions(self, floor: Optional[int] = None) -> np.ndarray:
+        """fdbcs_batch_read_versions: int64 per read of this batch (in read order), the history
+        version the read is checked against: the greatest version any key of [begin, end) reads (for
+        an empty read [k, k): the version just below k), with versions below `floor` (default: the
+        oldest version; NO_FLOOR: none) read as floor - 1.  A read that is not TooOld conflicts with
+        the history iff its entry is above its snapshot; the reads of a transaction that was TooOld
+        when added are not held by the batch and have no entry.  On a batch that is being added or
+        is uploaded, with no batch of the set in flight; the batch is uploaded and can be detected
+        afterwards as if it had not been queried."""
+        out = np.empty(self._held_reads(), np.int64)
+        rc = load_library().fdbcs_batch_read_versions(self._h, self._floor(floor), _p(out), len(out))
+        if rc != FDBCS_OK:
+            self._read_versions_failed(rc, "readVersions")
+        return out
+
+    def read_versions_device(self, dev_out_ptr: int, cap: int, floor: Optional[int] = None) -> None:
+        """fdbcs_batch_read_versions_device: the same, written as int64 to the `cap` entries of
+        device memory at `dev_out_ptr` (the set's GPU; e.g. a torch tensor's data_ptr()); complete
+        when the call returns."""
+        rc = load_library().fdbcs_batch_read_versions_device(self._h, self._floor(floor), _VP(dev_out_ptr or None),
+                                                             int(cap))
+        if rc != FDBCS_OK:
+            self._read_versions_failed(rc, "readVersionsDevice")
+
+    def read_versions_timing(self) -> Tuple[float, float]:
+        """Milliseconds of the last read_versions kernel on this batch's set (device) and of the whole
+        call (host)."""
+        a, b = ctypes.c_double(), ctypes.c_double()
+        rc = load_library().fdbcs_batch_read_versions_timing(self._h, ctypes.byref(a), ctypes.byref(b))
+        if rc != FDBCS_OK:
+            raise FdbcsError(rc, "readVersionsTiming")
+        return a.value, b.value
 
     def device_verdicts_ptr(self) -> int:
         p = ctypes.c_void_p()

@@ -928,6 +928,10 @@ void fdbcs_destroy_conflict_set(fdbcs_conflict_set* cs) {
     cs->g_state.release();
     for (hipEvent_t e : cs->g_ev)
         if (e) (void)hipEventDestroy(e);
+    cs->rv_out.release();
+    cs->rv_err.release();
+    for (hipEvent_t e : cs->rv_ev)
+        if (e) (void)hipEventDestroy(e);
     for (DBuf* x : {&cs->i_bytes, &cs->i_off, &cs->i_ver, &cs->i_bnd, &cs->i_okey, &cs->i_olt, &cs->i_over, &cs->i_otail,
                     &cs->i_mval, &cs->i_mkey, &cs->i_mlt, &cs->i_dblt, &cs->i_vblt, &cs->i_state,
                     &cs->i_gran, &cs->i_dstate})

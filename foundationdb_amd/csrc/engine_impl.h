@@ -413,6 +413,11 @@ struct fdbcs_conflict_set {
     DBuf g_state;
     hipEvent_t g_ev[2] = {};                      // around the digest's kernels
     double g_ms_kernels = 0, g_ms_host = 0;       // of the last digest (fdbcs_history_digest_timing)
+    // fdbcs_batch_read_versions: the host form's result (grow-only; the device form writes to the
+    // caller's memory) and the error word, allocated by the first query; nothing of the export's
+    DBuf rv_out, rv_err;
+    hipEvent_t rv_ev[2] = {};                     // around the query's kernel
+    double rv_ms_kernels = 0, rv_ms_host = 0;     // of the last query (fdbcs_batch_read_versions_timing)
     // fdbcs_history_import: device copies of the imported arrays (host-array form), the bounds' bytes,
     // the overlay stream (keys, lt, versions, tails), the merged stream (value, key, lt) and the import
     // words; all allocated by the first import and freed with the set.

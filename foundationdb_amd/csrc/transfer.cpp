@@ -1,7 +1,8 @@
 // transfer.cpp — the maintenance entry points of the C-ABI (include/fdb_conflict_set.h): history
-// export, the two history imports and the resolver's iops sample.  They work on an idle set (or,
-// for the sample, off the detect stream) through the state and helpers of engine_impl.h and launch
-// the kernels of transfer.hip; the detect pipeline's host side is engine.cpp.
+// export, the two history imports, the resolver's iops sample and the read versions of a batch.
+// They work on an idle set (or, for the sample, off the detect stream) through the state and
+// helpers of engine_impl.h and launch the kernels of transfer.hip; the detect pipeline's host side
+// is engine.cpp.
 #include "engine_impl.h"
 #include "transfer.h"
 
@@ -711,6 +712,79 @@ int fdbcs_batch_iops_sample_timing(fdbcs_batch* b, double* ms_kernels) {
     if (!b || !ms_kernels) return FDBCS_E_INVALID;
     if (!b->is_req || !b->is_done) return FDBCS_E_STATE;
     *ms_kernels = b->is_ms;
+    return FDBCS_OK;
+}
+
+// ---- the version each read of a batch is checked against
+
+// Either form of the query: the host form writes the set's own buffer and copies it out, the device
+// form writes the caller's memory.  The batch ends as an uploaded, undetected batch; neither the
+// set, its batch workspaces nor a pending export is touched.
+static int read_versions(fdbcs_batch* b, int64_t floor_version, int64_t* out, int64_t cap, bool device_form) {
+    if (!b) return FDBCS_E_INVALID;
+    const auto t0 = std::chrono::steady_clock::now();
+    fdbcs_conflict_set* cs = b->cs;
+    if (!cs) return FDBCS_E_STATE;
+    if (b->share_packed || (b->routed && !b->dev_added) || b->state > 1) return FDBCS_E_STATE;
+    if (cs->inflight) return FDBCS_E_STATE;
+    HIPOK(hipSetDevice(cs->device));
+    // a device-added batch: its add kernels first (a malformed one is FDBCS_E_INVALID and empty again)
+    if (int rc = finish_route(b)) return rc;
+    const int64_t R = b->R();
+    if (R == 0) return FDBCS_OK;
+    if (!out) return FDBCS_E_INVALID;
+    if (cap < R) return FDBCS_E_NOMEM;
+    if (b->state == 0)
+        if (int rc = fdbcs_batch_upload(b)) return rc;
+    if (int rc = sync_all(cs)) return rc;  // the upload too
+    if (cs->rv_err.ensure(sizeof(int))) return FDBCS_E_NOMEM;
+    if (!device_form && cs->rv_out.ensure(8 * (size_t)R)) return FDBCS_E_NOMEM;
+    for (hipEvent_t& e : cs->rv_ev)
+        if (!e) HIPOK(hipEventCreate(&e));
+    Scalars* sc = (Scalars*)cs->scal.p;
+    ReadVersionsArgs a{};
+    a.b = b->bd;
+    a.base = Tier{hist_of(cs, cs->cur), levels_of(cs, cs->cur), &sc->n, cs->header_version};
+    a.delta = Tier{delta_of(cs, cs->dcur), dlevels_of(cs, cs->dcur), &sc->ndb[cs->dcur], kHole};
+    a.htail = (const uint8_t*)cs->htail[cs->tcur].p;
+    a.floor = floor_version;
+    a.out = device_form ? out : (int64_t*)cs->rv_out.p;
+    a.error = (int*)cs->rv_err.p;
+    hipStream_t s = cs->stream;
+    t_record = nullptr;
+    HIPOK(hipMemsetAsync(cs->rv_err.p, 0, sizeof(int), s));
+    HIPOK(hipEventRecord(cs->rv_ev[0], s));
+    // the long-key form by the read check's rule (engine.cpp plan_layout)
+    const void* func = launch_read_versions(s, a, b->max_len > 24);
+    HIPOK(take_launch_error());
+    HIPOK(hipEventRecord(cs->rv_ev[1], s));
+    int err = 0;
+    HIPOK(hipMemcpyAsync(&err, cs->rv_err.p, sizeof(err), hipMemcpyDeviceToHost, s));
+    if (!device_form) HIPOK(hipMemcpyAsync(out, cs->rv_out.p, 8 * (size_t)R, hipMemcpyDeviceToHost, s));
+    HIPOK(hipStreamSynchronize(s));
+    cs->rv_ms_kernels = ev_ms(cs->rv_ev[0], cs->rv_ev[1]);
+    // which instantiation ran, as fdbcs_kernel_profile reports the pipeline's kernels
+    auto it = std::find_if(cs->kprof.begin(), cs->kprof.end(), [&](const auto& k) { return k.func == func; });
+    if (it == cs->kprof.end()) it = cs->kprof.insert(cs->kprof.end(), {func, 0, 0.0});
+    it->launches += 1;
+    it->ms += cs->rv_ms_kernels;
+    cs->rv_ms_host = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return err ? FDBCS_E_DEVICE : FDBCS_OK;  // a lookup left its tier: the tiers are inconsistent
+}
+
+int fdbcs_batch_read_versions(fdbcs_batch* b, int64_t floor_version, int64_t* versions_out, int64_t cap) {
+    return read_versions(b, floor_version, versions_out, cap, false);
+}
+
+int fdbcs_batch_read_versions_device(fdbcs_batch* b, int64_t floor_version, int64_t* dev_out, int64_t cap) {
+    return read_versions(b, floor_version, dev_out, cap, true);
+}
+
+int fdbcs_batch_read_versions_timing(fdbcs_batch* b, double* ms_kernels, double* ms_host) {
+    if (!b || !ms_kernels || !ms_host) return FDBCS_E_INVALID;
+    if (!b->cs) return FDBCS_E_STATE;
+    *ms_kernels = b->cs->rv_ms_kernels;
+    *ms_host = b->cs->rv_ms_host;
     return FDBCS_OK;
 }
 

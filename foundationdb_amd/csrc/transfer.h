@@ -1,6 +1,7 @@
 // transfer.h — internal interface between the maintenance entry points (transfer.cpp) and their
-// gfx950 kernels (transfer.hip): history export, the two history imports and the resolver's iops
-// sample.  Not part of the public C-ABI; the detect pipeline's interface is engine.h.
+// gfx950 kernels (transfer.hip): history export, the two history imports, the resolver's iops
+// sample and the read versions of a batch.  Not part of the public C-ABI; the detect pipeline's
+// interface is engine.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -181,5 +182,21 @@ struct IopsArgs {
 int64_t iops_scan_words(int64_t cap);
 // One launch on `s`, after the routing's; the scan state is zeroed by the caller.
 void launch_iops_sample(hipStream_t s, const IopsArgs& a, ScanState st);
+
+// ---- the version each read of a batch is checked against (fdbcs_batch_read_versions): per read r of
+// an uploaded batch, out[r] = the greatest H_f(k) over the read's keys (a degenerate read: H_f just
+// below its key), against an idle set.  Reads the batch's endpoint keys and both tiers; writes out
+// and, for a position no consistent tier can give, bit 0 of *error.
+struct ReadVersionsArgs {
+    BatchDev b;            // the uploaded batch: keys [2R] and tail are read, nothing else
+    Tier base, delta;      // the set's tiers as the read check sees them (sizes read on the device)
+    const uint8_t* htail;  // their tail arena
+    int64_t floor;         // versions below it read floor - 1 (kHole: no clamp)
+    int64_t* out;          // [R] device memory
+    int* error;            // one word, zeroed before the launch
+};
+// One launch on `s` (none for a batch without reads).  long_keys: as launch_check's.  Returns the
+// kernel launched (the instantiation's host function, as fdbcs_kernel_profile names kernels).
+const void* launch_read_versions(hipStream_t s, const ReadVersionsArgs& a, bool long_keys);
 
 }  // namespace fdbcs

@@ -1,7 +1,8 @@
 // transfer.hip — gfx950 kernels of the maintenance side of the engine: history export, the two
-// history imports and the resolver's iops sample.  They run on an idle set or off the detect
-// stream (transfer.cpp); the detect pipeline's kernels are in kernels.hip and call nothing here.
-// The searches both sides use are in search.h, the look-back scan in scan.h.
+// history imports, the resolver's iops sample and the read versions of a batch.  They run on an
+// idle set or off the detect stream (transfer.cpp); the detect pipeline's kernels are in
+// kernels.hip and call nothing here.  The searches both sides use are in search.h, the look-back
+// scan in scan.h.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 
@@ -878,5 +879,118 @@ void launch_import_delta_merge(hipStream_t s, const ImportDeltaArgs& d, uint64_t
     }
 }
 
+// ------------------------------------------------------------------ read versions
+//
+// V_r of every read of an uploaded batch against an idle set (fdbcs_batch_read_versions; the
+// definition is in include/fdb_conflict_set.h): the greatest clamped version H_f(k) over the read's
+// keys, or for a degenerate read [b, b) the version just below b.  The lookups are the read check's
+// (kernels.hip check_read_lanes: four lanes per read, begin and end key in the base and the delta
+// tier, the begin lane taking the end's position by a shuffle); what follows them is not: a range
+// maximum with no snapshot to stop at, so every level entry the span touches is read and a stale or
+// missed one shows as a wrong number.  Reads the batch's keys and the tiers, writes one word per
+// read; no snapshot, flag, write or workspace of the batch plays a part.
+
+// Entry i of a tier's top level: the max over its kL3Rep replicas (kernels.hip l3_at).
+__device__ __forceinline__ int64_t l3_entry(const int64_t* a, int64_t i) {
+    int64_t v[kL3Rep];
+#pragma unroll
+    for (int r = 0; r < kL3Rep; r++) v[r] = a[(i * kL3Rep + r) * kL3Pad];
+    int64_t best = v[0];
+#pragma unroll
+    for (int r = 1; r < kL3Rep; r++) best = v[r] > best ? v[r] : best;
+    return best;
+}
+
+// max(best, a[lo, hi)), four independent loads per round.
+__device__ __forceinline__ int64_t span_max(const int64_t* a, int64_t lo, int64_t hi, int64_t best) {
+    int64_t i = lo;
+    for (; i + 4 <= hi; i += 4) {
+        const int64_t v0 = a[i], v1 = a[i + 1], v2 = a[i + 2], v3 = a[i + 3];
+        const int64_t m0 = v0 > v1 ? v0 : v1, m1 = v2 > v3 ? v2 : v3;
+        const int64_t m = m0 > m1 ? m0 : m1;
+        best = m > best ? m : best;
+    }
+    for (; i < hi; i++) {
+        const int64_t v = a[i];
+        best = v > best ? v : best;
+    }
+    return best;
+}
+
+// The exact max of lvl[0][lo, hi) through the 64-ary hierarchy (LLONG_MIN for an empty span): per
+// level the entries before the first and after the last whole block, the whole blocks one level up;
+// a span of at most two blocks, or what reaches the top level, entry by entry.
+__device__ __forceinline__ int64_t range_max_full(const MaxLevels& m, int64_t lo, int64_t hi) {
+    int64_t best = LLONG_MIN;
+    for (int L = 0; L < kMaxLevels - 1; L++) {
+        const int64_t* a = m.lvl[L];
+        if (hi - lo <= 2 * kFan) return span_max(a, lo, hi, best);
+        const int64_t lo2 = (lo + kFan - 1) / kFan, hi2 = hi / kFan;
+        best = span_max(a, lo, lo2 * kFan, best);
+        best = span_max(a, hi2 * kFan, hi, best);
+        lo = lo2;
+        hi = hi2;
+    }
+    const int64_t* a = m.lvl[kMaxLevels - 1];
+    for (int64_t i = lo; i < hi; i++) {
+        const int64_t v = l3_entry(a, i);
+        best = v > best ? v : best;
+    }
+    return best;
+}
+
+template <bool LONG>
+__global__ __launch_bounds__(kBlock) void k_read_versions(ReadVersionsArgs a) {
+    const BatchDev& b = a.b;
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t r = t >> 2;
+    const int k = (int)(t & 3);
+    const bool live = r < b.R;
+    const int64_t rr = live ? r : 0;
+    const DKey kb = b.keys[2 * rr], ke = b.keys[2 * rr + 1];
+    const bool degenerate = dkey_cmp(kb, b.tail, ke, b.tail) == 0;
+    const bool is_delta = k >= 2;
+    const Tier& tier = is_delta ? a.delta : a.base;
+    const int64_t n = *tier.n;
+    const bool active = live && (!is_delta || n > 0);
+    int64_t lb = 0;
+    bool eq = false;
+    if (active && !((k & 1) && degenerate)) {
+        const DKey& q = (k & 1) ? ke : kb;
+        if constexpr (LONG) {
+            QTail qt;
+            load_qtail(qt, q, b.tail);
+            lb = lane_lower_bound_long(tier.h, tier.m, n, q, qt, a.htail, b.tail, eq);
+        } else {
+            lb = lane_lower_bound(tier.h, tier.m, n, q, a.htail, b.tail, eq);
+        }
+    }
+    const int64_t j = __shfl_xor(lb, 1, 64);  // the begin lane takes the end key's position
+    int64_t v = kHole;
+    if (active && !(k & 1)) {
+        const int64_t hdr = is_delta ? kHole : tier.hdr;
+        const int64_t ub = lb + (eq ? 1 : 0);
+        if (lb < 0 || lb > n || (!degenerate && (j < ub || j > n))) {
+            atomicOr(a.error, 1);  // a position outside the tier, or the end's below the begin's
+        } else if (degenerate) {
+            v = lb > 0 ? tier.h.ver[lb - 1] : hdr;  // the greatest boundary < b
+        } else {
+            // segments [ub - 1, j): the one containing b (the header if ub == 0) and the boundaries in (b, e)
+            v = range_max_full(tier.m, ub > 0 ? ub - 1 : 0, j);
+            if (ub == 0) v = hdr > v ? hdr : v;
+        }
+    }
+    const int64_t o = __shfl_xor(v, 2, 64);  // the delta tier's value to the quad's first lane
+    v = o > v ? o : v;
+    if (live && k == 0) a.out[r] = export_clamp(v, a.floor);
+}
+
+const void* launch_read_versions(hipStream_t s, const ReadVersionsArgs& a, bool long_keys) {
+    if (a.b.R == 0) return nullptr;
+    const int grid = (int)(((int64_t)a.b.R * 4 + kBlock - 1) / kBlock);
+    const auto k = long_keys ? k_read_versions<true> : k_read_versions<false>;
+    fdb_launch(k, dim3(grid), dim3(kBlock), 0, s, a);
+    return (const void*)k;
+}
 
 }  // namespace fdbcs

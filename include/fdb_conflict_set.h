@@ -634,6 +634,51 @@ int fdbcs_batch_share_pack_info(fdbcs_batch* b, int64_t* bytes, int32_t* n_txn, 
                                 int64_t* tail_bytes);
 int fdbcs_batch_share_pack_timing(fdbcs_batch* b, double* ms_kernels, double* ms_host);
 
+/* The history version each read of a batch is checked against, computed on the device against an
+ * idle set; neither the set nor the batch's outcome is modified.  No reference counterpart (the
+ * reference's CheckMax answers only "above the snapshot or not").
+ * With H(k) the version a read of key k sees and a floor f, H_f is exactly the export's clamp:
+ *   H_f(k) = H(k) if H(k) >= f, otherwise f - 1;  f = INT64_MIN: no clamp.
+ * For read r of the batch, with range [b, e), the result V_r is
+ *   b <  e:  V_r = max { H_f(k) : b <= k < e }: the segment containing b (the header if no
+ *            boundary is <= b) and every boundary inside (b, e); a boundary at e does not count.
+ *   b == e:  V_r = H_f just below b: the version of the greatest boundary < b, or the set's header
+ *            if there is none.  The empty key and a b equal to the first boundary both give the
+ *            header.  This is the reference's finger rule for empty reads (SkipList.cpp:650-666),
+ *            the rule the read check follows.
+ * Across the tiers V is the greater of the base tier's value and the delta tier's (a hole is
+ * INT64_MIN, and the delta has no header): a delta version that is not a hole is at least every base
+ * version it covers, which the two-tier read check already rests on.  Consequences:
+ *   1. At f <= the oldest version, a read that is not TooOld conflicts with the history iff
+ *      V_r > its snapshot.
+ *   2. At f = the oldest version the result does not depend on how the history is split between the
+ *      tiers, on when compaction or GC ran, or on which GPU or process holds the set.
+ * Snapshots, TooOld, report flags and the batch's writes play no part.
+ *
+ * The batch: one that is being added or is uploaded (a batch still being added is uploaded, as by
+ * fdbcs_batch_upload), built by fdbcs_batch_add_transaction, fdbcs_batch_add_packed or
+ * fdbcs_batch_add_packed_device; for a device-added batch the call first waits for its add kernels,
+ * and a malformed one gives FDBCS_E_INVALID and is left as a failed detect leaves it (empty again).
+ * Entry r of the output is V_r, in the order of the reads the batch holds (R of them): a
+ * transaction that was TooOld when the host added it carries no ranges (SkipList.cpp:770-790), so
+ * its reads are not held and have no entry; a device-added batch is judged at detect and holds
+ * them all.  A batch without reads writes nothing and is FDBCS_OK.  Both forms are complete when the call returns; the device form (dev_out: device
+ * memory of the set's GPU) copies nothing to the host but its error word.  The host form's result
+ * passes through a grow-only buffer owned by the set.
+ * The batch stays an uploaded, undetected batch: a later detect gives exactly the verdicts and
+ * conflicting reads it would have given without the query, nothing the pipeline expects zeroed is
+ * dirtied, and a pending export result of the set stays pending and readable.
+ * FDBCS_E_STATE: batches are in flight on the set; the batch is submitted or done; it was routed or
+ * packed a share; its set is gone.  FDBCS_E_NOMEM: cap < R, or the result buffer cannot grow.
+ * FDBCS_E_INVALID: a NULL handle, or a NULL output with R > 0.
+ * fdbcs_batch_read_versions_timing: device time of the last query's kernel on the batch's set and
+ * host time of the whole call (ms).  Every query's launch also counts in fdbcs_kernel_profile of the
+ * set under its kernel's name, k_read_versions<false> or, for a batch with a key over 24 bytes (the
+ * read check's rule for its long-key lookups), k_read_versions<true>. */
+int fdbcs_batch_read_versions(fdbcs_batch* b, int64_t floor_version, int64_t* versions_out, int64_t cap); /* host [R] */
+int fdbcs_batch_read_versions_device(fdbcs_batch* b, int64_t floor_version, int64_t* dev_out, int64_t cap);
+int fdbcs_batch_read_versions_timing(fdbcs_batch* b, double* ms_kernels, double* ms_host);
+
 /* Diagnostics (tuning, not part of the ConflictSet contract): average device time of one launch
  * of a pipeline kernel over `reps` back-to-back launches on the uploaded batch `b` against the
  * current history, with no batch in flight.  which: 0 = the read check (D.CheckRead); 1-2 = the
@@ -642,7 +687,7 @@ int fdbcs_batch_share_pack_timing(fdbcs_batch* b, double* ms_kernels, double* ms
 int fdbcs_debug_kernel_time(fdbcs_batch* b, int which, int reps, double* us_per_launch);
 /* Per-kernel device time accumulated since fdbcs_reset_stats: timing level 3 brackets every kernel
  * of every batch with events, level 1 the kernel named by fdbcs_set_timed_kernel on the sampled
- * batches.  Entry `index` (0-based; FDBCS_E_INVALID past the last): demangled kernel name (without
+ * batches, and the kernel of every fdbcs_batch_read_versions call at any level.  Entry `index` (0-based; FDBCS_E_INVALID past the last): demangled kernel name (without
  * namespace and parameters) into name[cap], its timed launches and their total milliseconds. */
 int fdbcs_kernel_profile(fdbcs_conflict_set* cs, int32_t index, char* name, int32_t cap, int64_t* launches,
                          double* ms);

@@ -7,7 +7,7 @@ compaction and GC cadence, and a sequence of batches whose snapshots straddle th
 conflicting-read reports must match oracle/skiplist_baseline.cpp batch by batch.
 
     python3 scripts/stress_parity.py [seconds] [first_seed] [--state-every K] [--digest-every K]
-                                     [--import-every K] [--import-into delta]
+                                     [--import-every K] [--import-into delta] [--read-versions-every K]
 
 --state-every K (default off) also feeds the semantic oracle and compares the engine's exported
 history (ConflictSet.dump_history at floor = oldest version) with the canonical form of the oracle's
@@ -28,6 +28,12 @@ verdicts the merged history gives.
 back to the fold when the delta could pass its bound); the final line counts the merges that took
 the delta path.
 
+--read-versions-every K (default off) also feeds the semantic oracle and compares, every K batches,
+ConflictSet.read_versions over a few hundred random ranges (ends drawn from the batch's own keys and
+the oracle's boundaries, by a generator of its own: the other options' streams are unchanged; every
+tenth range empty) with the plain-Python model (tests/read_versions_model.py) on the oracle's dump,
+at floor = oldest version.
+
 Exit status 1 and the failing seed on the first mismatch."""
 import os
 import sys
@@ -44,8 +50,10 @@ from oracle import oracle  # noqa: E402
 from tests.export_helpers import canon, split_dump  # noqa: E402
 from tests.helpers import EngineDriver  # noqa: E402
 from tests.import_helpers import merge_max_fast, pack  # noqa: E402
+from tests import read_versions_model  # noqa: E402
 
 DIGESTS = [0]  # digests compared (--digest-every)
+QUERIES = [0]  # ranges compared (--read-versions-every)
 
 KNOBS = {
     "FDBCS_DIR_BITS": ["0", "0", "16", "18"],
@@ -94,8 +102,9 @@ def merge_round(rng, e, o, so, key, hdr, now, pending, into="base"):
     return None, h
 
 
-def one(seed, state_every=0, import_every=0, import_into="base", digest_every=0):
+def one(seed, state_every=0, import_every=0, import_into="base", digest_every=0, read_versions_every=0):
     rng = np.random.default_rng(seed)
+    qrng = np.random.default_rng([seed, 15])
     for k, vals in KNOBS.items():
         os.environ[k] = vals[int(rng.integers(0, len(vals)))]
     kind = ["bytes", "digits", "sparse", "tiny"][int(rng.integers(0, 4))]
@@ -131,7 +140,7 @@ def one(seed, state_every=0, import_every=0, import_into="base", digest_every=0)
     e.load_history(kb, ko, vers)
     o.load_history(kb, ko, vers)
     so = None
-    if state_every or digest_every:  # the skip-list restatement has no dump: the semantic oracle holds the state
+    if state_every or digest_every or read_versions_every:  # the skip-list restatement has no dump: the semantic oracle holds the state
         so = oracle.OracleConflictSet()
         so.load_history(kb, ko, vers)
     now, oldest, hdr, merges = 1000, 0, 0, 0
@@ -166,6 +175,19 @@ def one(seed, state_every=0, import_every=0, import_into="base", digest_every=0)
                 DIGESTS[0] += 1
                 if got != want:
                     return f"digest batch {i}: {got}, oracle {want}"
+            if read_versions_every and (i + 1) % read_versions_every == 0:
+                keys, hv = so.dump_history()
+                pool = sorted(set(keys) | {pb.key(k) for k in range(len(pb.key_offsets) - 1)} | {b""})
+                ranges = []
+                for _ in range(300):
+                    a, b = sorted(qrng.integers(0, len(pool), size=2).tolist())
+                    ranges.append((pool[a], pool[a] if qrng.random() < 0.1 else pool[b]))
+                want = read_versions_model.read_versions(keys, hv.tolist(), hdr, ranges, so.oldest_version)
+                got = e.cs.read_versions(ranges).tolist()
+                QUERIES[0] += len(ranges)
+                if got != want:
+                    d = next(j for j in range(len(want)) if j >= len(got) or got[j] != want[j])
+                    return f"read versions batch {i}: range {ranges[d]!r}: {got[d:d + 1]}, model {want[d]}"
             if state_every and (i + 1) % state_every == 0:
                 keys, hv = so.dump_history()
                 want = canon(keys, hv, hdr, so.oldest_version)
@@ -204,13 +226,18 @@ def main():
         k = args.index("--import-into")
         import_into = args[k + 1]
         del args[k:k + 2]
+    read_versions_every = 0
+    if "--read-versions-every" in args:
+        k = args.index("--read-versions-every")
+        read_versions_every = int(args[k + 1])
+        del args[k:k + 2]
     budget = float(args[0]) if len(args) > 0 else 120.0
     seed = int(args[1]) if len(args) > 1 else 1
     oracle.build()
     t0 = time.time()
     n = 0
     while time.time() - t0 < budget:
-        err = one(seed, state_every, import_every, import_into, digest_every)
+        err = one(seed, state_every, import_every, import_into, digest_every, read_versions_every)
         knobs = {k: os.environ[k] for k in KNOBS}
         if err:
             print(f"MISMATCH seed {seed} knobs {knobs}: {err}", flush=True)
@@ -222,6 +249,8 @@ def main():
     print(f"stress: {n} random rounds, every batch exact ({time.time() - t0:.0f} s)")
     if digest_every:
         print(f"stress: {DIGESTS[0]} digests equal to the oracle's")
+    if read_versions_every:
+        print(f"stress: {QUERIES[0]} read versions equal to the model's")
     if import_every:
         print(f"stress: {PATHS[1]} merges into the delta, {PATHS[0]} folded into a new base")
 
