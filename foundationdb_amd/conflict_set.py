@@ -231,6 +231,7 @@ SIGNATURES = {
                                             ctypes.POINTER(ctypes.c_double)]),
     "fdbcs_set_timed_kernel": (ctypes.c_int, [_VP, ctypes.c_char_p]),
     "fdbcs_debug_hold": (ctypes.c_int, [_VP, _I32]),
+    "fdbcs_debug_live_resources": (ctypes.c_int, [ctypes.POINTER(_I64)] * 4),
     "fdbcs_sync": (ctypes.c_int, [_VP]),
     "fdbcs_strerror": (ctypes.c_char_p, [ctypes.c_int]),
 }
@@ -320,6 +321,16 @@ def digest_arrays(key_bytes, key_offsets, versions, header_version: int = 0) -> 
     if rc != FDBCS_OK:
         raise FdbcsError(rc, "historyDigestArrays")
     return HistoryDigest._of(d)
+
+
+def live_resources() -> Tuple[int, int, int, int]:
+    """fdbcs_debug_live_resources: (device buffers, pinned host buffers, events, streams) the engine
+    holds right now, over every set and batch of the process.  Needs no device.  Diagnostics."""
+    n = [_I64() for _ in range(4)]
+    rc = load_library().fdbcs_debug_live_resources(*[ctypes.byref(x) for x in n])
+    if rc != FDBCS_OK:
+        raise FdbcsError(rc, "debugLiveResources")
+    return tuple(x.value for x in n)
 
 
 def strerror(status: int) -> str:

@@ -392,12 +392,9 @@ int grow_sets(fdbcs_conflict_set* cs, DBuf* key, DBuf* lt, DBuf* ver, int live, 
             HIPOK(hipMemcpyAsync(nv.p, ver[k].p, 8 * n, hipMemcpyDeviceToDevice, cs->stream));
         }
         HIPOK(hipStreamSynchronize(cs->stream));
-        key[k].release();
-        lt[k].release();
-        ver[k].release();
-        key[k] = nk;
-        lt[k] = nl;
-        ver[k] = nv;
+        key[k] = std::move(nk);
+        lt[k] = std::move(nl);
+        ver[k] = std::move(nv);
     }
     return FDBCS_OK;
 }
@@ -458,61 +455,12 @@ int ensure_history(fdbcs_conflict_set* cs, int64_t need, int64_t tail_need) {
         if (tail_used)
             HIPOK(hipMemcpyAsync(nt.p, cs->htail[cs->tcur].p, tail_used, hipMemcpyDeviceToDevice, cs->stream));
         HIPOK(hipStreamSynchronize(cs->stream));
-        cs->htail[cs->tcur].release();
-        cs->htail[cs->tcur ^ 1].release();
-        cs->htail[cs->tcur] = nt;
-        cs->htail[cs->tcur ^ 1] = spare;
+        cs->htail[cs->tcur] = std::move(nt);
+        cs->htail[cs->tcur ^ 1] = std::move(spare);
         cs->tail_cap = tcap;
     }
     HIPOK(hipStreamSynchronize(cs->stream));
     return ensure_scan_arena(cs);
-}
-
-int ensure_events(fdbcs_batch* b) {
-    BatchSlot* sl = b->slot;
-    if (sl->events_made) return FDBCS_OK;
-    for (int i = 0; i < kPhCount; i++) HIPOK(hipEventCreate(&sl->ev[i]));
-    sl->events_made = true;
-    return FDBCS_OK;
-}
-
-void release_slot(BatchSlot* sl) {
-    if (!sl) return;
-    if (sl->events_made)
-        for (int i = 0; i < kPhCount; i++) (void)hipEventDestroy(sl->ev[i]);
-    if (sl->ev_up) (void)hipEventDestroy(sl->ev_up);
-    if (sl->ev_rt0) (void)hipEventDestroy(sl->ev_rt0);
-    if (sl->ev_rt1) (void)hipEventDestroy(sl->ev_rt1);
-    if (sl->ev_is0) (void)hipEventDestroy(sl->ev_is0);
-    if (sl->ev_is1) (void)hipEventDestroy(sl->ev_is1);
-    if (sl->ev_da0) (void)hipEventDestroy(sl->ev_da0);
-    if (sl->ev_da1) (void)hipEventDestroy(sl->ev_da1);
-    sl->da_scan.release();
-    sl->sp_toff.release();
-    sl->da_dres.release();
-    sl->da_res.release();
-    sl->is_state.release();
-    sl->is_met.release();
-    sl->is_idx.release();
-    sl->is_off.release();
-    sl->is_bytes.release();
-    sl->is_tot.release();
-    sl->rt_scan.release();
-    sl->rt_inv.release();
-    sl->rt_rids.release();
-    sl->rt_gids.release();
-    sl->rt_map.release();
-    sl->rt_map_pin.release();
-    sl->rt_dres.release();
-    sl->rt_info.release();
-    sl->rt_txpre.release();
-    sl->rt_res.release();
-    for (hipEvent_t e : sl->prof_pool) (void)hipEventDestroy(e);
-    sl->dev.release();
-    sl->dverdict.release();
-    sl->pin_in.release();
-    sl->pin_out.release();
-    delete sl;
 }
 
 // Layout of a batch in pin_in / dev (UploadLayout, engine_impl.h).
@@ -586,11 +534,11 @@ int ensure_slot(BatchSlot* sl, size_t upload_bytes, size_t T, size_t R) {
 }
 
 int make_slot_events(BatchSlot* sl) {
-    if (!sl->events_made) {
-        for (int i = 0; i < kPhCount; i++) HIPOK(hipEventCreate(&sl->ev[i]));
-        sl->events_made = true;
-    }
-    if (!sl->ev_up) HIPOK(hipEventCreateWithFlags(&sl->ev_up, hipEventDisableTiming));
+    if (sl->events_made) return FDBCS_OK;
+    for (Event& e : sl->ev)
+        if (int rc = e.make()) return rc;
+    if (int rc = sl->ev_up.make(hipEventDisableTiming)) return rc;
+    sl->events_made = true;
     return FDBCS_OK;
 }
 
@@ -627,8 +575,7 @@ inline bool stage_b_done(fdbcs_conflict_set* cs, int k) {
 // H2D of the packed batch by the DMA engine, issued now on `us` (the upload stream, or stage A's
 // stream when the phases are timed one after another); ev_up marks its completion.
 int do_upload(fdbcs_batch* b, hipStream_t us) {
-    fdbcs_conflict_set* cs = b->cs;
-    BatchSlot* sl = b->slot;
+    BatchSlot* sl = b->slot.get();
     const size_t T = b->T(), R = b->R(), W = b->W();
     const UploadLayout L = upload_layout(T, R, W, b->tail_size());
     int rc;
@@ -646,10 +593,8 @@ int do_upload(fdbcs_batch* b, hipStream_t us) {
     memcpy(h + L.roff, b->roff.data(), 4 * (T + 1));
     memcpy(h + L.woff, b->woff.data(), 4 * (T + 1));
     if (T) memcpy(h + L.flags, b->flags.data(), T);
-    // Both stages wait for ev_up.  A reused slot's device copy may still be read by the epilogue
-    // of the batch that used it last.
-    if (!sl->ev_up) HIPOK(hipEventCreateWithFlags(&sl->ev_up, hipEventDisableTiming));
-    (void)cs;
+    // Both stages wait for ev_up (made with the slot).  A reused slot's device copy may still be read
+    // by the epilogue of the batch that used it last.
     HIPOK(hipMemcpyAsync(sl->dev.p, h, L.total, hipMemcpyHostToDevice, us));
     HIPOK(hipEventRecord(sl->ev_up, us));
     char* d = (char*)sl->dev.p;
@@ -769,12 +714,6 @@ int flush_pending(fdbcs_conflict_set* cs) {
     return rc;
 }
 
-double ev_ms(hipEvent_t a, hipEvent_t b) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, a, b) != hipSuccess) return 0.0;
-    return (double)ms;
-}
-
 }  // namespace fdbcs::impl
 
 extern "C" {
@@ -829,15 +768,12 @@ int fdbcs_new_conflict_set(int device, fdbcs_conflict_set** out) {
     // Five streams at the default priority, every CU: stream priorities and CU partitions between
     // the chains measured slower (extra hardware queues; the chains slow each other
     // through the memory system, not by competing for CU slots).
-    auto mk = [](hipStream_t* st) { return hipStreamCreateWithFlags(st, hipStreamNonBlocking) == hipSuccess; };
-    bool ok = mk(&cs->stream) && mk(&cs->ystream) && mk(&cs->astream) && mk(&cs->ustream) && mk(&cs->cstream) &&
-              hipEventCreateWithFlags(&cs->ev_cmp, hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&cs->ev_quant, hipEventDisableTiming) == hipSuccess;
-    for (int k = 0; k < kNumWork && ok; k++)
-        ok = hipEventCreateWithFlags(&cs->ev_a[k], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&cs->ev_c[k], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&cs->ev_b[k], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&cs->ev_res[k], hipEventDisableTiming) == hipSuccess;
+    bool ok = true;
+    for (Stream* st : {&cs->stream, &cs->ystream, &cs->astream, &cs->ustream, &cs->cstream}) ok = ok && !st->make();
+    for (Event* e : {&cs->ev_cmp, &cs->ev_quant}) ok = ok && !e->make(hipEventDisableTiming);
+    for (int k = 0; k < kNumWork; k++)
+        for (Event* e : {&cs->ev_a[k], &cs->ev_c[k], &cs->ev_b[k], &cs->ev_res[k]})
+            ok = ok && !e->make(hipEventDisableTiming);
     if (!ok) {
         fdbcs_destroy_conflict_set(cs);
         return FDBCS_E_DEVICE;
@@ -891,73 +827,12 @@ void fdbcs_destroy_conflict_set(fdbcs_conflict_set* cs) {
                 cs->add_threads, (long long)cs->add_prof_n, cs->add_prof[0] / cs->add_prof_n,
                 cs->add_prof[1] / cs->add_prof_n, cs->add_prof[2] / cs->add_prof_n, cs->add_prof[3] / cs->add_prof_n);
     delete cs->add_pool;
-    cs->add_pool = nullptr;
-    if (cs->ustream) (void)hipStreamSynchronize(cs->ustream);
-    if (cs->cstream) (void)hipStreamSynchronize(cs->cstream);
-    if (cs->astream) (void)hipStreamSynchronize(cs->astream);
-    if (cs->stream) (void)hipStreamSynchronize(cs->stream);
-    if (cs->ystream) (void)hipStreamSynchronize(cs->ystream);
-    for (int k = 0; k < 2; k++) {
-        cs->hkey[k].release();
-        cs->hlt[k].release();
-        cs->hver[k].release();
-        cs->dkey[k].release();
-        cs->dlt[k].release();
-        cs->dver[k].release();
-    }
-    cs->htail[0].release();
-    cs->htail[1].release();
-    for (auto& l : cs->lvl) l.release();
-    cs->dir.release();
-    for (auto& e : cs->edir) e.release();
-    for (auto& set : cs->dlvl)
-        for (auto& l : set) l.release();
-    for (auto& x : cs->cws) x.release();
-    for (auto& set : cs->ws)
-        for (auto& x : set) x.release();
-    for (auto& x : cs->wbtail) x.release();
-    cs->scal.release();
-    cs->quant.release();
-    cs->trace_buf.release();
-    cs->hold.release();
-    cs->hedge.release();
-    for (DBuf* x : {&cs->x_pos, &cs->x_val, &cs->x_btail, &cs->x_state, &cs->x_ver, &cs->x_off, &cs->x_bytes})
-        x->release();
-    if (cs->x_ev0) (void)hipEventDestroy(cs->x_ev0);
-    if (cs->x_ev1) (void)hipEventDestroy(cs->x_ev1);
-    cs->g_state.release();
-    for (hipEvent_t e : cs->g_ev)
-        if (e) (void)hipEventDestroy(e);
-    cs->rv_out.release();
-    cs->rv_err.release();
-    for (hipEvent_t e : cs->rv_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (DBuf* x : {&cs->i_bytes, &cs->i_off, &cs->i_ver, &cs->i_bnd, &cs->i_okey, &cs->i_olt, &cs->i_over, &cs->i_otail,
-                    &cs->i_mval, &cs->i_mkey, &cs->i_mlt, &cs->i_dblt, &cs->i_vblt, &cs->i_state,
-                    &cs->i_gran, &cs->i_dstate})
-        x->release();
-    for (hipEvent_t e : cs->i_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (BatchSlot* sl : cs->pool) release_slot(sl);
-    cs->pool.clear();
+    for (const Stream* st : {&cs->ustream, &cs->cstream, &cs->astream, &cs->stream, &cs->ystream})
+        if (*st) (void)hipStreamSynchronize(*st);
     // batches that outlive their set (e.g. garbage-collection order in a binding) keep their own
     // slot and refuse every further call
     for (fdbcs_batch* b : cs->live) b->cs = nullptr;
-    cs->live.clear();
-    for (int k = 0; k < kNumWork; k++) {
-        if (cs->ev_a[k]) (void)hipEventDestroy(cs->ev_a[k]);
-        if (cs->ev_c[k]) (void)hipEventDestroy(cs->ev_c[k]);
-        if (cs->ev_b[k]) (void)hipEventDestroy(cs->ev_b[k]);
-        if (cs->ev_res[k]) (void)hipEventDestroy(cs->ev_res[k]);
-    }
-    if (cs->ustream) (void)hipStreamDestroy(cs->ustream);
-    if (cs->cstream) (void)hipStreamDestroy(cs->cstream);
-    if (cs->ev_cmp) (void)hipEventDestroy(cs->ev_cmp);
-    if (cs->ev_quant) (void)hipEventDestroy(cs->ev_quant);
-    if (cs->astream) (void)hipStreamDestroy(cs->astream);
-    if (cs->stream) (void)hipStreamDestroy(cs->stream);
-    if (cs->ystream) (void)hipStreamDestroy(cs->ystream);
-    delete cs;
+    delete cs;  // every buffer and event, the pooled slots, and last the streams (engine_impl.h)
 }
 
 int fdbcs_clear_conflict_set(fdbcs_conflict_set* cs, int64_t version) {
@@ -1153,7 +1028,8 @@ int fdbcs_debug_hold(fdbcs_conflict_set* cs, int32_t on) {
     if (int rc = sync_all(cs)) return rc;
     *word = 0;
     std::atomic_thread_fence(std::memory_order_seq_cst);
-    for (hipStream_t st : {cs->ustream, cs->astream, cs->cstream, cs->stream}) launch_hold(st, (const uint32_t*)cs->hold.dp);
+    for (const Stream* st : {&cs->ustream, &cs->astream, &cs->cstream, &cs->stream})
+        launch_hold(*st, (const uint32_t*)cs->hold.dp);
     HIPOK(take_launch_error());
     return FDBCS_OK;
 }
@@ -1176,16 +1052,12 @@ int fdbcs_batch_new(fdbcs_conflict_set* cs, int report_keys, fdbcs_batch** out) 
     if (!b) return FDBCS_E_NOMEM;
     b->cs = cs;
     if (!cs->pool.empty()) {
-        b->slot = cs->pool.back();
+        b->slot = std::move(cs->pool.back());
         cs->pool.pop_back();
     } else {
-        b->slot = new (std::nothrow) BatchSlot();
-        if (!b->slot) {
-            delete b;
-            return FDBCS_E_NOMEM;
-        }
-        if (int rc = make_slot_events(b->slot)) {
-            release_slot(b->slot);
+        b->slot.reset(new (std::nothrow) BatchSlot());
+        const int rc = b->slot ? make_slot_events(b->slot.get()) : FDBCS_E_NOMEM;
+        if (rc) {
             delete b;
             return rc;
         }
@@ -1198,19 +1070,15 @@ int fdbcs_batch_new(fdbcs_conflict_set* cs, int report_keys, fdbcs_batch** out) 
 
 void fdbcs_batch_destroy(fdbcs_batch* b) {
     if (!b) return;
-    if (!b->cs) {  // its set was destroyed first (and synchronized its streams)
-        release_slot(b->slot);
+    if (!b->cs) {  // its set was destroyed first (and synchronized its streams): the slot dies with it
         delete b;
         return;
     }
     if (b->state == 2) {  // still in flight: its set (which must outlive it) owns the stream
         (void)hipSetDevice(b->cs->device);
         (void)flush_pending(b->cs);
-        (void)hipStreamSynchronize(b->cs->ustream);
-        (void)hipStreamSynchronize(b->cs->cstream);
-        (void)hipStreamSynchronize(b->cs->astream);
-        (void)hipStreamSynchronize(b->cs->stream);
-        (void)hipStreamSynchronize(b->cs->ystream);
+        for (const Stream* st : {&b->cs->ustream, &b->cs->cstream, &b->cs->astream, &b->cs->stream, &b->cs->ystream})
+            (void)hipStreamSynchronize(*st);
         b->cs->inflight--;
     } else if (b->state == 1) {  // uploaded, never submitted: the copy may still be in flight
         (void)hipSetDevice(b->cs->device);
@@ -1225,7 +1093,7 @@ void fdbcs_batch_destroy(fdbcs_batch* b) {
     // sample's own buffers are the next batch's only once it is over
     if (b->slot && b->slot->is_inflight) {
         (void)hipSetDevice(b->cs->device);
-        (void)hipEventSynchronize(b->slot->ev_is1);
+        (void)hipEventSynchronize(b->slot->is_span.e1);
         b->slot->is_inflight = false;
     }
     // done (waited or synchronized): dependencies on it need no wait any more
@@ -1234,7 +1102,7 @@ void fdbcs_batch_destroy(fdbcs_batch* b) {
         if (b->cs->xfree_user[k] == b) b->cs->xfree_user[k] = nullptr;
     }
     // the slot goes back to the set's pool (its buffers and events are reused by the next batch)
-    if (b->slot) b->cs->pool.push_back(b->slot);
+    if (b->slot) b->cs->pool.push_back(std::move(b->slot));
     b->cs->live.erase(b);
     delete b;
 }
@@ -1346,7 +1214,7 @@ static int add_packed_direct(fdbcs_batch* b, const fdbcs_packed_batch* pb) {
     };
     const auto tp1 = clk::now();
     if (int rc = b->slot->pin_in.ensure(L.total, true)) return fail(rc);
-    if (int rc = ensure_slot(b->slot, L.total, T, Ra)) return fail(rc);
+    if (int rc = ensure_slot(b->slot.get(), L.total, T, Ra)) return fail(rc);
     const auto tp2 = clk::now();
     char* h = (char*)b->slot->pin_in.p;
     DKey* keys = (DKey*)(h + L.keys);
@@ -1780,7 +1648,7 @@ static int add_routed_impl(fdbcs_batch* b, const void* shares, int64_t stride, i
     if (lo_len >= 0 && hi_len >= 0 && cmp_bytes(lo_key, lo_len, hi_key, hi_len) >= 0) return FDBCS_E_INVALID;
     fdbcs_conflict_set* cs = b->cs;
     HIPOK(hipSetDevice(cs->device));
-    BatchSlot* sl = b->slot;
+    BatchSlot* sl = b->slot.get();
     int rc;
     RouteArgs a{};
     size_t map_bytes = 0;
@@ -1845,8 +1713,6 @@ static int add_routed_impl(fdbcs_batch* b, const void* shares, int64_t stride, i
     if ((rc = sl->rt_dres.ensure(sizeof(RouteResult)))) return rc;
     if ((rc = sl->rt_res.ensure(sizeof(RouteResult), true))) return rc;
     if ((rc = make_slot_events(sl))) return rc;
-    if (!sl->ev_rt0) HIPOK(hipEventCreate(&sl->ev_rt0));
-    if (!sl->ev_rt1) HIPOK(hipEventCreate(&sl->ev_rt1));
     const auto t_host = std::chrono::steady_clock::now();
     char* d = (char*)sl->dev.p;
     a.shares = (const uint8_t*)shares;
@@ -1898,10 +1764,10 @@ static int add_routed_impl(fdbcs_batch* b, const void* shares, int64_t stride, i
     uint64_t* sw = (uint64_t*)sl->rt_scan.p;
     ScanState st{sw + 8, (int*)sw, (int*)(sw + 1)};
     t_record = nullptr;
-    HIPOK(hipEventRecord(sl->ev_rt0, us));
+    if ((rc = sl->rt_span.begin(us))) return rc;
     launch_route(us, a, st);
     HIPOK(take_launch_error());
-    HIPOK(hipEventRecord(sl->ev_rt1, us));
+    if ((rc = sl->rt_span.end(us))) return rc;
     sl->rt_timed = true;
     HIPOK(hipEventRecord(sl->ev_up, us));
     cs->stats.host_ms_route += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host).count();
@@ -1950,7 +1816,7 @@ int fdbcs_batch_add_routed_map(fdbcs_batch* b, const void* shares, int64_t strid
 extern "C++" int fdbcs::impl::finish_route(fdbcs_batch* b) {
     if (!b->route_pending) return FDBCS_OK;
     if (b->dev_added) return finish_device_add(b);
-    BatchSlot* sl = b->slot;
+    BatchSlot* sl = b->slot.get();
     HIPOK(hipEventSynchronize(sl->ev_up));
     std::atomic_thread_fence(std::memory_order_acquire);
     RouteResult r;
@@ -2058,7 +1924,7 @@ struct DetectPlan {
     MaxLevels merge_dlv;
 
     DetectPlan(fdbcs_conflict_set* cs_, fdbcs_batch* b_, int64_t now_, int64_t oldest_)
-        : cs(cs_), b(b_), now(now_), oldest_arg(oldest_), sl(b_->slot), wp(cs_->wpar), w(cs_->work[cs_->wpar]) {}
+        : cs(cs_), b(b_), now(now_), oldest_arg(oldest_), sl(b_->slot.get()), wp(cs_->wpar), w(cs_->work[cs_->wpar]) {}
 
     // phase events: level 2 records every phase, level 1 only the hot kernels (roofline)
     // level 3 (per-kernel profile) records only the events around every kernel
@@ -2110,7 +1976,7 @@ static int detect_admit(fdbcs_conflict_set* cs, fdbcs_batch* b, DetectPlan& p) {
     if ((rc = ensure_delta(cs, cs->nd_ub + 2 * p.W + 1))) return rc;
     if ((rc = ensure_history(cs, cs->n_ub + cs->nd_ub + 2 * p.W + 1, cs->tail_ub + p.tail_add + 1)))
         return rc;
-    if ((rc = ensure_events(b))) return rc;
+    if ((rc = make_slot_events(b->slot.get()))) return rc;
     if (cs->ddir_counter == UINT32_MAX && cs->edir[0].p) {
         // the delta directory's 32-bit epoch tag is about to wrap: clear every entry (once per 2^32
         // batches) so that no entry left by an old fill can carry the reused epoch value
@@ -2712,7 +2578,7 @@ static int account_stats(fdbcs_conflict_set* cs, fdbcs_batch* b) {
         }
     for (const auto& sp : b->slot->prof_spans) {  // per-kernel events (levels 3 and 1)
         HIPOK(hipEventSynchronize(sp.second.second));
-        const double ms = ev_ms(sp.second.first, sp.second.second);
+        const double ms = Span::between(sp.second.first, sp.second.second);
         auto it = std::find_if(cs->kprof.begin(), cs->kprof.end(), [&](const auto& k) { return k.func == sp.first; });
         if (it == cs->kprof.end()) {
             cs->kprof.push_back({sp.first, 0, 0.0});
@@ -2721,9 +2587,10 @@ static int account_stats(fdbcs_conflict_set* cs, fdbcs_batch* b) {
         it->launches += 1;
         it->ms += ms;
     }
+    if (!b->slot->prof_spans.empty()) b->slot->prof_pool.count();
     b->slot->prof_spans.clear();
     auto ph = [&](int a, int z) {
-        return ((b->recorded >> a) & (b->recorded >> z) & 1u) ? ev_ms(b->slot->ev[a], b->slot->ev[z]) : 0.0;
+        return ((b->recorded >> a) & (b->recorded >> z) & 1u) ? Span::between(b->slot->ev[a], b->slot->ev[z]) : 0.0;
     };
     st.ms_upload += ph(kPhStart, kPhUpload);
     st.ms_sort += ph(kPhUpload, kPhSort);
@@ -2773,8 +2640,7 @@ static int account_stats(fdbcs_conflict_set* cs, fdbcs_batch* b) {
     st.gc_runs += b->gc_ran ? 1 : 0;
     st.sort_big_buckets += b->h_scal->sort_big;
     if (b->routed && !b->dev_added && b->slot->rt_timed) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, b->slot->ev_rt0, b->slot->ev_rt1) == hipSuccess) st.ms_route_kernels += ms;
+        st.ms_route_kernels += b->slot->rt_span.ms();
         st.routed_batches += 1;
         b->slot->rt_timed = false;
     }
@@ -2929,9 +2795,7 @@ int fdbcs_debug_kernel_time(fdbcs_batch* b, int which, int reps, double* us_per_
                               b->max_len > (int32_t)kSortNxLen, which, reps, us_per_launch));
         return FDBCS_OK;
     }
-    hipEvent_t e0, e1;
-    HIPOK(hipEventCreate(&e0));
-    HIPOK(hipEventCreate(&e1));
+    Span span;
     const bool dlong = b->max_len > 24;
     // 0: the whole check; 3 / 4: the split check's base / delta tier launch alone
     auto one = [&]() {
@@ -2942,17 +2806,24 @@ int fdbcs_debug_kernel_time(fdbcs_batch* b, int which, int reps, double* us_per_
             launch_check_tier(cs->stream, b->bd, w, which == 3 ? base : delta, which == 3, ht, dlong, PrevSegs{});
     };
     one();
-    HIPOK(hipEventRecord(e0, cs->stream));
+    if (int rc = span.begin(cs->stream)) return rc;
     for (int i = 0; i < reps; i++) one();
-    HIPOK(hipEventRecord(e1, cs->stream));
-    HIPOK(hipEventSynchronize(e1));
-    *us_per_launch = ev_ms(e0, e1) * 1000.0 / reps;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    if (int rc = span.end(cs->stream)) return rc;
+    HIPOK(hipEventSynchronize(span.e1));
+    *us_per_launch = span.ms() * 1000.0 / reps;
     // the check leaves per-transaction conflict flags the next batch on this workspace expects zeroed
     HIPOK(hipMemsetAsync(w.hist_conf, 0, w.cap_T, cs->stream));
     HIPOK(hipMemsetAsync(w.rconf, 0, w.cap_R, cs->stream));
     HIPOK(hipStreamSynchronize(cs->stream));
+    return FDBCS_OK;
+}
+
+int fdbcs_debug_live_resources(int64_t* device_buffers, int64_t* host_buffers, int64_t* events, int64_t* streams) {
+    if (!device_buffers || !host_buffers || !events || !streams) return FDBCS_E_INVALID;
+    *device_buffers = live_device_buffers.load();
+    *host_buffers = live_host_buffers.load();
+    *events = live_events.load();
+    *streams = live_streams.load();
     return FDBCS_OK;
 }
 

@@ -1,8 +1,8 @@
 // engine_impl.h — the host engine's state, shared by engine.cpp (the detect pipeline and the C-ABI's
 // lifecycle calls), transfer.cpp (history export and import, the iops sample) and ingest.cpp (whole
-// batches added from device memory): the buffer types,
-// the definitions of the conflict set, the batch and its staging slot, and the helpers of engine.cpp
-// that the maintenance entry points call.  Internal: nothing outside csrc/ includes it.
+// batches added from device memory): the owner types of its buffers, events and streams and their
+// live counts, the definitions of the conflict set, the batch and its staging slot, and the helpers of
+// engine.cpp that the maintenance entry points call.  Internal: nothing outside csrc/ includes it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -18,11 +18,14 @@
 #include <chrono>
 #include <condition_variable>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <unordered_set>
+#include <utility>
 #include <vector>
 
 #include "../../include/fdb_conflict_set.h"
@@ -50,23 +53,49 @@ constexpr int64_t kTailSlack = 64;  // bytes past a tail arena's capacity (dkey.
 constexpr int64_t kTailLimit = (int64_t)8 << 32;
 constexpr int64_t kTailReclaimDefault = kTailLimit / 2;  // force the GC repack past half of that
 
+// Owners of the engine's device resources.  Each frees what it holds when it dies and can be moved
+// but not copied, so a buffer, event or stream that is a member of the set or of a slot needs no
+// line anywhere else.  The live_* counts (fdbcs_debug_live_resources) go up where the runtime
+// handed a resource out and down where it took one back, nowhere else.
+inline std::atomic<int64_t> live_device_buffers{0}, live_host_buffers{0}, live_events{0}, live_streams{0};
+
 // Grow-only device allocation.
 struct DBuf {
     void* p = nullptr;
     size_t cap = 0;
+    DBuf() = default;
+    DBuf(const DBuf&) = delete;
+    DBuf& operator=(const DBuf&) = delete;
+    DBuf(DBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+    DBuf& operator=(DBuf&& o) noexcept {
+        if (this != &o) {
+            release();
+            p = std::exchange(o.p, nullptr);
+            cap = std::exchange(o.cap, 0);
+        }
+        return *this;
+    }
+    ~DBuf() { release(); }
     int ensure(size_t bytes) {
         if (bytes <= cap) return FDBCS_OK;
         size_t want = std::max(bytes, cap + cap / 2);
         want = align_up(want < 256 ? 256 : want, 256);
-        if (p) HIPOK(hipFree(p));
+        if (p) {
+            HIPOK(hipFree(p));
+            live_device_buffers--;
+        }
         p = nullptr;
         cap = 0;
         HIPOK(hipMalloc(&p, want));
+        live_device_buffers++;
         cap = want;
         return FDBCS_OK;
     }
     void release() {
-        if (p) (void)hipFree(p);
+        if (p) {
+            (void)hipFree(p);
+            live_device_buffers--;
+        }
         p = nullptr;
         cap = 0;
     }
@@ -77,25 +106,132 @@ struct HBuf {
     void* p = nullptr;
     void* dp = nullptr;  // device view (mapped buffers)
     size_t cap = 0;
+    HBuf() = default;
+    HBuf(const HBuf&) = delete;
+    HBuf& operator=(const HBuf&) = delete;
+    HBuf(HBuf&& o) noexcept
+        : p(std::exchange(o.p, nullptr)), dp(std::exchange(o.dp, nullptr)), cap(std::exchange(o.cap, 0)) {}
+    HBuf& operator=(HBuf&& o) noexcept {
+        if (this != &o) {
+            release();
+            p = std::exchange(o.p, nullptr);
+            dp = std::exchange(o.dp, nullptr);
+            cap = std::exchange(o.cap, 0);
+        }
+        return *this;
+    }
+    ~HBuf() { release(); }
     int ensure(size_t bytes, bool mapped = false, bool noncoherent = false) {
         if (bytes <= cap) return FDBCS_OK;
         size_t want = align_up(std::max(bytes, cap + cap / 2), 4096);
-        if (p) HIPOK(hipHostFree(p));
+        if (p) {
+            HIPOK(hipHostFree(p));
+            live_host_buffers--;
+        }
         p = dp = nullptr;
         cap = 0;
         const unsigned fl = !mapped ? hipHostMallocDefault
                                     : (hipHostMallocMapped | (noncoherent ? hipHostMallocNonCoherent : hipHostMallocCoherent));
         HIPOK(hipHostMalloc(&p, want, fl));
+        live_host_buffers++;
         if (mapped) HIPOK(hipHostGetDevicePointer(&dp, p, 0));
         cap = want;
         return FDBCS_OK;
     }
     void release() {
-        if (p) (void)hipHostFree(p);
+        if (p) {
+            (void)hipHostFree(p);
+            live_host_buffers--;
+        }
         p = dp = nullptr;
         cap = 0;
     }
 };
+
+// A move-only holder of one runtime handle, destroyed with it.
+template <typename H, hipError_t (*Destroy)(H), std::atomic<int64_t>& Live>
+struct Handle {
+    H h = nullptr;
+    Handle() = default;
+    Handle(Handle&& o) noexcept : h(std::exchange(o.h, nullptr)) {}
+    Handle& operator=(Handle&& o) noexcept {
+        reset(std::exchange(o.h, nullptr));
+        return *this;
+    }
+    ~Handle() { reset(); }
+    void reset(H next = nullptr) {
+        if (h) {
+            (void)Destroy(h);
+            Live--;
+        }
+        h = next;
+    }
+    operator H() const { return h; }
+};
+
+// One event, created by the first make().
+struct Event : Handle<hipEvent_t, hipEventDestroy, live_events> {
+    int make(unsigned flags = hipEventDefault) {
+        if (h) return FDBCS_OK;
+        HIPOK(hipEventCreateWithFlags(&h, flags));
+        live_events++;
+        return FDBCS_OK;
+    }
+};
+
+// One non-blocking stream, created by the first make().
+struct Stream : Handle<hipStream_t, hipStreamDestroy, live_streams> {
+    int make() {
+        if (h) return FDBCS_OK;
+        HIPOK(hipStreamCreateWithFlags(&h, hipStreamNonBlocking));
+        live_streams++;
+        return FDBCS_OK;
+    }
+};
+
+// Two timing events around a group of launches: begin(s), the launches, end(s), and once the
+// second event has completed, ms().
+struct Span {
+    Event e0, e1;
+    int begin(hipStream_t s) {
+        if (int rc = e0.make()) return rc;
+        if (int rc = e1.make()) return rc;
+        HIPOK(hipEventRecord(e0, s));
+        return FDBCS_OK;
+    }
+    int end(hipStream_t s) {
+        HIPOK(hipEventRecord(e1, s));
+        return FDBCS_OK;
+    }
+    // Milliseconds between two completed events (0 when either was never recorded).
+    static double between(hipEvent_t a, hipEvent_t b) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, a, b) != hipSuccess) return 0.0;
+        return (double)ms;
+    }
+    double ms() const { return between(e0, e1); }
+};
+
+// The per-kernel events of a slot.  LaunchList::Profile (launch.h) points into `v` and creates the
+// events it hands out, so they are counted here, by count() once a profiled batch is done.
+struct EventPool {
+    std::vector<hipEvent_t> v;
+    size_t counted = 0;
+    EventPool() = default;
+    EventPool(EventPool&& o) noexcept : v(std::move(o.v)), counted(std::exchange(o.counted, 0)) {}
+    void count() {
+        live_events += (int64_t)(v.size() - counted);
+        counted = v.size();
+    }
+    ~EventPool() {
+        for (hipEvent_t e : v) (void)hipEventDestroy(e);
+        live_events -= (int64_t)counted;
+    }
+};
+
+template <typename... T>
+constexpr bool move_only_v = ((!std::is_copy_constructible_v<T> && std::is_nothrow_move_constructible_v<T>) && ...);
+static_assert(move_only_v<DBuf, HBuf, Event, Stream, Span, EventPool>);
 
 enum Phase {
     kPhStart, kPhUpload, kPhSort, kPhEdges, kPhCheck, kPhIntra, kPhCombine, kPhCopyBegin, kPhCopyEnd, kPhMerge,
@@ -221,14 +357,26 @@ struct AddPool {
     }
 };
 
+// Ownership: every buffer, event and stream below is an owner type (DBuf, HBuf, Event, Span, Stream),
+// so `delete cs` releases them all and a new one needs its member and nothing else.  Members die in
+// reverse declaration order: the five streams are declared before every buffer and event, so they
+// go last (no event outlives the stream it was recorded on for the runtime to chase), in the order
+// ustream, cstream, astream, stream, ystream.  fdbcs_destroy_conflict_set has synchronized them.
 struct fdbcs_conflict_set {
     int device = 0;
-    hipStream_t stream = nullptr;   // stage B: everything that reads or writes the history, in batch order
-    hipStream_t astream = nullptr;  // stage A (and every upload): history-independent sort and edges
-    hipStream_t cstream = nullptr;  // split read check: the base-tier half (history-independent between
-                                    // compactions) beside stage A
-    hipEvent_t ev_c[kNumWork] = {}; // base-tier check of the batch using workspace k is done
-    hipEvent_t ev_cmp = nullptr;    // stage B of the last batch that rewrote the base (compaction / GC)
+    // Stage B in two halves on two streams: X (`stream`: read check, resolution, D.Combine) and Y
+    // (`ystream`: merge into the delta, compaction / GC, epilogue).  The check of batch i + 1 runs
+    // against the delta before batch i's merge plus batch i's union segments (PrevSegs), so it does
+    // not wait for that merge: Y(i) overlaps X(i + 1).
+    Stream ystream;
+    Stream stream;   // stage B: everything that reads or writes the history, in batch order
+    Stream astream;  // stage A (and every upload): history-independent sort and edges
+    Stream cstream;  // split read check: the base-tier half (history-independent between
+                     // compactions) beside stage A
+    Stream ustream;  // batch uploads (k_upload over PCIe), so batch i+1's upload overlaps
+                     // batch i's stage A; stage A waits for the upload's event
+    Event ev_c[kNumWork];  // base-tier check of the batch using workspace k is done
+    Event ev_cmp;          // stage B of the last batch that rewrote the base (compaction / GC)
     bool cmp_recorded = false;
     // FDBCS_SPLIT_CHECK: 0 = one read check over both tiers in stage B, 1 = the base-tier half on
     // its own stream beside stage A, 2 (default) = split only over a large base tier (>= 16M
@@ -236,18 +384,12 @@ struct fdbcs_conflict_set {
     // chain; over a 5M base (C2) the single launch measured faster (device-resident 34.0M vs
     // 32.1M txns/s: one launch and two cross-stream events fewer, no third stream competing)
     int split_check = 2;
-    hipStream_t ustream = nullptr;  // batch uploads (k_upload over PCIe), so batch i+1's upload overlaps
-                                    // batch i's stage A; stage A waits for the upload's event
-    hipEvent_t ev_a[kNumWork] = {}; // stage A of the batch using workspace k is done
-    hipEvent_t ev_b[kNumWork] = {}; // stage B (epilogue) of the batch using workspace k is done
-    // Stage B in two halves on two streams: X (`stream`: read check, resolution, D.Combine) and Y
-    // (`ystream`: merge into the delta, compaction / GC, epilogue).  The check of batch i + 1 runs
-    // against the delta before batch i's merge plus batch i's union segments (PrevSegs), so it does
-    // not wait for that merge: Y(i) overlaps X(i + 1).
-    hipStream_t ystream = nullptr;
-    hipEvent_t ev_res[kNumWork] = {};   // X of the batch using workspace k is done (Y waits for it)
+    Event ev_a[kNumWork];    // stage A of the batch using workspace k is done
+    Event ev_b[kNumWork];    // stage B (epilogue) of the batch using workspace k is done
+    Event ev_res[kNumWork];  // X of the batch using workspace k is done (Y waits for it)
     // the next batch's check is done with workspace k's segments: that batch's ev_res (the end of
-    // its half X, recorded anyway, and not re-recorded before workspace k's next user records)
+    // its half X, recorded anyway, and not re-recorded before workspace k's next user records);
+    // an alias of ev_res[], which owns the event
     hipEvent_t xfree_ev[kNumWork] = {};
     bool prev_segs = false;             // the last batch's segments are not merged when the next check runs
     int prev_wp = 0;
@@ -320,7 +462,7 @@ struct fdbcs_conflict_set {
     // the stream of the last stage A (its sort read one splitter table and wrote the other): a batch
     // whose stage A runs on another stream (a timing-level change) waits for ev_quant recorded there
     hipStream_t quant_sa = nullptr;
-    hipEvent_t ev_quant = nullptr;
+    Event ev_quant;
     int64_t sort_big_buckets = 0;  // buckets past kSlab so far (host view, from the published scalars)
     bool trace = false;     // FDBCS_TRACE=1: device timestamps of kernel sections printed per batch
     bool serial = false;    // FDBCS_SERIAL=1: both stages on one stream (no cross-batch overlap)
@@ -357,7 +499,7 @@ struct fdbcs_conflict_set {
     HBuf hedge;                        // per workspace {batch seq, any candidate edge} (Work::hedge)
     bool skip_edges = true;            // FDBCS_SKIP_EDGES=0: always issue the kGroupEdges launches
     fdbcs_stats stats{};
-    std::vector<BatchSlot*> pool;  // staging slots of destroyed batches, reused by new ones
+    std::vector<std::unique_ptr<BatchSlot>> pool;  // staging slots of destroyed batches, reused by new ones
     // Two submitting threads (the default since round 4: C2 +3-10 % over five same-box A/Bs, C3 and
     // C4 unchanged; FDBCS_SUBMIT_THREAD=0 keeps one).  A helper thread issues stage A of batch i
     // (and its base-tier check) while the calling thread issues stage B's X half of batch i-1,
@@ -405,25 +547,25 @@ struct fdbcs_conflict_set {
     DBuf x_pos, x_val, x_btail, x_state, x_ver, x_off, x_bytes;
     bool x_valid = false;
     int64_t x_n = 0, x_nbytes = 0;
-    hipEvent_t x_ev0 = nullptr, x_ev1 = nullptr;  // around the export's kernels
+    Span x_span;                                  // around the export's kernels
     double x_ms_kernels = 0, x_ms_d2h = 0;        // of the last export / read (fdbcs_history_export_timing)
     int64_t x_hdr = 0;                            // the pending result's header version
     // fdbcs_history_digest: its own words and per-tile starts (a pending export's words stay as they
     // are); x_pos, x_val and x_btail are shared with the export, which keeps no result in them
     DBuf g_state;
-    hipEvent_t g_ev[2] = {};                      // around the digest's kernels
+    Span g_span;                                  // around the digest's kernels
     double g_ms_kernels = 0, g_ms_host = 0;       // of the last digest (fdbcs_history_digest_timing)
     // fdbcs_batch_read_versions: the host form's result (grow-only; the device form writes to the
     // caller's memory) and the error word, allocated by the first query; nothing of the export's
     DBuf rv_out, rv_err;
-    hipEvent_t rv_ev[2] = {};                     // around the query's kernel
+    Span rv_span;                                 // around the query's kernel
     double rv_ms_kernels = 0, rv_ms_host = 0;     // of the last query (fdbcs_batch_read_versions_timing)
     // fdbcs_history_import: device copies of the imported arrays (host-array form), the bounds' bytes,
     // the overlay stream (keys, lt, versions, tails), the merged stream (value, key, lt) and the import
     // words; all allocated by the first import and freed with the set.
     DBuf i_bytes, i_off, i_ver, i_bnd, i_okey, i_olt, i_over, i_otail, i_mval, i_mkey, i_mlt, i_dblt, i_vblt, i_state;
     DBuf i_gran;                                  // the fold's scan granules
-    hipEvent_t i_ev[6] = {};                      // around the import's three groups of kernels
+    Span i_span[3];                               // around the import's three groups of kernels
     double i_ms_kernels = 0, i_ms_host = 0;       // of the last import (fdbcs_history_import_timing)
     // fdbcs_history_import_delta: its words + scan granules (allocated by the first delta import), and
     // what the last successful import of either kind did (fdbcs_history_import_info)
@@ -434,7 +576,7 @@ struct fdbcs_conflict_set {
 
 // Host/device staging of one batch.  Batches are short-lived (one per commit batch, as the
 // reference's ConflictBatch), so their pinned and device buffers come from a per-set pool instead
-// of fresh hipHostMalloc / hipMalloc calls.  A slot goes back to the pool only when its batch is
+// of fresh allocations.  A slot goes back to the pool only when its batch is
 // destroyed, after its completion flag was seen (the epilogue's last store) or, for a batch still
 // in flight, after its streams were synchronized: the next user's upload needs no event.
 struct BatchSlot {
@@ -442,9 +584,9 @@ struct BatchSlot {
     HBuf pin_in;
     HBuf pin_out;
     DBuf dverdict;
-    hipEvent_t ev[kPhCount] = {};
-    bool events_made = false;
-    hipEvent_t ev_up = nullptr;    // upload done (recorded on stage A's stream)
+    Event ev[kPhCount];
+    bool events_made = false;  // ev[] and ev_up exist (make_slot_events)
+    Event ev_up;               // upload done (recorded on stage A's stream)
     HBuf pin_inv;  // fdbcs_batch_set_conflict_output: global -> batch transaction map (host-mapped)
     // device routing (fdbcs_batch_add_routed): scan state, global -> batch map, read ids, totals
     DBuf rt_scan, rt_inv, rt_rids, rt_dres, rt_info, rt_txpre;
@@ -454,33 +596,33 @@ struct BatchSlot {
     DBuf rt_map;
     HBuf rt_map_pin;
     HBuf rt_res;
-    hipEvent_t ev_rt0 = nullptr, ev_rt1 = nullptr;  // around the routing kernels
+    Span rt_span;  // around the routing kernels
     bool rt_timed = false;
     // fdbcs_batch_set_iops_sample: scan state, result arrays, host-mapped totals and the events
     // around the kernel, all allocated by the slot's first sampled batch.  is_inflight: a sample
-    // was enqueued and nobody has waited for ev_is1 since (it reads the slot's device copy)
+    // was enqueued and nobody has waited for its end since (it reads the slot's device copy)
     DBuf is_state, is_met, is_idx, is_off, is_bytes;
     HBuf is_tot;
-    hipEvent_t ev_is0 = nullptr, ev_is1 = nullptr;
+    Span is_span;
     bool is_inflight = false;
     // fdbcs_batch_add_packed_device: scan state, the device and host-mapped totals and the events
     // around the add kernels, all allocated by the slot's first device-added batch
     DBuf da_scan, da_dres;
     HBuf da_res;
-    hipEvent_t ev_da0 = nullptr, ev_da1 = nullptr;
+    Span da_span;
     // fdbcs_batch_share_pack_device shares them (a batch does one or the other) and adds each key's
     // place in the share's tail region, the scan's store
     DBuf sp_toff;
     // per-kernel events of the batch (timing level 3, or the timed kernel at level 1)
-    std::vector<hipEvent_t> prof_pool;
+    EventPool prof_pool;
     size_t prof_next = 0;
     std::vector<std::pair<const void*, std::pair<hipEvent_t, hipEvent_t>>> prof_spans;
-    LaunchList::Profile prof{&prof_pool, &prof_next, &prof_spans};
+    LaunchList::Profile prof{&prof_pool.v, &prof_next, &prof_spans};
 };
 
 struct fdbcs_batch {
     fdbcs_conflict_set* cs = nullptr;
-    BatchSlot* slot = nullptr;
+    std::unique_ptr<BatchSlot> slot;  // back to the set's pool when the batch dies, or freed with it once the set is gone
     int report_enabled = 0;
     int state = 0;  // 0 adding, 1 uploaded, 2 submitted, 3 done
     // host staging (pageable); in `direct` mode (one fdbcs_batch_add_packed) the endpoint keys,
@@ -571,7 +713,6 @@ MaxLevels dlevels_of(fdbcs_conflict_set* cs, int k);
 int ensure_delta(fdbcs_conflict_set* cs, int64_t need);
 int ensure_history(fdbcs_conflict_set* cs, int64_t need, int64_t tail_need);
 int64_t delta_limit_for(const fdbcs_conflict_set* cs, int64_t n_base);  // delta size that triggers a compaction
-double ev_ms(hipEvent_t a, hipEvent_t b);
 int finish_route(fdbcs_batch* b);  // wait for a routed batch's routing and take its sizes and error
 // Its sibling for a device-added batch (ingest.cpp; finish_route hands such a batch over): wait for
 // the add kernels and take the totals; on an error the batch is empty again.

@@ -14,12 +14,12 @@
 // touched.
 int fdbcs::impl::finish_device_add(fdbcs_batch* b) {
     if (!b->route_pending) return FDBCS_OK;
-    BatchSlot* sl = b->slot;
+    BatchSlot* sl = b->slot.get();
     HIPOK(hipEventSynchronize(sl->ev_up));
     std::atomic_thread_fence(std::memory_order_acquire);
     IngestResult r;
     memcpy(&r, (const void*)sl->da_res.p, sizeof(r));
-    b->da_ms_kernels = ev_ms(sl->ev_da0, sl->ev_da1);
+    b->da_ms_kernels = sl->da_span.ms();
     if (r.error != 0) {
         // 1: the arrays break the layout or hold an inverted range; 2: the ready flag was never set;
         // 4: the scan's look-back gave up
@@ -48,14 +48,14 @@ int fdbcs::impl::finish_device_add(fdbcs_batch* b) {
 // the kernels left the empty share in the caller's buffer.
 int fdbcs::impl::finish_share_pack(fdbcs_batch* b) {
     if (!b->sp_pending) return b->sp_rc;
-    BatchSlot* sl = b->slot;
+    BatchSlot* sl = b->slot.get();
     b->sp_pending = false;
     b->sp_rc = FDBCS_E_DEVICE;
-    HIPOK(hipEventSynchronize(sl->ev_da1));
+    HIPOK(hipEventSynchronize(sl->da_span.e1));
     std::atomic_thread_fence(std::memory_order_acquire);
     ShareResult r;
     memcpy(&r, (const void*)sl->da_res.p, sizeof(r));
-    b->sp_ms_kernels = ev_ms(sl->ev_da0, sl->ev_da1);
+    b->sp_ms_kernels = sl->da_span.ms();
     b->sp_bytes = r.bytes;
     b->sp_tail = r.tail_bytes;
     if (r.error != 0) {
@@ -104,7 +104,7 @@ int fdbcs_batch_share_pack_device(fdbcs_batch* b, const fdbcs_packed_batch_dev* 
     share_layout(0, 0, 0, 0, &empty);
     fdbcs_conflict_set* cs = b->cs;
     HIPOK(hipSetDevice(cs->device));
-    BatchSlot* sl = b->slot;
+    BatchSlot* sl = b->slot.get();
     int rc;
     const int64_t n_elems = ingest_elems(T, nk);
     const size_t scan_bytes = align_up(8 * (size_t)share_scan_words(n_elems), 16);
@@ -112,8 +112,6 @@ int fdbcs_batch_share_pack_device(fdbcs_batch* b, const fdbcs_packed_batch_dev* 
     if ((rc = sl->da_dres.ensure(sizeof(ShareResult)))) return rc;
     if ((rc = sl->da_res.ensure(sizeof(ShareResult), true))) return rc;
     if ((rc = sl->sp_toff.ensure(4 * (size_t)std::max<int64_t>(nk, 1)))) return rc;
-    if (!sl->ev_da0) HIPOK(hipEventCreate(&sl->ev_da0));
-    if (!sl->ev_da1) HIPOK(hipEventCreate(&sl->ev_da1));
     ShareArgs a{};
     a.in.T = T;
     a.in.R = R;
@@ -145,10 +143,10 @@ int fdbcs_batch_share_pack_device(fdbcs_batch* b, const fdbcs_packed_batch_dev* 
     HIPOK(hipMemsetAsync(sl->da_scan.p, 0, scan_bytes, us));
     ScanState st{sw + 8, (int*)sw, (int*)(sw + 1)};
     t_record = nullptr;
-    HIPOK(hipEventRecord(sl->ev_da0, us));
+    if (int rc = sl->da_span.begin(us)) return rc;
     launch_share_pack(us, a, st);
     HIPOK(take_launch_error());
-    HIPOK(hipEventRecord(sl->ev_da1, us));
+    if (int rc = sl->da_span.end(us)) return rc;
     b->share_packed = b->sp_pending = true;
     b->sp_rc = FDBCS_OK;
     b->sp_T = T;
@@ -199,7 +197,7 @@ int fdbcs_batch_add_packed_device(fdbcs_batch* b, const fdbcs_packed_batch_dev* 
     if (pb->key_bytes_len >= ((int64_t)1 << 32) || (int64_t)R + W >= ((int64_t)1 << 28)) return FDBCS_E_NOMEM;
     fdbcs_conflict_set* cs = b->cs;
     HIPOK(hipSetDevice(cs->device));
-    BatchSlot* sl = b->slot;
+    BatchSlot* sl = b->slot.get();
     int rc;
     // a key's tail, padded to 8, is shorter than the key: the arena's size bounds the tail region
     const UploadLayout L = upload_layout((size_t)T, (size_t)R, (size_t)W, (size_t)pb->key_bytes_len);
@@ -210,8 +208,6 @@ int fdbcs_batch_add_packed_device(fdbcs_batch* b, const fdbcs_packed_batch_dev* 
     if ((rc = sl->da_dres.ensure(sizeof(IngestResult)))) return rc;
     if ((rc = sl->da_res.ensure(sizeof(IngestResult), true))) return rc;
     if ((rc = make_slot_events(sl))) return rc;
-    if (!sl->ev_da0) HIPOK(hipEventCreate(&sl->ev_da0));
-    if (!sl->ev_da1) HIPOK(hipEventCreate(&sl->ev_da1));
     char* d = (char*)sl->dev.p;
     IngestArgs a{};
     a.T = T;
@@ -247,10 +243,10 @@ int fdbcs_batch_add_packed_device(fdbcs_batch* b, const fdbcs_packed_batch_dev* 
     HIPOK(hipMemsetAsync(sl->da_scan.p, 0, scan_bytes, us));
     ScanState st{sw + 8, (int*)sw, (int*)(sw + 1)};
     t_record = nullptr;
-    HIPOK(hipEventRecord(sl->ev_da0, us));
+    if (int rc = sl->da_span.begin(us)) return rc;
     launch_ingest(us, a, st);
     HIPOK(take_launch_error());
-    HIPOK(hipEventRecord(sl->ev_da1, us));
+    if (int rc = sl->da_span.end(us)) return rc;
     HIPOK(hipEventRecord(sl->ev_up, us));
     b->bd.T = T;
     b->bd.R = R;

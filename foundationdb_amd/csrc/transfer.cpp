@@ -93,8 +93,6 @@ int fdbcs_history_export(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t 
     if ((rc = cs->x_ver.ensure(8 * (size_t)(total + 1)))) return rc;
     if ((rc = cs->x_off.ensure(8 * (size_t)(total + 1)))) return rc;
     if ((rc = cs->x_bytes.ensure((size_t)(16 * total + sc.tail_used + 64)))) return rc;
-    if (!cs->x_ev0) HIPOK(hipEventCreate(&cs->x_ev0));
-    if (!cs->x_ev1) HIPOK(hipEventCreate(&cs->x_ev1));
     a.words = (int64_t*)cs->x_state.p;
     a.tile_tb = a.words + kXwWords + 3 * tiles;  // after the scan's granules
     a.versions = (int64_t*)cs->x_ver.p;
@@ -104,14 +102,14 @@ int fdbcs_history_export(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t 
     hipStream_t s = cs->stream;
     if (!bt.empty()) HIPOK(hipMemcpyAsync(cs->x_btail.p, bt.data(), bt.size(), hipMemcpyHostToDevice, s));
     HIPOK(hipMemsetAsync(cs->x_state.p, 0, 8 * (size_t)(kXwWords + 3 * tiles), s));
-    HIPOK(hipEventRecord(cs->x_ev0, s));
+    if (int rc = cs->x_span.begin(s)) return rc;
     launch_export(s, a, levels_of(cs, cs->cur), (uint64_t*)cs->x_state.p + kXwWords, sc.tail_used > 0 ? 2 : 1);
     HIPOK(take_launch_error());
-    HIPOK(hipEventRecord(cs->x_ev1, s));
+    if (int rc = cs->x_span.end(s)) return rc;
     int64_t words[kXwWords];
     HIPOK(hipMemcpyAsync(words, cs->x_state.p, sizeof(words), hipMemcpyDeviceToHost, s));
     HIPOK(hipStreamSynchronize(s));
-    cs->x_ms_kernels = ev_ms(cs->x_ev0, cs->x_ev1);
+    cs->x_ms_kernels = cs->x_span.ms();
     cs->x_ms_d2h = 0;
     if (((const int32_t*)&words[kXwScan])[1]) return FDBCS_E_DEVICE;  // look-back bound, positions out of order, key buffer
     cs->x_n = words[kXwN];
@@ -165,21 +163,19 @@ int fdbcs_history_digest(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t 
     const int64_t tiles = export_tiles(a.nb + a.nd);
     if ((rc = export_scratch(cs, a, bt))) return rc;
     if ((rc = cs->g_state.ensure(8 * (size_t)(kXwWords + tiles)))) return rc;
-    for (hipEvent_t& e : cs->g_ev)
-        if (!e) HIPOK(hipEventCreate(&e));
     a.words = (int64_t*)cs->g_state.p;
     a.tile_tb = a.words + kXwWords;
     hipStream_t s = cs->stream;
     if (!bt.empty()) HIPOK(hipMemcpyAsync(cs->x_btail.p, bt.data(), bt.size(), hipMemcpyHostToDevice, s));
     HIPOK(hipMemsetAsync(cs->g_state.p, 0, 8 * (size_t)kXwWords, s));
-    HIPOK(hipEventRecord(cs->g_ev[0], s));
+    if (int rc = cs->g_span.begin(s)) return rc;
     launch_export_digest(s, a, levels_of(cs, cs->cur), sc.tail_used > 0 ? 2 : 1);
     HIPOK(take_launch_error());
-    HIPOK(hipEventRecord(cs->g_ev[1], s));
+    if (int rc = cs->g_span.end(s)) return rc;
     int64_t words[kXwWords];
     HIPOK(hipMemcpyAsync(words, cs->g_state.p, sizeof(words), hipMemcpyDeviceToHost, s));
     HIPOK(hipStreamSynchronize(s));
-    cs->g_ms_kernels = ev_ms(cs->g_ev[0], cs->g_ev[1]);
+    cs->g_ms_kernels = cs->g_span.ms();
     cs->g_ms_host = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (((const int32_t*)&words[kXwScan])[1]) return FDBCS_E_DEVICE;  // positions out of order
     out->n = words[kXwN];
@@ -302,8 +298,6 @@ static int import_phase1(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t 
     if ((rc = cs->i_vblt.ensure(8 * (size_t)(n + 2)))) return rc;
     if ((rc = cs->i_state.ensure(8 * (size_t)kIwWords))) return rc;
     if (to_delta && (rc = cs->i_dstate.ensure(8 * (size_t)kIdWords))) return rc;
-    for (hipEvent_t& e : cs->i_ev)
-        if (!e) HIPOK(hipEventCreate(&e));
     pl.u_end = u_end;
     pl.d = ImportDeltaArgs{};
     ImportArgs& a = pl.d.a;
@@ -343,15 +337,15 @@ static int import_phase1(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t 
     const int64_t none = kHole;
     HIPOK(hipMemcpyAsync(&a.words[kIwMaxVer], &none, 8, hipMemcpyHostToDevice, s));
     int64_t words[kIwWords];
-    HIPOK(hipEventRecord(cs->i_ev[0], s));
+    if (int rc = cs->i_span[0].begin(s)) return rc;
     launch_import_overlay(s, a);
     if (to_delta) launch_import_delta_bounds(s, pl.d);
     HIPOK(take_launch_error());
-    HIPOK(hipEventRecord(cs->i_ev[1], s));
+    if (int rc = cs->i_span[0].end(s)) return rc;
     HIPOK(hipMemcpyAsync(words, cs->i_state.p, sizeof(words), hipMemcpyDeviceToHost, s));
     if (to_delta) HIPOK(hipMemcpyAsync(pl.dw, cs->i_dstate.p, sizeof(pl.dw), hipMemcpyDeviceToHost, s));
     HIPOK(hipStreamSynchronize(s));
-    cs->i_ms_kernels = ev_ms(cs->i_ev[0], cs->i_ev[1]);
+    cs->i_ms_kernels = cs->i_span[0].ms();
     if ((int32_t)words[kIwError] & 1) return FDBCS_E_INVALID;
     if (words[kIwError]) return FDBCS_E_DEVICE;
     if (has_lo && has_hi && cmp_bytes(lo_key, lo_len, hi_key, hi_len) == 0) {
@@ -373,17 +367,17 @@ static int import_finish(fdbcs_conflict_set* cs, const ImportArgs& a, bool delta
     Scalars* dsc = (Scalars*)cs->scal.p;
     const MaxLevels lv = delta_tier ? dlevels_of(cs, cs->dcur) : levels_of(cs, cs->cur);
     const int64_t lvl3_n = delta_tier ? cs->dlvl3_n : cs->lvl3_n, lvl2_n = delta_tier ? cs->dlvl2_n : cs->lvl2_n;
-    HIPOK(hipEventRecord(cs->i_ev[4], s));
+    if (int rc = cs->i_span[2].begin(s)) return rc;
     launch_rangemax(s, lv, dsc, delta_tier ? &dsc->ndb[cs->dcur] : &dsc->n, lvl3_n, lvl2_n,
                     std::max<int64_t>(n_new, 1));
     // the top of the rebuilt levels (holes are INT64_MIN), never a pass over the elements
     launch_import_max(s, lv, lvl3_n, &a.words[kIwMaxVer]);
     HIPOK(take_launch_error());
-    HIPOK(hipEventRecord(cs->i_ev[5], s));
+    if (int rc = cs->i_span[2].end(s)) return rc;
     int64_t max_ver;
     HIPOK(hipMemcpyAsync(&max_ver, &a.words[kIwMaxVer], 8, hipMemcpyDeviceToHost, s));
     HIPOK(hipStreamSynchronize(s));
-    cs->i_ms_kernels += ev_ms(cs->i_ev[4], cs->i_ev[5]);
+    cs->i_ms_kernels += cs->i_span[2].ms();
     cs->header_version = a.new_hdr;
     cs->max_written = std::max({cs->max_written, a.new_hdr, max_ver});
     cs->ddir_epoch[0] = cs->ddir_epoch[1] = 0;  // the delta's directory: not trusted until an epilogue refills it
@@ -407,15 +401,15 @@ static int import_fold(fdbcs_conflict_set* cs, ImportPlan& pl, int64_t* boundari
     import_tiers(cs, a, false);
     hipStream_t s = cs->stream;
     HIPOK(hipMemsetAsync(cs->i_gran.p, 0, gran, s));
-    HIPOK(hipEventRecord(cs->i_ev[2], s));
+    if (int rc = cs->i_span[1].begin(s)) return rc;
     HIPOK(hipMemsetAsync(cs->i_mlt.p, 0, 8 * (size_t)(nb + nd + m), s));
     launch_import_fold(s, a, m, (uint64_t*)cs->i_gran.p);
     HIPOK(take_launch_error());
-    HIPOK(hipEventRecord(cs->i_ev[3], s));
+    if (int rc = cs->i_span[1].end(s)) return rc;
     int64_t words[kIwWords];
     HIPOK(hipMemcpyAsync(words, cs->i_state.p, sizeof(words), hipMemcpyDeviceToHost, s));
     HIPOK(hipStreamSynchronize(s));
-    cs->i_ms_kernels += ev_ms(cs->i_ev[2], cs->i_ev[3]);
+    cs->i_ms_kernels += cs->i_span[1].ms();
     if ((int32_t)words[kIwError] & 8) return FDBCS_E_NOMEM;
     if (words[kIwError] || ((const int32_t*)&words[kIwScan])[1]) return FDBCS_E_DEVICE;
     // success: the buffers the fold filled become current, the delta is empty
@@ -496,14 +490,14 @@ static int import_delta_device(fdbcs_conflict_set* cs, const uint8_t* lo_key, in
     d.dwords = (int64_t*)cs->i_dstate.p;
     hipStream_t s = cs->stream;
     HIPOK(hipMemsetAsync(cs->i_dstate.p, 0, 8 * (size_t)(kIdWords + gran), s));
-    HIPOK(hipEventRecord(cs->i_ev[2], s));
+    if (int rc = cs->i_span[1].begin(s)) return rc;
     HIPOK(hipMemsetAsync(cs->i_mlt.p, 0, 8 * (size_t)(total + 1), s));
     launch_import_delta_merge(s, d, (uint64_t*)cs->i_dstate.p + kIdWords);
     HIPOK(take_launch_error());
-    HIPOK(hipEventRecord(cs->i_ev[3], s));
+    if (int rc = cs->i_span[1].end(s)) return rc;
     HIPOK(hipMemcpyAsync(pl.dw, cs->i_dstate.p, sizeof(pl.dw), hipMemcpyDeviceToHost, s));
     HIPOK(hipStreamSynchronize(s));
-    cs->i_ms_kernels += ev_ms(cs->i_ev[2], cs->i_ev[3]);
+    cs->i_ms_kernels += cs->i_span[1].ms();
     if ((int32_t)dw[kIdError] & 8) return FDBCS_E_NOMEM;
     if (dw[kIdError] || ((const int32_t*)&dw[kIdScan])[1]) return FDBCS_E_DEVICE;
     const int64_t kept = dw[kIdKept], units = dw[kIdTailUnits];
@@ -623,9 +617,9 @@ int fdbcs_batch_set_iops_sample(fdbcs_batch* b, int32_t units, uint64_t seed) {
     if (bytes_cap >= ((int64_t)1 << 32)) return FDBCS_E_NOMEM;
     fdbcs_conflict_set* cs = b->cs;
     HIPOK(hipSetDevice(cs->device));
-    BatchSlot* sl = b->slot;
+    BatchSlot* sl = b->slot.get();
     if (sl->is_inflight) {  // a request replaced: its kernel is over before its buffers are touched
-        HIPOK(hipEventSynchronize(sl->ev_is1));
+        HIPOK(hipEventSynchronize(sl->is_span.e1));
         sl->is_inflight = false;
     }
     b->is_req = b->is_done = false;
@@ -637,8 +631,6 @@ int fdbcs_batch_set_iops_sample(fdbcs_batch* b, int32_t units, uint64_t seed) {
     if ((rc = sl->is_off.ensure(8 * (size_t)(cap + 1)))) return rc;
     if ((rc = sl->is_bytes.ensure((size_t)bytes_cap + 64))) return rc;
     if ((rc = sl->is_tot.ensure(sizeof(IopsTotals), true))) return rc;
-    if (!sl->ev_is0) HIPOK(hipEventCreate(&sl->ev_is0));
-    if (!sl->ev_is1) HIPOK(hipEventCreate(&sl->ev_is1));
     IopsArgs a{};
     a.keys = b->bd.keys;
     a.tail = b->bd.tail;
@@ -660,10 +652,10 @@ int fdbcs_batch_set_iops_sample(fdbcs_batch* b, int32_t units, uint64_t seed) {
     uint64_t* sw = (uint64_t*)sl->is_state.p;
     ScanState st{sw + 8, (int*)sw, (int*)(sw + 1)};
     t_record = nullptr;
-    HIPOK(hipEventRecord(sl->ev_is0, us));
+    if (int rc = sl->is_span.begin(us)) return rc;
     launch_iops_sample(us, a, st);
     HIPOK(take_launch_error());
-    HIPOK(hipEventRecord(sl->ev_is1, us));
+    if (int rc = sl->is_span.end(us)) return rc;
     sl->is_inflight = true;
     b->is_req = true;
     return FDBCS_OK;
@@ -675,9 +667,9 @@ int fdbcs_batch_iops_sample(fdbcs_batch* b, int64_t* n_out, int64_t* key_bytes_o
     HIPOK(hipSetDevice(b->cs->device));
     if (int rc = finish_route(b)) return rc;  // the routing's error first (the request went with the batch)
     if (!b->is_req) return FDBCS_E_STATE;
-    BatchSlot* sl = b->slot;
+    BatchSlot* sl = b->slot.get();
     if (!b->is_done) {
-        HIPOK(hipEventSynchronize(sl->ev_is1));
+        HIPOK(hipEventSynchronize(sl->is_span.e1));
         sl->is_inflight = false;
         std::atomic_thread_fence(std::memory_order_acquire);
         IopsTotals t;
@@ -687,7 +679,7 @@ int fdbcs_batch_iops_sample(fdbcs_batch* b, int64_t* n_out, int64_t* key_bytes_o
         if (words[2] || t.n < 0) return FDBCS_E_DEVICE;  // look-back bound, key buffer
         b->is_n = t.n;
         b->is_nbytes = t.key_bytes;
-        b->is_ms = ev_ms(sl->ev_is0, sl->ev_is1);
+        b->is_ms = sl->is_span.ms();
         b->is_done = true;
     }
     *n_out = b->is_n;
@@ -702,7 +694,7 @@ int fdbcs_batch_iops_sample_read(fdbcs_batch* b, uint8_t* key_bytes, int64_t key
     if (cap < b->is_n || key_bytes_cap < b->is_nbytes) return FDBCS_E_NOMEM;
     if ((b->is_n && !metrics) || (b->is_nbytes && !key_bytes)) return FDBCS_E_INVALID;
     HIPOK(hipSetDevice(b->cs->device));
-    const BatchSlot* sl = b->slot;
+    const BatchSlot* sl = b->slot.get();
     if (b->is_n && index) HIPOK(hipMemcpy(index, sl->is_idx.p, 4 * (size_t)b->is_n, hipMemcpyDeviceToHost));
     return copy_keyed_result(b->is_n, b->is_nbytes, metrics, sl->is_met.p, 4, key_offsets, sl->is_off.p, key_bytes,
                              sl->is_bytes.p);
@@ -739,8 +731,6 @@ static int read_versions(fdbcs_batch* b, int64_t floor_version, int64_t* out, in
     if (int rc = sync_all(cs)) return rc;  // the upload too
     if (cs->rv_err.ensure(sizeof(int))) return FDBCS_E_NOMEM;
     if (!device_form && cs->rv_out.ensure(8 * (size_t)R)) return FDBCS_E_NOMEM;
-    for (hipEvent_t& e : cs->rv_ev)
-        if (!e) HIPOK(hipEventCreate(&e));
     Scalars* sc = (Scalars*)cs->scal.p;
     ReadVersionsArgs a{};
     a.b = b->bd;
@@ -753,16 +743,16 @@ static int read_versions(fdbcs_batch* b, int64_t floor_version, int64_t* out, in
     hipStream_t s = cs->stream;
     t_record = nullptr;
     HIPOK(hipMemsetAsync(cs->rv_err.p, 0, sizeof(int), s));
-    HIPOK(hipEventRecord(cs->rv_ev[0], s));
+    if (int rc = cs->rv_span.begin(s)) return rc;
     // the long-key form by the read check's rule (engine.cpp plan_layout)
     const void* func = launch_read_versions(s, a, b->max_len > 24);
     HIPOK(take_launch_error());
-    HIPOK(hipEventRecord(cs->rv_ev[1], s));
+    if (int rc = cs->rv_span.end(s)) return rc;
     int err = 0;
     HIPOK(hipMemcpyAsync(&err, cs->rv_err.p, sizeof(err), hipMemcpyDeviceToHost, s));
     if (!device_form) HIPOK(hipMemcpyAsync(out, cs->rv_out.p, 8 * (size_t)R, hipMemcpyDeviceToHost, s));
     HIPOK(hipStreamSynchronize(s));
-    cs->rv_ms_kernels = ev_ms(cs->rv_ev[0], cs->rv_ev[1]);
+    cs->rv_ms_kernels = cs->rv_span.ms();
     // which instantiation ran, as fdbcs_kernel_profile reports the pipeline's kernels
     auto it = std::find_if(cs->kprof.begin(), cs->kprof.end(), [&](const auto& k) { return k.func == func; });
     if (it == cs->kprof.end()) it = cs->kprof.insert(cs->kprof.end(), {func, 0, 0.0});

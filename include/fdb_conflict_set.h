@@ -697,6 +697,12 @@ int fdbcs_set_timed_kernel(fdbcs_conflict_set* cs, const char* name);
  * submitted next wait behind it; on == 0 releases them, and they run back to back at the device's
  * own rate (the device-bound throughput, free of the submitting thread). */
 int fdbcs_debug_hold(fdbcs_conflict_set* cs, int32_t on);
+/* Diagnostics: what the engine holds of the HIP runtime right now, over every set and batch of the
+ * process: device allocations, pinned host allocations, events and streams.  Each count goes up
+ * where the runtime handed one out and down where it took one back, so the four are back at their
+ * earlier values once the sets and batches created since are destroyed (a leak check for tests).
+ * Needs no device and no set; FDBCS_E_INVALID on a NULL pointer. */
+int fdbcs_debug_live_resources(int64_t* device_buffers, int64_t* host_buffers, int64_t* events, int64_t* streams);
 
 const char* fdbcs_strerror(int status);
 

@@ -62,6 +62,19 @@ def test_no_cpu_fallback_without_device(lib):
     assert e.value.status == C.FDBCS_E_NODEVICE
 
 
+def test_nothing_is_held_after_a_set_failed_without_device(lib):
+    import torch
+
+    from foundationdb_amd import conflict_set as C
+
+    if torch.cuda.is_available():
+        pytest.skip("GPU present")
+    with pytest.raises(C.FdbcsError) as e:
+        C.ConflictSet(0)
+    assert e.value.status == C.FDBCS_E_NODEVICE
+    assert C.live_resources() == (0, 0, 0, 0)
+
+
 def test_strerror(lib):
     from foundationdb_amd import conflict_set as C
 
