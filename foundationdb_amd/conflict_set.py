@@ -161,6 +161,14 @@ SIGNATURES = {
     "fdbcs_history_digest_arrays": (ctypes.c_int, [_I64, _VP, _VP, _VP, _I64, ctypes.POINTER(_CDigest)]),
     "fdbcs_history_digest_timing": (ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_double),
                                                    ctypes.POINTER(ctypes.c_double)]),
+    "fdbcs_history_digest_ranges": (ctypes.c_int, [_VP, _I32, _VP, _VP, ctypes.c_int, ctypes.c_int, _I64, _VP]),
+    "fdbcs_history_digest_arrays_ranges": (ctypes.c_int, [_I64, _VP, _VP, _VP, _I64, _I32, _VP, _VP, ctypes.c_int,
+                                                          ctypes.c_int, _VP]),
+    "fdbcs_history_split_keys": (ctypes.c_int, [_VP, _VP, _I32, _VP, _I32, _I32, ctypes.POINTER(_I64),
+                                                ctypes.POINTER(_I64)]),
+    "fdbcs_history_split_keys_read": (ctypes.c_int, [_VP, _VP, _I64, _VP, _I64]),
+    "fdbcs_history_split_keys_timing": (ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_double),
+                                                       ctypes.POINTER(ctypes.c_double)]),
     "fdbcs_history_import": (ctypes.c_int, [_VP, _VP, _I32, _VP, _I32, _I64, _VP, _VP, _VP, _I64,
                                             ctypes.POINTER(_I64)]),
     "fdbcs_history_import_pending": (ctypes.c_int, [_VP, _VP, _VP, _I32, _VP, _I32, ctypes.POINTER(_I64)]),
@@ -321,6 +329,98 @@ def digest_arrays(key_bytes, key_offsets, versions, header_version: int = 0) -> 
     if rc != FDBCS_OK:
         raise FdbcsError(rc, "historyDigestArrays")
     return HistoryDigest._of(d)
+
+
+def _bounds_arrays(bounds, open_lo: bool, open_hi: bool):
+    """The bounds of a partition in the export's key layout and the number of ranges they define."""
+    bounds = [bytes(b) for b in bounds]
+    kb = np.frombuffer(b"".join(bounds), np.uint8)
+    ko = np.zeros(len(bounds) + 1, np.int64)
+    np.cumsum([len(b) for b in bounds], out=ko[1:])
+    return kb, ko, len(bounds) - 1 + bool(open_lo) + bool(open_hi)
+
+
+def digest_arrays_ranges(key_bytes, key_offsets, versions, header_version: int, bounds, open_lo: bool = False,
+                         open_hi: bool = False) -> List[HistoryDigest]:
+    """fdbcs_history_digest_arrays_ranges (host only): one digest per range of the partition `bounds`
+    define (ConflictSet.digest_ranges has the ranges' order) over arrays in the layout dump_history
+    returns, read as given; the keys must ascend.  Range i's header is the version of the last
+    boundary <= its lower bound, its boundaries those strictly inside.  How a checkpoint file or a
+    model's canonical form is digested chunk by chunk."""
+    kb = np.ascontiguousarray(key_bytes, np.uint8)
+    ko = np.ascontiguousarray(key_offsets, np.int64)
+    vv = np.ascontiguousarray(versions, np.int64)
+    bb, bo, K = _bounds_arrays(bounds, open_lo, open_hi)
+    out = (_CDigest * max(K, 1))()
+    rc = load_library().fdbcs_history_digest_arrays_ranges(len(vv), _p(kb), _p(ko), _p(vv), int(header_version),
+                                                           len(bo) - 1, _p(bb), _p(bo), int(bool(open_lo)),
+                                                           int(bool(open_hi)), ctypes.addressof(out))
+    if rc != FDBCS_OK:
+        raise FdbcsError(rc, "historyDigestArraysRanges")
+    return [HistoryDigest._of(out[i]) for i in range(K)]
+
+
+def locate_divergence(digests_a, digests_b, split_keys_a, lo: Optional[bytes] = None, hi: Optional[bytes] = None,
+                      fanout: int = 256, leaf: int = 64) -> List[Tuple[Optional[bytes], Optional[bytes]]]:
+    """Where two holders of [lo, hi) differ, by a `fanout`-way bisection on digests: the ascending list
+    of disjoint (lo, hi) ranges (None: an open end) whose digests differ, each refined until both
+    sides report n <= `leaf` there or side a has no split key left inside it; [] when the whole-range
+    digests are equal.  The sides are callables, so they may live in different processes:
+    digests_x(bounds, open_lo, open_hi) returns that side's digests (ConflictSet.digest_ranges, or
+    digest_arrays_ranges over a dump, under one floor), split_keys_a(lo, hi, want) keys of side a
+    strictly inside (lo, hi) (ConflictSet.split_keys): both sides are digested on side a's keys.
+    A range [s, t) covers a difference at s itself: H_f(s) is its header.  One digests call per side
+    and level, whatever the number of ranges refined at that level."""
+    if fanout < 2 or leaf < 0:
+        raise ValueError("fanout must be at least 2 and leaf at least 0")
+
+    def both(edges):
+        bounds = [e for e in edges if e is not None]
+        ol, oh = edges[0] is None, edges[-1] is None
+        da, db = digests_a(bounds, ol, oh), digests_b(bounds, ol, oh)
+        if len(da) != len(edges) - 1 or len(db) != len(edges) - 1:
+            raise ValueError("a side returned a digest count other than the number of ranges")
+        return da, db
+
+    da, db = both([lo, hi])
+    if tuple(da[0]) == tuple(db[0]):
+        return []
+    level, found = [((lo, hi), da[0], db[0])], []
+    while level:
+        # the edges of this level: every range still refined, cut at side a's keys
+        edges, watch, nxt = [], [], []
+
+        def flush():
+            if watch:
+                da, db = both(edges)
+                subs = {}
+                for parent, i in watch:
+                    differing = subs.setdefault(parent, [])
+                    if tuple(da[i]) != tuple(db[i]):
+                        differing.append(((edges[i], edges[i + 1]), da[i], db[i]))
+                for parent, differing in subs.items():
+                    if differing:
+                        nxt.extend(differing)
+                    else:  # only by hash accident: the parent stands as it is
+                        found.append(parent)
+            edges.clear()
+            watch.clear()
+
+        for (rlo, rhi), ra, rb in level:
+            keys = [] if ra.n <= leaf and rb.n <= leaf else [bytes(k) for k in split_keys_a(rlo, rhi, fanout - 1)]
+            if not keys:
+                found.append((rlo, rhi))
+                continue
+            if len(edges) + len(keys) + 2 > 60000:  # a call takes at most 65536 ranges
+                flush()
+            if edges and (edges[-1] is None or rlo is None or edges[-1] > rlo):
+                raise ValueError("split keys out of order")
+            first = len(edges)
+            edges.extend([rlo] + keys + [rhi])
+            watch.extend(((rlo, rhi), i) for i in range(first, first + len(keys) + 1))
+        flush()
+        level = nxt
+    return sorted(found, key=lambda r: (r[0] is not None, r[0] or b""))
 
 
 def live_resources() -> Tuple[int, int, int, int]:
@@ -516,6 +616,55 @@ class ConflictSet:
         a, b = ctypes.c_double(), ctypes.c_double()
         _check(load_library().fdbcs_history_digest_timing(self._h, ctypes.byref(a), ctypes.byref(b)), "digestTiming")
         return a.value, b.value
+
+    def digest_ranges(self, bounds, floor: Optional[int] = None, open_lo: bool = False,
+                      open_hi: bool = False) -> List[HistoryDigest]:
+        """fdbcs_history_digest_ranges: the digests of the ranges the ascending keys `bounds` define,
+        in one pass on the device: first the range below bounds[0] if `open_lo`, then
+        [bounds[i], bounds[i + 1]) for each neighbouring pair, then the range from bounds[-1] on if
+        `open_hi`.  Entry i equals digest(lo_i, hi_i, floor) of range i."""
+        if floor is None:
+            floor = self.oldest_version
+        bb, bo, K = _bounds_arrays(bounds, open_lo, open_hi)
+        out = (_CDigest * max(K, 1))()
+        _check(load_library().fdbcs_history_digest_ranges(self._h, len(bo) - 1, _p(bb), _p(bo), int(bool(open_lo)),
+                                                          int(bool(open_hi)), floor, ctypes.addressof(out)),
+               "historyDigestRanges")
+        return [HistoryDigest._of(out[i]) for i in range(K)]
+
+    def split_keys(self, lo: Optional[bytes], hi: Optional[bytes], want: int) -> List[bytes]:
+        """fdbcs_history_split_keys: up to `want` boundary keys strictly inside (lo, hi), ascending, at
+        evenly spaced positions of the tier that holds more boundaries there.  They depend on the tier
+        split and the GC cadence, not on the canonical history alone: use them as bounds only, and on
+        both sides of a comparison use one side's keys."""
+        L = load_library()
+        kl, ll, kh, hl = self._bounds(lo, hi)
+        n, nb = _I64(), _I64()
+        _check(L.fdbcs_history_split_keys(self._h, _p(kl), ll, _p(kh), hl, int(want), ctypes.byref(n), ctypes.byref(nb)),
+               "historySplitKeys")
+        kb = np.empty(nb.value, np.uint8)
+        ko = np.empty(n.value + 1, np.int64)
+        _check(L.fdbcs_history_split_keys_read(self._h, _p(kb), nb.value, _p(ko), n.value), "historySplitKeysRead")
+        raw = kb.tobytes()
+        return [raw[ko[i]:ko[i + 1]] for i in range(n.value)]
+
+    def split_keys_timing(self) -> Tuple[float, float]:
+        """Milliseconds of the last split_keys' kernels (device) and of its first call (host)."""
+        a, b = ctypes.c_double(), ctypes.c_double()
+        _check(load_library().fdbcs_history_split_keys_timing(self._h, ctypes.byref(a), ctypes.byref(b)),
+               "splitKeysTiming")
+        return a.value, b.value
+
+    def diverging_ranges(self, other: "ConflictSet", lo: Optional[bytes] = None, hi: Optional[bytes] = None,
+                         floor: Optional[int] = None, fanout: int = 256, leaf: int = 64):
+        """locate_divergence for two sets of one process: the ranges of [lo, hi) in which this set's
+        and `other`'s canonical histories differ under `floor` (default: this set's oldest version),
+        bisected on this set's split keys."""
+        if floor is None:
+            floor = self.oldest_version
+        return locate_divergence(lambda b, ol, oh: self.digest_ranges(b, floor, ol, oh),
+                                 lambda b, ol, oh: other.digest_ranges(b, floor, ol, oh), self.split_keys, lo, hi,
+                                 fanout, leaf)
 
     def read_versions(self, ranges, floor: Optional[int] = None) -> np.ndarray:
         """The history version each of `ranges` (a list of (begin, end) byte pairs, begin <= end) is

@@ -555,6 +555,17 @@ struct fdbcs_conflict_set {
     DBuf g_state;
     Span g_span;                                  // around the digest's kernels
     double g_ms_kernels = 0, g_ms_host = 0;       // of the last digest (fdbcs_history_digest_timing)
+    // fdbcs_history_digest_ranges: the bounds as uploaded (bytes, offsets), two stream positions per
+    // edge and the result blocks; they grow with the number of ranges only.  Words, tile starts and
+    // timing are the digest's (g_state, g_span, g_ms_*).
+    DBuf r_bytes, r_off, r_pos, r_out;
+    // fdbcs_history_split_keys: its words, and the result (offsets, key bytes) until it is read.  The
+    // result is a copy, so it outlives changes of the set; another call replaces it.
+    DBuf k_state, k_off, k_bytes;
+    bool k_valid = false;
+    int64_t k_n = 0, k_nbytes = 0;
+    Span k_span;
+    double k_ms_kernels = 0, k_ms_host = 0;       // of the last call (fdbcs_history_split_keys_timing)
     // fdbcs_batch_read_versions: the host form's result (grow-only; the device form writes to the
     // caller's memory) and the error word, allocated by the first query; nothing of the export's
     DBuf rv_out, rv_err;

@@ -1,5 +1,6 @@
 // transfer.cpp — the maintenance entry points of the C-ABI (include/fdb_conflict_set.h): history
-// export, the two history imports, the resolver's iops sample and the read versions of a batch.
+// export, the history digests, split keys, the two history imports, the resolver's iops sample and
+// the read versions of a batch.
 // They work on an idle set (or, for the sample, off the detect stream) through the state and
 // helpers of engine_impl.h and launch the kernels of transfer.hip; the detect pipeline's host side
 // is engine.cpp.
@@ -66,6 +67,53 @@ static inline uint64_t digest_mix(uint64_t z) {
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
+}
+
+// e_c(k, v) of the definition for both lanes.
+static inline void digest_entry(const uint8_t* p, uint64_t len, int64_t version, uint64_t (&e)[2]) {
+    constexpr uint64_t G = 0x9E3779B97F4A7C15ull, S[2] = {0x243F6A8885A308D3ull, 0x13198A2E03707344ull};
+    uint64_t h[2] = {digest_mix(S[0] + len), digest_mix(S[1] + len)};
+    for (uint64_t o = 0; o < len; o += 8) {
+        uint64_t w = 0;  // bytes [o, o + 8) big-endian, zero past the key
+        for (uint64_t b = 0; b < 8; b++) w = (w << 8) | (o + b < len ? p[o + b] : 0);
+        for (uint64_t& x : h) x = digest_mix((x ^ w) + G);
+    }
+    for (int c = 0; c < 2; c++) e[c] = digest_mix((h[c] ^ (uint64_t)version) + G);
+}
+
+// The arrays of a digest on the host (fdbcs_history_digest_arrays and its partitioned form).
+static int digest_arrays_ok(int64_t n, const uint8_t* key_bytes, const int64_t* key_offsets, const int64_t* versions) {
+    if (n < 0 || (n > 0 && (!key_offsets || !versions))) return FDBCS_E_INVALID;
+    if (n > 0 && key_offsets[0] != 0) return FDBCS_E_INVALID;
+    for (int64_t i = 0; i < n; i++)
+        if (key_offsets[i + 1] < key_offsets[i]) return FDBCS_E_INVALID;
+    if (n > 0 && key_offsets[n] > 0 && !key_bytes) return FDBCS_E_INVALID;
+    return FDBCS_OK;
+}
+
+constexpr int64_t kMaxDigestRanges = 65536;  // as the routing map's ranges
+
+// The bounds of a partition (fdbcs_history_digest_ranges and its host form): ascending keys in the
+// export's layout; *K_out: the ranges they and the open ends define.
+static int ranges_bounds_ok(int32_t n_bounds, const uint8_t* bound_bytes, const int64_t* bound_offsets, int open_lo,
+                            int open_hi, int64_t* K_out) {
+    if (n_bounds < 0 || (n_bounds > 0 && !bound_offsets)) return FDBCS_E_INVALID;
+    const int64_t K = (int64_t)n_bounds - 1 + (open_lo ? 1 : 0) + (open_hi ? 1 : 0);
+    if (K < 1) return FDBCS_E_INVALID;
+    if (n_bounds > 0 && bound_offsets[0] != 0) return FDBCS_E_INVALID;
+    for (int32_t i = 0; i < n_bounds; i++) {
+        const int64_t len = bound_offsets[i + 1] - bound_offsets[i];
+        if (len < 0 || len > (int64_t)INT32_MAX) return FDBCS_E_INVALID;
+    }
+    if (n_bounds > 0 && bound_offsets[n_bounds] > 0 && !bound_bytes) return FDBCS_E_INVALID;
+    if (K > kMaxDigestRanges) return FDBCS_E_NOMEM;
+    for (int32_t i = 1; i < n_bounds; i++) {
+        const int64_t* o = bound_offsets + i - 1;
+        if (cmp_bytes(bound_bytes + o[0], (int32_t)(o[1] - o[0]), bound_bytes + o[1], (int32_t)(o[2] - o[1])) > 0)
+            return FDBCS_E_INVALID;
+    }
+    *K_out = K;
+    return FDBCS_OK;
 }
 
 extern "C" {
@@ -188,29 +236,223 @@ int fdbcs_history_digest(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t 
 
 int fdbcs_history_digest_arrays(int64_t n, const uint8_t* key_bytes, const int64_t* key_offsets,
                                 const int64_t* versions, int64_t header_version, fdbcs_digest* out) {
-    if (!out || n < 0 || (n > 0 && (!key_offsets || !versions))) return FDBCS_E_INVALID;
-    if (n > 0 && key_offsets[0] != 0) return FDBCS_E_INVALID;
-    for (int64_t i = 0; i < n; i++)
-        if (key_offsets[i + 1] < key_offsets[i]) return FDBCS_E_INVALID;
-    if (n > 0 && key_offsets[n] > 0 && !key_bytes) return FDBCS_E_INVALID;
-    constexpr uint64_t G = 0x9E3779B97F4A7C15ull, S[2] = {0x243F6A8885A308D3ull, 0x13198A2E03707344ull};
+    if (!out) return FDBCS_E_INVALID;
+    if (int rc = digest_arrays_ok(n, key_bytes, key_offsets, versions)) return rc;
     uint64_t sum[2] = {0, 0};
     for (int64_t i = 0; i < n; i++) {
-        const uint8_t* p = key_bytes + key_offsets[i];
-        const uint64_t len = (uint64_t)(key_offsets[i + 1] - key_offsets[i]);
-        uint64_t h[2] = {digest_mix(S[0] + len), digest_mix(S[1] + len)};
-        for (uint64_t o = 0; o < len; o += 8) {
-            uint64_t w = 0;  // bytes [o, o + 8) big-endian, zero past the key
-            for (uint64_t b = 0; b < 8; b++) w = (w << 8) | (o + b < len ? p[o + b] : 0);
-            for (uint64_t& x : h) x = digest_mix((x ^ w) + G);
-        }
-        for (int c = 0; c < 2; c++) sum[c] += digest_mix((h[c] ^ (uint64_t)versions[i]) + G);
+        uint64_t e[2];
+        digest_entry(key_bytes + key_offsets[i], (uint64_t)(key_offsets[i + 1] - key_offsets[i]), versions[i], e);
+        sum[0] += e[0];
+        sum[1] += e[1];
     }
     out->n = n;
     out->key_bytes = n > 0 ? key_offsets[n] : 0;
     out->header_version = header_version;
     out->sum[0] = sum[0];
     out->sum[1] = sum[1];
+    return FDBCS_OK;
+}
+
+int fdbcs_history_digest_ranges(fdbcs_conflict_set* cs, int32_t n_bounds, const uint8_t* bound_bytes,
+                                const int64_t* bound_offsets, int open_lo, int open_hi, int64_t floor_version,
+                                fdbcs_digest* out) {
+    if (!cs || !out) return FDBCS_E_INVALID;
+    int64_t K = 0;
+    if (int rc = ranges_bounds_ok(n_bounds, bound_bytes, bound_offsets, open_lo, open_hi, &K)) return rc;
+    const int64_t nbytes = n_bounds > 0 ? bound_offsets[n_bounds] : 0;
+    if (nbytes + 16 >= ((int64_t)1 << 32)) return FDBCS_E_NOMEM;  // a bound's tail offset is 32-bit
+    if (cs->inflight) return FDBCS_E_STATE;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPOK(hipSetDevice(cs->device));
+    if (int rc = sync_all(cs)) return rc;
+    // the span's bounds for the launches the digest shares: the first and the last bound
+    const uint8_t* lo_key = nullptr;
+    const uint8_t* hi_key = nullptr;
+    int32_t lo_len = -1, hi_len = -1;
+    if (!open_lo) lo_key = bound_bytes, lo_len = (int32_t)bound_offsets[1];
+    if (!open_hi) {
+        hi_key = bound_bytes + bound_offsets[n_bounds - 1];
+        hi_len = (int32_t)(nbytes - bound_offsets[n_bounds - 1]);
+    }
+    Scalars sc;
+    ExportArgs a;
+    std::vector<uint8_t> bt;
+    int rc;
+    if ((rc = export_inputs(cs, lo_key, lo_len, hi_key, hi_len, floor_version, a, sc, bt))) return rc;
+    const int64_t tiles = export_tiles(a.nb + a.nd);
+    if ((rc = export_scratch(cs, a, bt))) return rc;
+    if ((rc = cs->g_state.ensure(8 * (size_t)(kXwWords + tiles)))) return rc;
+    if ((rc = cs->r_bytes.ensure((size_t)nbytes + kTailSlack))) return rc;
+    if ((rc = cs->r_off.ensure(8 * (size_t)(n_bounds + 1)))) return rc;
+    if ((rc = cs->r_pos.ensure(16 * (size_t)(K + 1)))) return rc;
+    if ((rc = cs->r_out.ensure(8 * (size_t)(kDrWords * K)))) return rc;
+    a.words = (int64_t*)cs->g_state.p;
+    a.tile_tb = a.words + kXwWords;
+    DigestRangesArgs r{};
+    r.n_bounds = n_bounds;
+    r.open_lo = open_lo ? 1 : 0;
+    r.open_hi = open_hi ? 1 : 0;
+    r.K = K;
+    r.bytes = (const uint8_t*)cs->r_bytes.p;
+    r.offsets = (const int64_t*)cs->r_off.p;
+    r.lt = (int64_t*)cs->r_pos.p;
+    r.le = r.lt + (K + 1);
+    r.out = (int64_t*)cs->r_out.p;
+    hipStream_t s = cs->stream;
+    if (!bt.empty()) HIPOK(hipMemcpyAsync(cs->x_btail.p, bt.data(), bt.size(), hipMemcpyHostToDevice, s));
+    if (nbytes) HIPOK(hipMemcpyAsync(cs->r_bytes.p, bound_bytes, (size_t)nbytes, hipMemcpyHostToDevice, s));
+    if (n_bounds)
+        HIPOK(hipMemcpyAsync(cs->r_off.p, bound_offsets, 8 * (size_t)(n_bounds + 1), hipMemcpyHostToDevice, s));
+    HIPOK(hipMemsetAsync(cs->g_state.p, 0, 8 * (size_t)kXwWords, s));
+    HIPOK(hipMemsetAsync(cs->r_out.p, 0, 8 * (size_t)(kDrWords * K), s));
+    if (int rc = cs->g_span.begin(s)) return rc;
+    launch_export_digest_ranges(s, a, r, levels_of(cs, cs->cur), sc.tail_used > 0 ? 2 : 1);
+    HIPOK(take_launch_error());
+    if (int rc = cs->g_span.end(s)) return rc;
+    int64_t words[kXwWords];
+    std::vector<int64_t> res((size_t)(kDrWords * K));
+    HIPOK(hipMemcpyAsync(words, cs->g_state.p, sizeof(words), hipMemcpyDeviceToHost, s));
+    HIPOK(hipMemcpyAsync(res.data(), cs->r_out.p, 8 * res.size(), hipMemcpyDeviceToHost, s));
+    HIPOK(hipStreamSynchronize(s));
+    cs->g_ms_kernels = cs->g_span.ms();
+    cs->g_ms_host = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (((const int32_t*)&words[kXwScan])[1]) return FDBCS_E_DEVICE;  // positions out of order
+    for (int64_t i = 0; i < K; i++) {
+        const int64_t* w = res.data() + kDrWords * i;
+        out[i].n = w[kDrN];
+        out[i].key_bytes = w[kDrBytes];
+        out[i].header_version = w[kDrHeader];
+        out[i].sum[0] = (uint64_t)w[kDrSum0];
+        out[i].sum[1] = (uint64_t)w[kDrSum1];
+    }
+    return FDBCS_OK;
+}
+
+int fdbcs_history_digest_arrays_ranges(int64_t n, const uint8_t* key_bytes, const int64_t* key_offsets,
+                                       const int64_t* versions, int64_t header_version, int32_t n_bounds,
+                                       const uint8_t* bound_bytes, const int64_t* bound_offsets, int open_lo,
+                                       int open_hi, fdbcs_digest* out) {
+    if (!out) return FDBCS_E_INVALID;
+    if (int rc = digest_arrays_ok(n, key_bytes, key_offsets, versions)) return rc;
+    int64_t K = 0;
+    if (int rc = ranges_bounds_ok(n_bounds, bound_bytes, bound_offsets, open_lo, open_hi, &K)) return rc;
+    for (int64_t i = 0; i < n; i++)
+        if (key_offsets[i + 1] - key_offsets[i] > (int64_t)INT32_MAX) return FDBCS_E_INVALID;
+    for (int64_t i = 0; i < K; i++) out[i] = fdbcs_digest{0, 0, header_version, {0, 0}};
+    const int shift = open_lo ? 1 : 0;  // bound b is edge b + shift
+    auto header = [&](int64_t b, int64_t v) {
+        if (b + shift < K) out[b + shift].header_version = v;
+    };
+    auto cmp = [&](int64_t b, int64_t i) {  // bound b against boundary i
+        return cmp_bytes(bound_bytes + bound_offsets[b], (int32_t)(bound_offsets[b + 1] - bound_offsets[b]),
+                         key_bytes + key_offsets[i], (int32_t)(key_offsets[i + 1] - key_offsets[i]));
+    };
+    // one walk over the boundaries and the bounds, both ascending: b = bounds at or below boundary i
+    int64_t cur = header_version, b = 0;
+    for (int64_t i = 0; i < n; i++) {
+        while (b < n_bounds && cmp(b, i) < 0) header(b++, cur);  // the bound lies below this boundary
+        cur = versions[i];
+        bool on_bound = false;
+        while (b < n_bounds && cmp(b, i) == 0) header(b++, cur), on_bound = true;
+        const int64_t range = b - 1 + shift;  // after its last bound at or below
+        if (on_bound || range < 0 || range >= K) continue;
+        uint64_t e[2];
+        const uint64_t len = (uint64_t)(key_offsets[i + 1] - key_offsets[i]);
+        digest_entry(key_bytes + key_offsets[i], len, versions[i], e);
+        out[range].n += 1;
+        out[range].key_bytes += (int64_t)len;
+        out[range].sum[0] += e[0];
+        out[range].sum[1] += e[1];
+    }
+    while (b < n_bounds) header(b++, cur);
+    return FDBCS_OK;
+}
+
+int fdbcs_history_split_keys(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, const uint8_t* hi_key,
+                             int32_t hi_len, int32_t want, int64_t* n_out, int64_t* key_bytes_out) {
+    if (!cs || !n_out || !key_bytes_out || want < 0) return FDBCS_E_INVALID;
+    if (int rc = import_bounds_ok(lo_key, lo_len, hi_key, hi_len)) return rc;
+    if (want > kMaxDigestRanges) return FDBCS_E_NOMEM;
+    if (cs->inflight) return FDBCS_E_STATE;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPOK(hipSetDevice(cs->device));
+    if (int rc = sync_all(cs)) return rc;
+    cs->k_valid = false;
+    Scalars sc;
+    ExportArgs x;  // the tiers and the bounds as the export reads them
+    std::vector<uint8_t> bt;
+    int rc;
+    if ((rc = export_inputs(cs, lo_key, lo_len, hi_key, hi_len, kHole, x, sc, bt))) return rc;
+    if ((rc = cs->x_btail.ensure(bt.size() + kTailSlack))) return rc;
+    if ((rc = cs->k_state.ensure(8 * (size_t)kSwWords))) return rc;
+    if ((rc = cs->k_off.ensure(8 * (size_t)(want + 1)))) return rc;
+    SplitArgs a{};
+    a.base = x.base;
+    a.delta = x.delta;
+    a.htail = x.htail;
+    a.nb = x.nb;
+    a.nd = x.nd;
+    a.has_lo = x.has_lo;
+    a.has_hi = x.has_hi;
+    a.lo = x.lo;
+    a.hi = x.hi;
+    a.btail = (const uint8_t*)cs->x_btail.p;
+    a.want = want;
+    a.words = (int64_t*)cs->k_state.p;
+    a.offsets = (int64_t*)cs->k_off.p;
+    hipStream_t s = cs->stream;
+    if (!bt.empty()) HIPOK(hipMemcpyAsync(cs->x_btail.p, bt.data(), bt.size(), hipMemcpyHostToDevice, s));
+    HIPOK(hipMemsetAsync(cs->k_state.p, 0, 8 * (size_t)kSwWords, s));
+    if (int rc = cs->k_span.begin(s)) return rc;
+    launch_split_plan(s, a);
+    HIPOK(take_launch_error());
+    if (int rc = cs->k_span.end(s)) return rc;
+    int64_t words[kSwWords];
+    HIPOK(hipMemcpyAsync(words, cs->k_state.p, sizeof(words), hipMemcpyDeviceToHost, s));
+    HIPOK(hipStreamSynchronize(s));
+    double ms = cs->k_span.ms();
+    const int64_t n = words[kSwN], nbytes = words[kSwBytes];
+    if (n < 0 || n > want || nbytes < 0 || nbytes > 16 * n + sc.tail_used) return FDBCS_E_DEVICE;
+    if (n > 0) {
+        if ((rc = cs->k_bytes.ensure((size_t)nbytes + 64))) return rc;
+        a.bytes = (uint8_t*)cs->k_bytes.p;
+        a.bytes_cap = (int64_t)cs->k_bytes.cap;
+        if (int rc = cs->k_span.begin(s)) return rc;
+        launch_split_gather(s, a, n);
+        HIPOK(take_launch_error());
+        if (int rc = cs->k_span.end(s)) return rc;
+        HIPOK(hipMemcpyAsync(words, cs->k_state.p, sizeof(words), hipMemcpyDeviceToHost, s));
+        HIPOK(hipStreamSynchronize(s));
+        ms += cs->k_span.ms();
+        if ((int32_t)words[kSwError]) return FDBCS_E_DEVICE;  // an offset past the key buffer
+    }
+    cs->k_ms_kernels = ms;
+    cs->k_ms_host = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    cs->k_n = n;
+    cs->k_nbytes = nbytes;
+    cs->k_valid = true;
+    *n_out = n;
+    *key_bytes_out = nbytes;
+    return FDBCS_OK;
+}
+
+int fdbcs_history_split_keys_read(fdbcs_conflict_set* cs, uint8_t* key_bytes, int64_t key_bytes_cap,
+                                  int64_t* key_offsets, int64_t cap) {
+    if (!cs || key_bytes_cap < 0 || cap < 0 || !key_offsets) return FDBCS_E_INVALID;
+    if (!cs->k_valid) return FDBCS_E_STATE;
+    if (cap < cs->k_n || key_bytes_cap < cs->k_nbytes) return FDBCS_E_NOMEM;
+    if (cs->k_nbytes && !key_bytes) return FDBCS_E_INVALID;
+    HIPOK(hipSetDevice(cs->device));
+    HIPOK(hipMemcpy(key_offsets, cs->k_off.p, 8 * (size_t)(cs->k_n + 1), hipMemcpyDeviceToHost));
+    if (cs->k_nbytes) HIPOK(hipMemcpy(key_bytes, cs->k_bytes.p, (size_t)cs->k_nbytes, hipMemcpyDeviceToHost));
+    cs->k_valid = false;
+    return FDBCS_OK;
+}
+
+int fdbcs_history_split_keys_timing(fdbcs_conflict_set* cs, double* ms_kernels, double* ms_host) {
+    if (!cs || !ms_kernels || !ms_host) return FDBCS_E_INVALID;
+    *ms_kernels = cs->k_ms_kernels;
+    *ms_host = cs->k_ms_host;
     return FDBCS_OK;
 }
 

@@ -1,7 +1,7 @@
 // transfer.h — internal interface between the maintenance entry points (transfer.cpp) and their
-// gfx950 kernels (transfer.hip): history export, the two history imports, the resolver's iops
-// sample and the read versions of a batch.  Not part of the public C-ABI; the detect pipeline's
-// interface is engine.h.
+// gfx950 kernels (transfer.hip): history export, the history digests, split keys, the two history
+// imports, the resolver's iops sample and the read versions of a batch.  Not part of the public
+// C-ABI; the detect pipeline's interface is engine.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -47,6 +47,44 @@ void launch_export(hipStream_t s, const ExportArgs& a, const MaxLevels& basem, u
 enum DigestWord { kDwSum0 = 6, kDwSum1 = 7 };
 static_assert((int)kDwSum1 < (int)kXwWords && (int)kDwSum0 > (int)kXwScan, "the digest's sums lie in the export's spare words");
 void launch_export_digest(hipStream_t s, const ExportArgs& a, const MaxLevels& basem, int mode);
+
+// ---- partitioned digest (fdbcs_history_digest_ranges): K ranges between ascending bounds in one pass
+// over the span they cover.  Edge e of the partition is a bound, or with an open end "below every
+// key" (edge 0) or "past every key" (edge K); range i lies between edges i and i + 1.  The ExportArgs
+// are the digest's, with lo / hi the first / last bound (absent at an open end); of its words only
+// kXwLo, kXwHi, kXwHeader and the error word are used.
+enum DigestRangeWord { kDrN, kDrBytes, kDrHeader, kDrSum0, kDrSum1, kDrWords };
+struct DigestRangesArgs {
+    int32_t n_bounds, open_lo, open_hi;
+    int64_t K;               // ranges: n_bounds - 1 + open_lo + open_hi
+    const uint8_t* bytes;    // the bounds' bytes as given (8-byte aligned, kTailSlack readable bytes past them)
+    const int64_t* offsets;  // [n_bounds + 1]
+    int64_t* lt;             // [K + 1] per edge: stream elements below it
+    int64_t* le;             // [K + 1] per edge: stream elements at or below it
+    int64_t* out;            // [K][kDrWords], zeroed before the launches
+};
+// k_digest_ranges_bounds, the export's first three launches, k_export_digest_ranges.
+void launch_export_digest_ranges(hipStream_t s, const ExportArgs& a, const DigestRangesArgs& r, const MaxLevels& basem,
+                                 int mode);
+
+// ---- split keys (fdbcs_history_split_keys): boundary keys of one tier at evenly spaced positions
+// inside (lo, hi).  Reads both tiers, writes only the arrays below.
+enum SplitWord { kSwN, kSwBytes, kSwTier, kSwFirst, kSwCount, kSwError /* int */, kSwWords = 8 };
+struct SplitArgs {
+    Hist base, delta;
+    const uint8_t* htail;
+    int64_t nb, nd;
+    int32_t has_lo, has_hi;
+    DKey lo, hi;
+    const uint8_t* btail;  // their tails
+    int64_t want;          // keys asked for
+    int64_t* words;        // [kSwWords] SplitWord, zeroed before the launches
+    int64_t* offsets;      // [want + 1]
+    uint8_t* bytes;        // sized by the host from kSwBytes, between the two launches
+    int64_t bytes_cap;
+};
+void launch_split_plan(hipStream_t s, const SplitArgs& a);
+void launch_split_gather(hipStream_t s, const SplitArgs& a, int64_t n);
 
 // ---- history import (fdbcs_history_import / fdbcs_history_import_pending): folds an exported range
 // into both tiers, H'(k) = max(H(k), I(k)) over [lo, hi).  Reads the current buffers, writes only

@@ -1,8 +1,8 @@
-// transfer.hip — gfx950 kernels of the maintenance side of the engine: history export, the two
-// history imports, the resolver's iops sample and the read versions of a batch.  They run on an
-// idle set or off the detect stream (transfer.cpp); the detect pipeline's kernels are in
-// kernels.hip and call nothing here.  The searches both sides use are in search.h, the look-back
-// scan in scan.h.
+// transfer.hip — gfx950 kernels of the maintenance side of the engine: history export, the history
+// digest and its partitioned form, split keys, the two history imports, the resolver's iops sample
+// and the read versions of a batch.  They run on an idle set or off the detect stream
+// (transfer.cpp); the detect pipeline's kernels are in kernels.hip and call nothing here.  The
+// searches both sides use are in search.h, the look-back scan in scan.h.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 
@@ -253,6 +253,71 @@ __device__ __forceinline__ uint64_t digest_mix(uint64_t z) {
 constexpr uint64_t kDigestG = 0x9E3779B97F4A7C15ull;
 constexpr uint64_t kDigestS0 = 0x243F6A8885A308D3ull, kDigestS1 = 0x13198A2E03707344ull;
 
+// One kept element's terms (k_export_digest, k_export_digest_ranges): e is the element's index in the
+// tile export_resolve_tile resolved; acc counts kept, key bytes, sum[0], sum[1].
+__device__ __forceinline__ void digest_element(const ExportArgs& a, const int64_t* s_val, const int64_t* s_src, int e,
+                                               uint64_t (&acc)[4]) {
+    const int64_t src = s_src[e];
+    const Hist& h = src >= 0 ? a.base : a.delta;
+    const int64_t p = src >= 0 ? src : ~src;
+    const ulonglong2 key = h.key[p];
+    const uint2 lt = h.lt[p];
+    const uint32_t len = lt.x, nw = (len + 7u) >> 3;
+    uint64_t h0 = digest_mix(kDigestS0 + len), h1 = digest_mix(kDigestS1 + len);
+    // the prefix words are the big-endian words of the definition, zero past the key
+    if (nw > 0u) h0 = digest_mix((h0 ^ key.x) + kDigestG), h1 = digest_mix((h1 ^ key.x) + kDigestG);
+    if (nw > 1u) h0 = digest_mix((h0 ^ key.y) + kDigestG), h1 = digest_mix((h1 ^ key.y) + kDigestG);
+    if (nw > 2u) {
+        // tail words hold the key's bytes lowest first; what the last one holds past the key is not read
+        const uint64_t* tw = (const uint64_t*)hist_tail(a.htail, lt.y);
+        const uint32_t last = nw - 3u, used = len & 7u;
+        for (uint32_t q = 0; q <= last; q++) {
+            uint64_t w = __builtin_bswap64(tw[q]);
+            if (q == last && used) w &= ~0ull << (64u - 8u * used);
+            h0 = digest_mix((h0 ^ w) + kDigestG);
+            h1 = digest_mix((h1 ^ w) + kDigestG);
+        }
+    }
+    const uint64_t v = (uint64_t)s_val[e + 1];
+    acc[0] += 1;
+    acc[1] += len;
+    acc[2] += digest_mix((h0 ^ v) + kDigestG);
+    acc[3] += digest_mix((h1 ^ v) + kDigestG);
+}
+
+// A wave's totals of four terms, in every lane.
+__device__ __forceinline__ void digest_wave_sum(uint64_t (&acc)[4]) {
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        unsigned long long x = acc[c];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+        acc[c] = x;
+    }
+}
+
+// The workgroup's totals added to words[w0 .. w3] (kept, key bytes, sum[0], sum[1]): wave, then
+// workgroup, then one atomic per total.  The whole workgroup calls it.
+__device__ __forceinline__ void digest_tile_add(uint64_t (&acc)[4], uint64_t (&s_part)[kScanThreads / 64][4],
+                                                int64_t* words, int w0, int w1, int w2, int w3) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    digest_wave_sum(acc);
+    if (lane == 0) {
+#pragma unroll
+        for (int c = 0; c < 4; c++) s_part[wid][c] = acc[c];
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        uint64_t x = 0, kept = 0;
+#pragma unroll
+        for (int q = 0; q < kScanThreads / 64; q++) x += s_part[q][threadIdx.x], kept += s_part[q][0];
+        if (kept != 0) {  // a tile that kept nothing adds nothing
+            const int word = threadIdx.x == 0 ? w0 : threadIdx.x == 1 ? w1 : threadIdx.x == 2 ? w2 : w3;
+            atomicAdd((unsigned long long*)&words[word], (unsigned long long)x);
+        }
+    }
+}
+
 __global__ __launch_bounds__(kScanThreads) void k_export_digest(ExportArgs a) {
     __shared__ int64_t s_pos[kExpWin];
     __shared__ int64_t s_val[kScanTile + 1];
@@ -270,50 +335,154 @@ __global__ __launch_bounds__(kScanThreads) void k_export_digest(ExportArgs a) {
     for (int k = 0; k < kScanPer; k++) {
         const int e = k * kScanThreads + threadIdx.x;
         if (e >= cnt || s_val[e + 1] == s_val[e]) continue;
-        const int64_t src = s_src[e];
-        const Hist& h = src >= 0 ? a.base : a.delta;
-        const int64_t p = src >= 0 ? src : ~src;
-        const ulonglong2 key = h.key[p];
-        const uint2 lt = h.lt[p];
-        const uint32_t len = lt.x, nw = (len + 7u) >> 3;
-        uint64_t h0 = digest_mix(kDigestS0 + len), h1 = digest_mix(kDigestS1 + len);
-        // the prefix words are the big-endian words of the definition, zero past the key
-        if (nw > 0u) h0 = digest_mix((h0 ^ key.x) + kDigestG), h1 = digest_mix((h1 ^ key.x) + kDigestG);
-        if (nw > 1u) h0 = digest_mix((h0 ^ key.y) + kDigestG), h1 = digest_mix((h1 ^ key.y) + kDigestG);
-        if (nw > 2u) {
-            // tail words hold the key's bytes lowest first; what the last one holds past the key is not read
-            const uint64_t* tw = (const uint64_t*)hist_tail(a.htail, lt.y);
-            const uint32_t last = nw - 3u, used = len & 7u;
-            for (uint32_t q = 0; q <= last; q++) {
-                uint64_t w = __builtin_bswap64(tw[q]);
-                if (q == last && used) w &= ~0ull << (64u - 8u * used);
-                h0 = digest_mix((h0 ^ w) + kDigestG);
-                h1 = digest_mix((h1 ^ w) + kDigestG);
+        digest_element(a, s_val, s_src, e, acc);
+    }
+    digest_tile_add(acc, s_part, a.words, kXwN, kXwBytes, kDwSum0, kDwSum1);
+}
+
+// ---- partitioned digest (fdbcs_history_digest_ranges; the definition is in include/fdb_conflict_set.h)
+//
+// K ranges between ascending bounds, digested in one pass over the span they cover.  The canonical
+// elements of range i are the canonical elements of the whole span that lie strictly between its two
+// bounds, and "H_f changes here" is a property of an element and its predecessor in the stream, so the
+// tiles, their resolve step and the keep rule are the single digest's; only where a kept element's
+// terms are added differs.  With edge e the e-th bound (edge 0 below every key with an open low end,
+// edge K past every key with an open high end):
+//   k_digest_ranges_bounds  two lanes per bound (base, delta): the bound is normalized from its bytes
+//                    where it is searched, lt[e] / le[e] = stream elements below / at or below it
+//                    (plain binary searches over full keys), and range e's header, the clamped value
+//                    of element le[e] - 1 (k_export_bounds' rule), goes into its result block.
+//   launch_export_head      as it stands, over (first bound, last bound): the span's words, d_pos /
+//                    d_val and the tile starts.
+//   k_export_digest_ranges  range i owns the stream positions [le[i], lt[i + 1]); elements in
+//                    [lt[i], le[i]) equal a bound and belong to no range.  A workgroup looks up the
+//                    bins of its first and last element once; when they agree it reduces as
+//                    k_export_digest does, into the bin's block.  Otherwise every element finds its
+//                    bin among the tile's (positions ascend, so bins do), a wave whose elements share
+//                    one reduces by shuffles and adds once, and only a wave that straddles a bound
+//                    adds per element.
+
+__device__ __forceinline__ void ranges_bound_key(const DigestRangesArgs& r, int64_t j, DKey& q) {
+    const int64_t o = r.offsets[j];
+    const uint32_t len = (uint32_t)(r.offsets[j + 1] - o);
+    const uint8_t* p = r.bytes + o;
+    uint64_t w0 = len ? load8_unaligned(p) : 0ull, w1 = len > 8u ? load8_unaligned(p + 8) : 0ull;
+    if (len < 8u) w0 &= (1ull << (8u * len)) - 1ull;
+    if (len < 16u) w1 &= len > 8u ? (1ull << (8u * (len - 8u))) - 1ull : 0ull;
+    // the first key byte is the lowest of the loaded word and the highest of the prefix word
+    q.hi = __builtin_bswap64(w0);
+    q.lo = __builtin_bswap64(w1);
+    q.len = len;
+    q.tail = (uint32_t)(o + 16);  // bytes [16, len) where they lie (tail_cmp reads at any alignment)
+}
+
+__global__ __launch_bounds__(kBlock) void k_digest_ranges_bounds(ExportArgs a, DigestRangesArgs r) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t j = g >> 1;
+    const int tier = (int)(g & 1);  // 0 base, 1 delta
+    const bool live = j < r.n_bounds;
+    int64_t lt = 0, le = 0;
+    if (live) {
+        DKey q;
+        ranges_bound_key(r, j, q);
+        const Hist& h = tier ? a.delta : a.base;
+        const int64_t n = tier ? a.nd : a.nb;
+        lt = tier_bounds_lane(tier, a.base, a.nb, a.delta, a.nd, a.htail, true, true, false,
+                              [&](bool, DKey& k, const uint8_t*& t) {
+                                  k = q;
+                                  t = r.bytes;
+                              });
+        // a tier's keys ascend strictly: at most one equals the bound
+        le = lt + (lt < n && hist_cmp(h, lt, a.htail, q, r.bytes) == 0 ? 1 : 0);
+    }
+    const int64_t dlt = __shfl_xor(lt, 1, 64), dle = __shfl_xor(le, 1, 64);  // the delta lane's to the base lane
+    if (live && tier == 0) {
+        const int64_t e = j + r.open_lo;
+        r.lt[e] = lt + dlt;
+        r.le[e] = le + dle;
+        if (e < r.K) {  // H_f at the bound: the last boundary at or below it, the delta's unless a hole
+            int64_t h = a.hdr;
+            if (le > 0) h = a.base.ver[le - 1];
+            if (dle > 0) {
+                const int64_t dv = a.delta.ver[dle - 1];
+                if (dv != kHole) h = dv;
             }
+            r.out[e * kDrWords + kDrHeader] = export_clamp(h, a.floor);
         }
-        const uint64_t v = (uint64_t)s_val[e + 1];
-        acc[0] += 1;
-        acc[1] += len;
-        acc[2] += digest_mix((h0 ^ v) + kDigestG);
-        acc[3] += digest_mix((h1 ^ v) + kDigestG);
     }
-    // wave, then workgroup, then one atomic per total
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-        unsigned long long x = acc[c];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-        if (lane == 0) s_part[wid][c] = x;
+    if (g == 0) {
+        if (r.open_lo) {
+            r.lt[0] = r.le[0] = 0;
+            r.out[kDrHeader] = export_clamp(a.hdr, a.floor);
+        }
+        if (r.open_hi) r.lt[r.K] = r.le[r.K] = a.nb + a.nd;
     }
+}
+
+// The range that owns stream position p among edges [e_lo, e_hi): the last whose le is at or below p
+// (e_lo - 1 if none).
+__device__ __forceinline__ int64_t ranges_bin(const DigestRangesArgs& r, int64_t e_lo, int64_t e_hi, int64_t p) {
+    return first_false<int64_t>(e_lo, e_hi, [&](int64_t e) { return r.le[e] <= p; }) - 1;
+}
+
+__global__ __launch_bounds__(kScanThreads) void k_export_digest_ranges(ExportArgs a, DigestRangesArgs r) {
+    __shared__ int64_t s_pos[kExpWin];
+    __shared__ int64_t s_val[kScanTile + 1];
+    __shared__ int64_t s_src[kScanTile];
+    __shared__ uint64_t s_part[kScanThreads / 64][4];
+    __shared__ int64_t s_bin[2];
+    const int64_t m_lo = a.words[kXwLo], n = a.words[kXwHi] - m_lo;
+    const int64_t tile = blockIdx.x;
+    const int64_t ntiles = n > 0 ? (n + kScanTile - 1) / kScanTile : 1;
+    if (tile >= ntiles) return;  // spare tile of the launch sized by both tiers
+    export_resolve_tile(a, tile, m_lo, n, s_pos, s_val, s_src, (int*)&a.words[kXwScan] + 1);
+    const int64_t rest = n - tile * kScanTile;
+    const int cnt = (int)(rest < kScanTile ? rest : kScanTile);
+    if (cnt <= 0) return;  // an empty span: the headers are all there is
+    const int64_t p0 = m_lo + tile * kScanTile;  // the tile's first stream position
+    if (threadIdx.x < 2) s_bin[threadIdx.x] = ranges_bin(r, 0, r.K, threadIdx.x ? p0 + cnt - 1 : p0);
     __syncthreads();
-    if (threadIdx.x < 4) {
-        uint64_t x = 0, kept = 0;
+    const int64_t b0 = s_bin[0], b1 = s_bin[1];
+    if (b0 < 0 || b1 < b0) {  // the span starts below the first range: the two bound searches disagree
+        if (threadIdx.x == 0) atomicOr((int*)&a.words[kXwScan] + 1, 4);
+        return;
+    }
+    if (b0 == b1) {  // one range's tile: the single digest's reduction into that range's block
+        const int64_t end = r.lt[b0 + 1] - p0;  // elements from here on equal the next bound
+        uint64_t acc[4] = {0, 0, 0, 0};
 #pragma unroll
-        for (int q = 0; q < kScanThreads / 64; q++) x += s_part[q][threadIdx.x], kept += s_part[q][0];
-        if (kept != 0) {  // a tile that kept nothing adds nothing
-            const int word = threadIdx.x == 0 ? kXwN : threadIdx.x == 1 ? kXwBytes : threadIdx.x == 2 ? kDwSum0 : kDwSum1;
-            atomicAdd((unsigned long long*)&a.words[word], (unsigned long long)x);
+        for (int k = 0; k < kScanPer; k++) {
+            const int e = k * kScanThreads + threadIdx.x;
+            if (e >= cnt || e >= end || s_val[e + 1] == s_val[e]) continue;
+            digest_element(a, s_val, s_src, e, acc);
+        }
+        digest_tile_add(acc, s_part, r.out + b0 * kDrWords, kDrN, kDrBytes, kDrSum0, kDrSum1);
+        return;
+    }
+    const int lane = threadIdx.x & 63;
+    for (int k = 0; k < kScanPer; k++) {  // every lane takes every round: the shuffles need whole waves
+        const int e = k * kScanThreads + threadIdx.x;
+        const bool in = e < cnt;
+        const int64_t bin = in ? ranges_bin(r, b0, b1 + 1, p0 + e) : -1;
+        uint64_t t[4] = {0, 0, 0, 0};
+        const bool adds = in && bin >= b0 && s_val[e + 1] != s_val[e] && p0 + e < r.lt[bin + 1];
+        if (adds) digest_element(a, s_val, s_src, e, t);
+        const int64_t wb = __shfl(bin, 0, 64);  // elements ascend with the lane: lane 0 is outside only if all are
+        if (__all(!in || bin == wb)) {
+            digest_wave_sum(t);
+            if (lane == 0 && t[0] != 0) {
+                unsigned long long* o = (unsigned long long*)(r.out + wb * kDrWords);
+                atomicAdd(&o[kDrN], (unsigned long long)t[0]);
+                atomicAdd(&o[kDrBytes], (unsigned long long)t[1]);
+                atomicAdd(&o[kDrSum0], (unsigned long long)t[2]);
+                atomicAdd(&o[kDrSum1], (unsigned long long)t[3]);
+            }
+        } else if (adds) {
+            unsigned long long* o = (unsigned long long*)(r.out + bin * kDrWords);
+            atomicAdd(&o[kDrN], (unsigned long long)t[0]);
+            atomicAdd(&o[kDrBytes], (unsigned long long)t[1]);
+            atomicAdd(&o[kDrSum0], (unsigned long long)t[2]);
+            atomicAdd(&o[kDrSum1], (unsigned long long)t[3]);
         }
     }
 }
@@ -346,6 +515,98 @@ void launch_export(hipStream_t s, const ExportArgs& a, const MaxLevels& basem, u
 void launch_export_digest(hipStream_t s, const ExportArgs& a, const MaxLevels& basem, int mode) {
     const int64_t tiles = launch_export_head(s, a, basem, mode);
     fdb_launch(k_export_digest, dim3((unsigned)tiles), dim3(kScanThreads), 0, s, a);
+}
+
+void launch_export_digest_ranges(hipStream_t s, const ExportArgs& a, const DigestRangesArgs& r, const MaxLevels& basem,
+                                 int mode) {
+    const int64_t lanes = std::max<int64_t>(1, 2 * (int64_t)r.n_bounds);
+    fdb_launch(k_digest_ranges_bounds, dim3((unsigned)((lanes + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, a, r);
+    const int64_t tiles = launch_export_head(s, a, basem, mode);
+    fdb_launch(k_export_digest_ranges, dim3((unsigned)tiles), dim3(kScanThreads), 0, s, a, r);
+}
+
+// ---- split keys (fdbcs_history_split_keys; the definition is in include/fdb_conflict_set.h)
+//
+// Up to `want` boundary keys strictly inside (lo, hi), taken at evenly spaced positions of the tier
+// that holds more boundaries there.  Read-only; two launches with a host read between them, which
+// sizes the key buffer:
+//   k_split_plan    one workgroup: the bounds' positions in both tiers (k_export_bounds' searches), the
+//                   tier, the count n and the picked boundaries' byte offsets (each thread sums the
+//                   lengths of a contiguous share of the picks, the shares are scanned in LDS)
+//   k_split_gather  one lane per picked boundary: its original bytes by export_put_key
+
+// Pick k of n among c boundaries: the middle of the k-th of n equal shares (strictly ascending for n <= c).
+__device__ __forceinline__ int64_t split_pick(int64_t k, int64_t n, int64_t c) { return ((2 * k + 1) * c) / (2 * n); }
+
+__global__ __launch_bounds__(kBlock) void k_split_plan(SplitArgs a) {
+    __shared__ int64_t r[4];  // boundaries <= lo in base, delta; boundaries < hi in base, delta
+    __shared__ int64_t s_sum[kBlock];
+    const int t = threadIdx.x;
+    if (t < 4)
+        r[t] = tier_bounds_lane(t, a.base, a.nb, a.delta, a.nd, a.htail, a.has_lo, a.has_hi, true,
+                                [&](bool is_hi, DKey& q, const uint8_t*& qtail) {
+                                    q = is_hi ? a.hi : a.lo;
+                                    qtail = a.btail;
+                                });
+    __syncthreads();
+    const int64_t cb = r[2] > r[0] ? r[2] - r[0] : 0, cd = r[3] > r[1] ? r[3] - r[1] : 0;
+    const int tier = cd > cb ? 1 : 0;
+    const int64_t first = tier ? r[1] : r[0], c = tier ? cd : cb;
+    const int64_t n = a.want < c ? a.want : c;
+    const Hist& h = tier ? a.delta : a.base;
+    // thread t owns picks [k0, k1)
+    const int64_t per = (n + kBlock - 1) / kBlock;
+    const int64_t k0 = t * per < n ? t * per : n, k1 = k0 + per < n ? k0 + per : n;
+    int64_t sum = 0;
+    for (int64_t k = k0; k < k1; k++) sum += h.lt[first + split_pick(k, n, c)].x;
+    s_sum[t] = sum;
+    __syncthreads();
+    if (t == 0) {
+        int64_t run = 0;
+        for (int q = 0; q < kBlock; q++) {
+            const int64_t x = s_sum[q];
+            s_sum[q] = run;
+            run += x;
+        }
+        a.words[kSwN] = n;
+        a.words[kSwBytes] = run;
+        a.words[kSwTier] = tier;
+        a.words[kSwFirst] = first;
+        a.words[kSwCount] = c;
+        a.offsets[n] = run;
+    }
+    __syncthreads();
+    int64_t off = s_sum[t];
+    for (int64_t k = k0; k < k1; k++) {
+        a.offsets[k] = off;
+        off += h.lt[first + split_pick(k, n, c)].x;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_split_gather(SplitArgs a) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t n = a.words[kSwN], c = a.words[kSwCount];
+    if (k >= n || k >= a.want) return;
+    const Hist& h = a.words[kSwTier] ? a.delta : a.base;
+    const int64_t p = a.words[kSwFirst] + split_pick(k, n, c);
+    const ulonglong2 key = h.key[p];
+    const uint2 lt = h.lt[p];
+    const int64_t P = a.offsets[k];
+    if (P < 0 || P + (int64_t)lt.x > a.bytes_cap) {  // never past the buffer the host sized from the plan
+        atomicOr((int*)&a.words[kSwError], 8);
+        return;
+    }
+    // the prefix words are big-endian: swapped back, the key's first byte is the lowest
+    const uint64_t w0 = __builtin_bswap64(key.x), w1 = __builtin_bswap64(key.y);
+    const uint64_t* tw = (const uint64_t*)hist_tail(a.htail, lt.x > 16u ? lt.y : 0u);
+    export_put_key(a.bytes + P, lt.x, (lt.x + 7u) >> 3,
+                   [&](uint32_t q) { return q == 0u ? w0 : q == 1u ? w1 : tw[q - 2u]; });
+}
+
+void launch_split_plan(hipStream_t s, const SplitArgs& a) { fdb_launch(k_split_plan, dim3(1), dim3(kBlock), 0, s, a); }
+
+void launch_split_gather(hipStream_t s, const SplitArgs& a, int64_t n) {
+    if (n > 0) fdb_launch(k_split_gather, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, a);
 }
 
 // ------------------------------------------------------------------ iops sample

@@ -225,6 +225,63 @@ int fdbcs_history_digest_arrays(int64_t n, const uint8_t* key_bytes, const int64
                                 const int64_t* versions, int64_t header_version, fdbcs_digest* out);
 /* Diagnostics: device time of the last digest's kernels and host time of the whole call (ms). */
 int fdbcs_history_digest_timing(fdbcs_conflict_set* cs, double* ms_kernels, double* ms_host);
+/* The digests of many key ranges of this set's canonical history in one pass on the device: what two
+ * holders whose digests differ exchange to find out where (one call per level of a K-way bisection
+ * instead of K), and the digest of a checkpoint chunk by chunk.  No reference counterpart.
+ * The bounds s_0 <= s_1 <= ... <= s_{n_bounds-1} are host bytes in the export's key layout
+ * (bound_offsets [n_bounds + 1], bound_offsets[0] = 0).  They define, in this order, the range from
+ * below every key to s_0 if open_lo is set, [s_i, s_{i+1}) for each neighbouring pair, and the range
+ * from the last bound to the end if open_hi is set: K = n_bounds - 1 + open_lo + open_hi ranges
+ * (n_bounds = 0 with both ends open is the whole history).  out[i] equals, field for field, what
+ * fdbcs_history_digest returns for range i under the same floor_version (n, key_bytes, header_version
+ * = H_f at the range's lower bound, both sums); equal neighbouring bounds give n = 0 and the header,
+ * as lo == hi does there.  A canonical boundary equal to an interior bound belongs to no range (it
+ * is the header of the range it opens), so the whole span's n is the sum of the ranges' n plus the
+ * interior bounds that are canonical boundaries.
+ * One pass over the stream of both tiers whatever K is: the bounds' stream positions are found by one
+ * launch (long bounds included), the tiles are the single digest's.  Scratch grows with K and the
+ * tile count only, in buffers the set owns.  The set is not modified and a pending export result
+ * stays pending and readable.  FDBCS_E_STATE with batches in flight; FDBCS_E_INVALID for a NULL
+ * handle or out, n_bounds < 0, K < 1, bound_offsets[0] != 0, decreasing offsets or decreasing
+ * bounds; FDBCS_E_NOMEM for K > 65536 (the bound of the routing map's ranges).
+ * fdbcs_history_digest_timing reports the last call of either kind. */
+int fdbcs_history_digest_ranges(fdbcs_conflict_set* cs, int32_t n_bounds, const uint8_t* bound_bytes,
+                                const int64_t* bound_offsets /* [n_bounds + 1] */, int open_lo, int open_hi,
+                                int64_t floor_version, fdbcs_digest* out /* [K] */);
+/* Host only (no device is touched): the same partition over arrays in the layout of
+ * fdbcs_load_history, read as given (nothing is canonicalised).  The arrays' keys must ascend, as a
+ * canonical history's do; this is not checked.  Range i's header_version is the version of the last
+ * boundary <= its lower bound (header_version if there is none, or below an open low end), its
+ * boundaries are those strictly between its bounds.  On the arrays fdbcs_history_export_read returns
+ * for a span it gives what fdbcs_history_digest_ranges gives for the set over the same bounds: how a
+ * checkpoint file or a model's canonical form is digested chunk by chunk.  Validation as
+ * fdbcs_history_digest_arrays and, for the bounds, as fdbcs_history_digest_ranges. */
+int fdbcs_history_digest_arrays_ranges(int64_t n, const uint8_t* key_bytes, const int64_t* key_offsets,
+                                       const int64_t* versions, int64_t header_version, int32_t n_bounds,
+                                       const uint8_t* bound_bytes, const int64_t* bound_offsets, int open_lo,
+                                       int open_hi, fdbcs_digest* out /* [K] */);
+/* Up to `want` boundary keys strictly inside (lo, hi), strictly ascending, in original bytes: bounds
+ * to bisect a range on without an export.  They are taken at evenly spaced positions among the
+ * boundaries inside the range of whichever tier (base or delta) holds more of them there: fewer than
+ * `want` when that tier holds fewer, none when the range holds no boundary.
+ * The keys depend on how the history is split between the tiers and on when GC ran: they are NOT
+ * canonical, and two sets with equal canonical histories may return different keys.  They serve only
+ * as bounds (fdbcs_history_digest_ranges accepts any ascending keys); both sides of a comparison use
+ * the keys of one side.
+ * Two calls, as the export: this one runs on the device and reports the sizes, the read copies the
+ * result out (key_offsets [n + 1]) and releases it; FDBCS_E_NOMEM from the read for a capacity too
+ * small (the result stays), FDBCS_E_STATE when none is pending.  The result is a copy: it stays
+ * readable whatever the set does next, until it is read or another call replaces it.  The set is
+ * not modified and a pending export result stays pending and readable.  FDBCS_E_STATE with batches
+ * in flight, FDBCS_E_INVALID for lo > hi, want < 0 or a NULL argument, FDBCS_E_NOMEM for
+ * want > 65536. */
+int fdbcs_history_split_keys(fdbcs_conflict_set* cs, const uint8_t* lo_key, int32_t lo_len, /* lo_len < 0: no lower bound */
+                             const uint8_t* hi_key, int32_t hi_len,                       /* hi_len < 0: no upper bound */
+                             int32_t want, int64_t* n_out, int64_t* key_bytes_out);
+int fdbcs_history_split_keys_read(fdbcs_conflict_set* cs, uint8_t* key_bytes, int64_t key_bytes_cap,
+                                  int64_t* key_offsets, int64_t cap);
+/* Diagnostics: device time of the last fdbcs_history_split_keys' kernels and host time of the call (ms). */
+int fdbcs_history_split_keys_timing(fdbcs_conflict_set* cs, double* ms_kernels, double* ms_host);
 /* Merge an exported history range into a live set, on the device: the receiving half of a range
  * hand-over.  No reference counterpart.  The arrays are in the layout of fdbcs_load_history and the
  * export and describe a step function I: I(k) is the version of the last imported boundary <= k,

@@ -16,7 +16,8 @@ not when a later read happens to meet it.
 
 --digest-every K (default off) also feeds the semantic oracle and compares, every K batches, the
 engine's digest of its state (ConflictSet.digest at floor = oldest version: no export, no copy) with
-digest_arrays of the canonical form of the oracle's step function.
+digest_arrays of the canonical form of the oracle's step function.  When they differ, the first
+diverging key range (locate_divergence: digest_ranges against digest_arrays_ranges) is printed too.
 
 --import-every K (default off; implies --state-every 1 unless given) merges, every K batches, a
 random key range of a second set's history into the engine (ConflictSet.merge_history, every other
@@ -174,7 +175,12 @@ def one(seed, state_every=0, import_every=0, import_into="base", digest_every=0,
                 got = e.cs.digest()
                 DIGESTS[0] += 1
                 if got != want:
-                    return f"digest batch {i}: {got}, oracle {want}"
+                    # where: bisect the engine's state against the oracle's canonical arrays
+                    arr = pack(canon(keys, hv, hdr, so.oldest_version))
+                    where = C.locate_divergence(lambda b, ol, oh: e.cs.digest_ranges(b, None, ol, oh),
+                                                lambda b, ol, oh: C.digest_arrays_ranges(*arr, b, ol, oh),
+                                                e.cs.split_keys, leaf=4)
+                    return f"digest batch {i}: {got}, oracle {want}; first diverging range {where[0] if where else None}"
             if read_versions_every and (i + 1) % read_versions_every == 0:
                 keys, hv = so.dump_history()
                 pool = sorted(set(keys) | {pb.key(k) for k in range(len(pb.key_offsets) - 1)} | {b""})
