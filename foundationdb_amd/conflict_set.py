@@ -100,6 +100,10 @@ class Stats(ctypes.Structure):
         ("host_ms_add", ctypes.c_double),
         ("added_txns", ctypes.c_int64),
         ("x_launches_skipped", ctypes.c_int64),
+        ("x_edge_free_unskipped", ctypes.c_int64),
+        ("x_held", ctypes.c_int64),
+        ("x_forced", ctypes.c_int64),
+        ("x_flushed", ctypes.c_int64),
     ]
 
     def as_dict(self):

@@ -54,7 +54,7 @@ int ensure_scan_arena(fdbcs_conflict_set* cs) {
     return FDBCS_OK;
 }
 
-int flush_pending(fdbcs_conflict_set* cs);
+int flush_pending(fdbcs_conflict_set* cs, const fdbcs_batch* upto = nullptr);
 
 // Both streams idle (before reallocating anything either stage uses).
 int sync_all(fdbcs_conflict_set* cs) {
@@ -680,37 +680,79 @@ void worker_stop(fdbcs_conflict_set* cs) {
     cs->worker.join();
 }
 
-// The skip groups of batch b's X half at its replay: the kGroupEdges launches are left out once
-// b's stage A has completed (ev_a) and its edge scan told the host (Work::hedge) that b has no
-// candidate edge; otherwise (stage A still running, or not tracked) everything is issued.
-uint8_t x_skip(fdbcs_conflict_set* cs, const fdbcs_batch* b) {
-    if (!b || !cs->skip_edges || !cs->hedge.p) return 0;
+// What the host knows of batch b's candidate edges: the word its edge scan's finish wrote
+// (Work::hedge: {the batch's sequence number, any candidate edge}; the count first, a system-scope
+// fence, then the tag).  Only a word tagged with b's own sequence number speaks for b: until the
+// scan has run, the word is still that of the workspace's previous user.
+// -1: not known yet (or not tracked), 0: no candidate edge, 1: some.
+int x_edges(const fdbcs_conflict_set* cs, const fdbcs_batch* b) {
+    if (!b || !cs->skip_edges || !cs->hedge.p) return -1;
     const volatile uint32_t* h = (const volatile uint32_t*)((char*)cs->hedge.p + 64 * b->wp);
-    if (h[0] != b->seq) return 0;  // (cheap test first: no runtime call when the scan is not done)
-    if (hipEventQuery(cs->ev_a[b->wp]) != hipSuccess) return 0;
+    if (h[0] != b->seq) return -1;
     std::atomic_thread_fence(std::memory_order_acquire);
-    return h[1] == 0u ? kGroupEdges : 0;
+    return h[1] == 0u ? 0 : 1;
 }
 
-int flush_pending(fdbcs_conflict_set* cs) {
-    if (int rc = worker_wait(cs)) return rc;  // stage A / check of the pending batch issued
-    if (!cs->pending_batch) return FDBCS_OK;
-    const uint8_t skip = x_skip(cs, cs->pending_batch);
-    const uint32_t pseq = cs->pending_batch->seq;
-    cs->pending_batch = nullptr;
-    int rc = FDBCS_OK;
+// The skip groups of batch b's X half at its replay: the kGroupEdges launches are left out once
+// b's edge scan told the host that b has no candidate edge; otherwise (scan not over, or not
+// tracked) everything is issued.
+uint8_t x_skip(const fdbcs_conflict_set* cs, const fdbcs_batch* b) { return x_edges(cs, b) == 0 ? kGroupEdges : 0; }
+
+// Is there nothing to gain from holding h's X half back another call?  So when its edge word has
+// arrived, when the word is not tracked, or when the list has no launch a count of 0 leaves out
+// (timed kernels are always issued).
+bool x_known(const fdbcs_conflict_set* cs, const fdbcs_conflict_set::Held& h) {
+    if (!cs->skip_edges || !cs->hedge.p || x_edges(cs, h.batch) >= 0) return true;
+    for (const LaunchList::Rec& r : h.x.recs)
+        if (r.kind == LaunchList::kKernel && (r.group & kGroupEdges)) return false;
+    return true;
+}
+
+// Batch b's recorded X half onto the batch-order stream, now.
+hipError_t issue_x(fdbcs_conflict_set* cs, fdbcs_batch* b, LaunchList& x) {
+    const uint8_t skip = x_skip(cs, b);
     const int64_t tx = cs->htrace ? mono_ns() : 0;
-    if (cs->pending_b.replay(cs->stream, skip, &cs->stats.x_launches_skipped) != hipSuccess) rc = FDBCS_E_DEVICE;
-    const int64_t ty = cs->htrace ? mono_ns() : 0;
-    cs->x_issued.fetch_add(1, std::memory_order_release);
-    if (cs->pending_y.replay(cs->pending_ys) != hipSuccess) rc = FDBCS_E_DEVICE;
-    if (cs->htrace) {
-        cs->htr[0].push_back({pseq, 'X', tx, ty});
-        cs->htr[0].push_back({pseq, 'Y', ty, mono_ns()});
+    const hipError_t e = x.replay(cs->stream, skip, &cs->stats.x_launches_skipped);
+    if (cs->htrace) cs->htr[0].push_back({b->seq, 'X', tx, mono_ns()});
+    // issued whole with launches a known count of 0 would have left out: too early if b is edge-free
+    b->x_unskipped = false;
+    if (!skip && cs->skip_edges && cs->hedge.p)
+        for (const LaunchList::Rec& r : x.recs)
+            if (r.kind == LaunchList::kKernel && (r.group & kGroupEdges)) b->x_unskipped = true;
+    x.clear();
+    return e;
+}
+
+// The held batches leave the front of the queue (n of them: their lists were issued or handed on).
+void drop_held(fdbcs_conflict_set* cs, int n) {
+    for (int k = n; k < cs->n_held; k++) std::swap(cs->held[k - n], cs->held[k]);
+    cs->n_held -= n;
+    for (int k = cs->n_held; k < kMaxHold; k++) cs->held[k].batch = nullptr;
+}
+
+// Issue the held stage-B lists, oldest first, up to and including batch `upto` (null: all of
+// them).  A batch that is not held needs nothing issued.
+int flush_pending(fdbcs_conflict_set* cs, const fdbcs_batch* upto) {
+    if (int rc = worker_wait(cs)) return rc;  // stage A / check of the held batches issued
+    int n = cs->n_held;
+    if (upto) {
+        n = 0;
+        for (int k = 0; k < cs->n_held; k++)
+            if (cs->held[k].batch == upto) n = k + 1;
     }
-    cs->b_issued.fetch_add(1, std::memory_order_release);
-    cs->pending_b.clear();
-    cs->pending_y.clear();
+    int rc = FDBCS_OK;
+    for (int k = 0; k < n; k++) {
+        fdbcs_conflict_set::Held& h = cs->held[k];
+        if (issue_x(cs, h.batch, h.x) != hipSuccess) rc = FDBCS_E_DEVICE;
+        cs->x_issued.fetch_add(1, std::memory_order_release);
+        const int64_t ty = cs->htrace ? mono_ns() : 0;
+        if (h.y.replay(h.ys) != hipSuccess) rc = FDBCS_E_DEVICE;
+        if (cs->htrace) cs->htr[0].push_back({h.batch->seq, 'Y', ty, mono_ns()});
+        cs->b_issued.fetch_add(1, std::memory_order_release);
+        h.y.clear();
+        cs->stats.x_flushed += 1;
+    }
+    drop_held(cs, n);
     return rc;
 }
 
@@ -970,6 +1012,7 @@ int fdbcs_load_history(fdbcs_conflict_set* cs, int64_t n, const uint8_t* key_byt
 int fdbcs_get_stats(fdbcs_conflict_set* cs, fdbcs_stats* out) {
     if (!cs || !out) return FDBCS_E_INVALID;
     *out = cs->stats;
+    out->x_held = cs->n_held;  // (a gauge: what is held now)
     return FDBCS_OK;
 }
 
@@ -2127,7 +2170,7 @@ static int record_stage_a(fdbcs_conflict_set* cs, fdbcs_batch* b, DetectPlan& p)
     if (b->state == 0 && (rc = do_upload(b, p.us))) return rc;
     if (hipEvent_t e = p.rec(kPhUpload, 2)) HIPOK(hipEventRecord(e, sa));
     RecordInto recording(cs->rec_a);
-    // workspace wp was last used by the batch before the previous one: its epilogue re-zeroed it.
+    // workspace wp was last used kNumWork batches ago: that batch's epilogue re-zeroed it.
     // ev_b[wp] is recorded by every batch's stage B, whatever its stream layout, so the query is
     // never answered by a stale or never-recorded event (a timing-level change with batches in
     // flight included).
@@ -2358,38 +2401,53 @@ static int submit_lists(fdbcs_conflict_set* cs, fdbcs_batch* b, DetectPlan& p) {
     hipStream_t s = p.s, sa = p.sa, ys = p.ys;
     int rc;
     if (p.threaded) {
-        // the helper issues this batch's stage A and check while this thread issues the
-        // previous batch's stage B; this batch's stage B waits for the next call (or a flush)
+        // the helper issues this batch's stage A and check while this thread issues the stage B
+        // of earlier batches; this batch's stage B is held for a later call (or a flush)
         if ((rc = worker_wait(cs))) return rc;
         std::swap(cs->work_a, la);
         std::swap(cs->work_c, lc);  // empty unless split
         cs->work_sa = sa;
         cs->work_a_seq = b->seq;
-        const bool prev = cs->pending_batch != nullptr;
-        if (prev) {  // the previous batch's Y to the helper, after the X this thread issues below
-            cs->work_y_seq = cs->pending_batch->seq;
-            std::swap(cs->work_y, cs->pending_y);
-            cs->work_ys = cs->pending_ys;
-            cs->work_need_x = cs->x_issued.load(std::memory_order_relaxed) + 1;
-            cs->work_y_batch = cs->pending_batch;
+        // Which held X halves go out now, oldest first: the batch of two calls ago whatever the
+        // host knows, the previous batch's once its edge word is there (x_known).  A split check
+        // goes out behind every Y recorded so far (it may wait on the ev_cmp one of them records),
+        // so under that layout nothing is held a second call.
+        int go = cs->n_held == kMaxHold ? 1 : 0;
+        cs->stats.x_forced += go;
+        while (go < cs->n_held && (p.split || x_known(cs, cs->held[go]))) go++;
+        // Two at one call: the older one's X and Y both from this thread, before the hand-over.  The
+        // newer one's X may wait on the older one's ev_b (its check reads the delta that Y leaves,
+        // when that batch compacted or no segments stand in for it), and a wait takes the event's
+        // last record: that Y must be issued before this X, not beside it by the helper.
+        while (go > 1) {
+            if (flush_pending(cs, cs->held[0].batch)) return FDBCS_E_DEVICE;
+            go--;
         }
-        cs->work_need_b = cs->b_recorded;  // every stage B recorded so far, batch i-1's included
+        fdbcs_batch* xb = nullptr;
+        if (go) {  // its Y half to the helper, after the X this thread issues below
+            fdbcs_conflict_set::Held& h = cs->held[0];
+            cs->work_y_seq = h.batch->seq;
+            std::swap(cs->work_y, h.y);
+            cs->work_ys = h.ys;
+            cs->work_y_batch = xb = h.batch;
+            std::swap(cs->go_x, h.x);  // (go_x: empty, kept in the set for its capacity)
+            cs->work_need_x = cs->x_issued.load(std::memory_order_relaxed) + 1;
+            drop_held(cs, 1);
+        }
+        // the check goes out once every stage B that is issued at this call is
+        cs->work_need_b = cs->b_recorded - (uint32_t)cs->n_held;
         worker_start_job(cs);
-        if (prev) {
-            fdbcs_batch* pb_ = cs->pending_batch;
-            cs->pending_batch = nullptr;
-            const int64_t tx = cs->htrace ? mono_ns() : 0;
-            const uint32_t pseq = pb_->seq;
-            hipError_t e = cs->pending_b.replay(s, x_skip(cs, pb_), &cs->stats.x_launches_skipped);
-            if (cs->htrace) cs->htr[0].push_back({pseq, 'X', tx, mono_ns()});
+        if (xb) {
+            const hipError_t e = issue_x(cs, xb, cs->go_x);
             cs->x_issued.fetch_add(1, std::memory_order_release);  // (the helper issues its Y)
             if (e != hipSuccess) return FDBCS_E_DEVICE;
         }
-        std::swap(cs->pending_b, lb);
-        std::swap(cs->pending_y, ly);
-        cs->pending_ys = ys;
+        fdbcs_conflict_set::Held& h = cs->held[cs->n_held++];
+        std::swap(h.x, lb);
+        std::swap(h.y, ly);
+        h.ys = ys;
+        h.batch = b;
         cs->b_recorded++;
-        cs->pending_batch = b;
     } else if (flush_pending(cs)) {
         return FDBCS_E_DEVICE;
     } else {
@@ -2439,6 +2497,9 @@ int fdbcs_batch_detect_async(fdbcs_batch* b, int64_t now, int64_t new_oldest_ver
     if ((rc = detect_admit(cs, b, p))) return rc;
     if ((rc = detect_bind_results(cs, b, p))) return rc;
     plan_layout(cs, b, p);
+    // a layout that issues from this thread alone holds nothing back: whatever an earlier layout
+    // left held goes out first, so that every event this batch's steps query has been recorded
+    if (!p.threaded && cs->n_held && (rc = flush_pending(cs))) return rc;
     cs->stats.host_ms_prepare += host_ms_since(p.t_begin);
     const auto t_rec = std::chrono::steady_clock::now();
     plan_views(cs, p);
@@ -2462,8 +2523,11 @@ int fdbcs_batch_detect_async(fdbcs_batch* b, int64_t now, int64_t new_oldest_ver
 static int wait_flag(fdbcs_conflict_set* cs, fdbcs_batch* b) {
     const int64_t tw0 = cs->htrace ? mono_ns() : 0;
     HIPOK(hipSetDevice(cs->device));
-    if (cs->pending_batch == b)  // its stage B still waits for the next detect: launch it now
-        if (int rc = flush_pending(cs)) return rc;
+    for (int k = 0; k < cs->n_held; k++)
+        if (cs->held[k].batch == b) {  // its stage B is still held: issue it now, behind every batch before it
+            if (int rc = flush_pending(cs, b)) return rc;
+            break;
+        }
     if (cs->work_y_batch == b)  // its Y is with the helper: issued (events and all) before reading them
         if (int rc = worker_wait(cs)) return rc;
     // the epilogue publishes b->seq; poll it, checking the streams for errors only every ~2 ms:
@@ -2610,6 +2674,9 @@ static int account_stats(fdbcs_conflict_set* cs, fdbcs_batch* b) {
         st.intra_edges += b->h_scal->intra_edges;
         st.intra_rounds += b->h_scal->intra_rounds;
     }
+    // an edge-free batch whose X half went out whole: the host issued it before the edge word came
+    if (b->x_unskipped && b->h_scal->intra_edges == 0) st.x_edge_free_unskipped += 1;
+    b->x_unskipped = false;
     // algorithmic bytes of the copy kernels (roofline.py): read every kept old boundary and
     // every inserted one (its key from the batch), write every boundary of the result, 32 B
     // each (16 B key, 8 B length/tail, 8 B version); kept + inserted = the result's size

@@ -247,9 +247,22 @@ struct BatchSlot;
 
 // ws[k] slots: ensure_workspace TAKEs [0, kWsTileSlot); then the copy-tile index and the scan arena.
 constexpr int kWsTileSlot = 54, kWsArenaSlot = 55;
-// Batch workspaces in rotation: stage A can run up to two batches ahead of stage B, so each
-// workspace is reused every third batch.
-constexpr int kNumWork = 3;
+// Batch workspaces in rotation: stage A of batch i starts once Y of batch i - kNumWork and X of
+// batch i - kNumWork + 1 are over, so it can run up to kNumWork - 1 batches ahead of stage B.
+// Eight: in a loop that keeps eight batches in flight the host issues A(i) when batch i - 8 is
+// done, so the ring never holds stage A back and its edge word reaches the host before X(i) has
+// to be issued (the depth's measurement: DESIGN.md §5, builds of 4, 6, 8 and 12 through
+// FDBCS_NUM_WORK, `profiles/x_tail_skip_ab.jsonl`).
+#ifndef FDBCS_NUM_WORK
+#define FDBCS_NUM_WORK 8
+#endif
+constexpr int kNumWork = FDBCS_NUM_WORK;
+// A held X half (kMaxHold below) is issued while the helper issues stage A of the batch two calls
+// later: that stage A waits on the events of the X half kNumWork - 1 batches back, which must
+// have been issued by an earlier call.
+static_assert(kNumWork >= 4, "the workspace ring must outlast the two-call hold of an X half");
+// Stage-B lists (X and the Y behind it) recorded and not yet issued: at most the last two batches'.
+constexpr int kMaxHold = 2;
 constexpr int kGcEveryCompactions = 4;  // removeBefore cadence of size-triggered compactions
 
 // FDBCS_HOST_TRACE=<path>: host-side spans of the pipeline (steady_clock ns, the clock rocprofv3
@@ -502,8 +515,9 @@ struct fdbcs_conflict_set {
     std::vector<std::unique_ptr<BatchSlot>> pool;  // staging slots of destroyed batches, reused by new ones
     // Two submitting threads (the default since round 4: C2 +3-10 % over five same-box A/Bs, C3 and
     // C4 unchanged; FDBCS_SUBMIT_THREAD=0 keeps one).  A helper thread issues stage A of batch i
-    // (and its base-tier check) while the calling thread issues stage B's X half of batch i-1,
-    // which waited for this call; the helper then issues that batch's Y half once X is out:
+    // (and its base-tier check) while the calling thread issues the held X halves that are due
+    // (batch i-2's, and batch i-1's once its edge word is known: `held`); the helper then issues
+    // each of those batches' Y half once its X is out:
     // kernel launches on two streams from two threads take about half the wall time of one
     // thread's (tools/threadbench.hip: 3.4 -> 1.85 us per launch).  The
     // check of batch i waits (host side) until stage B of batch i-1 is issued, because it may wait
@@ -516,7 +530,7 @@ struct fdbcs_conflict_set {
     // FDBCS_HOST_TRACE: spans of the calling thread [0] and of the helper [1]
     bool htrace = false;
     std::vector<HSpan> htr[2];
-    uint32_t work_a_seq = 0, work_y_seq = 0;
+    uint32_t work_a_seq = 0;
     double add_prof[4] = {0, 0, 0, 0};  // FDBCS_ADD_PROFILE: ms in add's serial pass, slot, count, fill
     int64_t add_prof_n = 0;
     std::thread worker;
@@ -529,17 +543,28 @@ struct fdbcs_conflict_set {
     LaunchList work_a, work_c;          // the helper's lists
     hipStream_t work_sa = nullptr;
     uint32_t work_need_b = 0;           // the check goes out once b_issued >= this
-    // Stage B's Y half of the previous batch, issued by the helper once the calling thread has
-    // issued its X half.  The calling thread issues record + X, the helper stage A + Y + base
-    // check: their runtime calls split about evenly instead of ~2:1.
+    // Stage B's Y half of the batch whose X half the calling thread issues at this call, issued
+    // by the helper once that X half is out.  The calling thread issues record + X, the helper
+    // stage A + Y + base check: their runtime calls split about evenly instead of ~2:1.
     LaunchList work_y;
     hipStream_t work_ys = nullptr;
+    uint32_t work_y_seq = 0;
     uint32_t work_need_x = 0;            // Y goes out once x_issued >= this
     std::atomic<uint32_t> x_issued{0};   // stage-B X lists issued (calling thread)
     fdbcs_batch* work_y_batch = nullptr; // whose Y the helper holds (calling thread's view)
-    LaunchList rec_a, rec_b, rec_c, rec_y, pending_b, pending_y;
-    hipStream_t pending_ys = nullptr;  // the stream of pending_y
-    fdbcs_batch* pending_batch = nullptr;
+    LaunchList rec_a, rec_b, rec_c, rec_y;
+    // Recorded stage-B lists not yet issued, oldest first.  X(i) is held until the host has seen
+    // batch i's edge word (x_known), at most two calls: it goes out at call i + 1 when the word is
+    // there, at call i + 2 whatever the word says, and before that whenever somebody waits for
+    // batch i or a later one (flush_pending).  Always in batch order.
+    struct Held {
+        fdbcs_batch* batch = nullptr;
+        LaunchList x, y;
+        hipStream_t ys = nullptr;  // the stream of y
+    };
+    Held held[kMaxHold];
+    int n_held = 0;
+    LaunchList go_x;  // the X list being issued at this call (taken out of `held`)
     std::unordered_set<fdbcs_batch*> live;  // batches not yet destroyed (detached if the set goes first)
     // fdbcs_history_export: scratch (per delta boundary), the bounds' tails, scan granules + export
     // words, and the result arrays; all allocated by the first export.  x_valid: a result is pending
@@ -668,6 +693,9 @@ struct fdbcs_batch {
     int64_t out_n = 0;
     uint8_t* out_dev = nullptr;
     int wp = 0;           // the workspace this batch's detect used
+    // its X half was issued whole although it had launches a known edge count of 0 leaves out
+    // (account_stats: counted as too early when the batch turns out edge-free)
+    bool x_unskipped = false;
     int32_t max_len = 0;  // longest key added (the sort stages tail windows only past kSortNxLen)
     int64_t wtail = 0;       // history tail bytes the batch's write endpoints could add (8-byte padded)
     std::vector<int32_t> conf_off, conf_idx;

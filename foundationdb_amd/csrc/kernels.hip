@@ -1500,8 +1500,9 @@ struct EdgePairScan {
         w.bsc->n_pranges = tot[2];
         w.bsc->n_edges = tot[0];
         w.bsc->edge_overflow = (int64_t)tot[0] > w.edge_cap || tot[0] > 0x7fffffffu || tot[1] > 0x7fffffffu ? 1 : 0;
-        // to the host (mapped memory): does this batch have candidate edges?  Read once the
-        // batch's stage A event completed, tagged with the batch's sequence number
+        // to the host (mapped memory): does this batch have candidate edges?  The answer first, then
+        // (system-scope fence) the batch's sequence number: the host trusts the answer only under
+        // this batch's own tag
         if (w.hedge) {
             w.hedge[1] = tot[0] != 0 ? 1u : 0u;
             __threadfence_system();

@@ -137,6 +137,17 @@ typedef struct fdbcs_stats {
     /* Launches of batch-order resolution left out of a batch's X half because the host had seen
      * its stage A find no candidate intra-batch edge (k_resolve, k_combine, k_intra_report). */
     int64_t x_launches_skipped;
+    /* Edge-free batches whose X half was issued with those launches in it: the host issued it
+     * before stage A's edge count had arrived (too early to skip).  Counted at the batch's wait; a
+     * batch closed without a wait is never counted. */
+    int64_t x_edge_free_unskipped;
+    /* The held stage-B lists ("The held X half"): batches held right now (a gauge, at
+     * most 2), X halves issued at their second call because two were held, and batches issued by a
+     * flush from the calling thread (a wait, sync or close reached them, or two went out at one
+     * call and the older one took this path). */
+    int64_t x_held;
+    int64_t x_forced;
+    int64_t x_flushed;
 } fdbcs_stats;
 
 /* newConflictSet() — SkipList.cpp:739-741.  `device` = HIP ordinal. */
