@@ -12,9 +12,10 @@ ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "libfdbcs.so")
 # The engine's sources, named here once: roofline.BUILD_SOURCES (the build id of profile files) and
 # scripts/build_variant.sh (same-box A/B libraries) read these lists.
-SOURCES = ["engine.cpp", "transfer.cpp", "ingest.cpp", "kernels.hip", "transfer.hip", "ingest.hip"]
-HEADERS = ["dkey.h", "engine.h", "engine_impl.h", "transfer.h", "ingest.h", "search.h", "scan.h", "launch.h",
-           "lane_xor.h"]
+SOURCES = ["engine.cpp", "transfer.cpp", "ingest.cpp", "verify.cpp", "kernels.hip", "transfer.hip", "ingest.hip",
+           "verify.hip"]
+HEADERS = ["dkey.h", "engine.h", "engine_impl.h", "transfer.h", "ingest.h", "verify.h", "search.h", "scan.h",
+           "launch.h", "lane_xor.h"]
 PUBLIC_HEADER = "include/fdb_conflict_set.h"  # relative to the repository root
 ARCH = os.environ.get("FDBCS_OFFLOAD_ARCH", "gfx950")
 

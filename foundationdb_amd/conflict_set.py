@@ -133,6 +133,95 @@ class HistoryDigest(NamedTuple):
         return cls(int(d.n), int(d.key_bytes), int(d.header_version), (int(d.sum[0]), int(d.sum[1])))
 
 
+# fdbcs_history_verify: check classes (bit c of `checks`, row c of a tier's report) and the arrays an
+# override can name (FDBCS_VERIFY_OV_*).
+VERIFY_CLASSES = ("order", "padding", "tails", "versions", "dominance", "lvl1", "lvl2", "lvl3", "skey8", "skey",
+                  "dir", "edir")
+VERIFY_ARRAYS = ("key", "len_tail", "version", "lvl1", "lvl2", "lvl3", "skey8", "skey", "dir", "edir", "tail_word")
+
+
+class _CVerifyClass(ctypes.Structure):
+    _fields_ = [("examined", ctypes.c_int64), ("violations", ctypes.c_int64), ("first", ctypes.c_int64)]
+
+
+class _CVerifyTier(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_int64), ("cls", _CVerifyClass * len(VERIFY_CLASSES))]
+
+
+class _CVerifyReport(ctypes.Structure):
+    """fdbcs_verify_report."""
+    _fields_ = [("tier", _CVerifyTier * 2), ("edir_trusted", ctypes.c_int64)]
+
+
+class _CVerifyOverride(ctypes.Structure):
+    """fdbcs_verify_override."""
+    _fields_ = [("what", ctypes.c_int32), ("tier", ctypes.c_int32), ("level", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("index", ctypes.c_int64), ("xor_lo", ctypes.c_uint64),
+                ("xor_hi", ctypes.c_uint64)]
+
+
+class VerifyOverride(NamedTuple):
+    """One what-if element of ConflictSet.verify (a debug facility): the verifier reads element
+    `index` of array `what` (a VERIFY_ARRAYS name) of `tier` (0 base, 1 delta) as its stored words
+    XOR (xor_lo, xor_hi); nothing in device memory changes."""
+    what: str
+    tier: int
+    index: int
+    xor_lo: int = 0
+    xor_hi: int = 0
+    level: int = 0
+
+    def c_struct(self) -> "_CVerifyOverride":
+        m = (1 << 64) - 1
+        return _CVerifyOverride(VERIFY_ARRAYS.index(self.what) + 1, int(self.tier), int(self.level), 0, int(self.index),
+                                int(self.xor_lo) & m, int(self.xor_hi) & m)
+
+
+def _cls(cls) -> int:
+    return VERIFY_CLASSES.index(cls) if isinstance(cls, str) else int(cls)
+
+
+class VerifyReport:
+    """fdbcs_verify_report: per tier (0 base, 1 delta) its size and, per check class, the elements
+    examined, the violations and the least violating index (-1: none)."""
+
+    def __init__(self, sizes, rows, edir_trusted):
+        self.sizes = tuple(int(x) for x in sizes)
+        self.rows = tuple(tuple(tuple(int(x) for x in r) for r in t) for t in rows)  # [tier][class] -> 3 ints
+        self.edir_trusted = int(edir_trusted)
+
+    @classmethod
+    def _of(cls, r: "_CVerifyReport") -> "VerifyReport":
+        return cls([r.tier[t].n for t in range(2)],
+                   [[(c.examined, c.violations, c.first) for c in r.tier[t].cls] for t in range(2)], r.edir_trusted)
+
+    @property
+    def ok(self) -> bool:
+        return not any(r[1] for t in self.rows for r in t)
+
+    def examined(self, tier: int, cls) -> int:
+        return self.rows[tier][_cls(cls)][0]
+
+    def violations(self, tier: int, cls) -> int:
+        return self.rows[tier][_cls(cls)][1]
+
+    def first(self, tier: int, cls) -> int:
+        return self.rows[tier][_cls(cls)][2]
+
+    def as_dict(self) -> dict:
+        return {"edir_trusted": self.edir_trusted,
+                "tiers": [{"n": self.sizes[t],
+                           **{name: dict(zip(("examined", "violations", "first"), self.rows[t][c]))
+                              for c, name in enumerate(VERIFY_CLASSES)}} for t in range(2)]}
+
+    def __eq__(self, other):
+        return isinstance(other, VerifyReport) and self.as_dict() == other.as_dict()
+
+    def __repr__(self):
+        bad = [(t, VERIFY_CLASSES[c], r) for t in range(2) for c, r in enumerate(self.rows[t]) if r[1]]
+        return f"VerifyReport(sizes={self.sizes}, edir_trusted={self.edir_trusted}, violations={bad})"
+
+
 class _CKeyResolvers(ctypes.Structure):
     """fdbcs_key_resolvers."""
     _fields_ = [
@@ -168,6 +257,11 @@ SIGNATURES = {
     "fdbcs_history_digest_ranges": (ctypes.c_int, [_VP, _I32, _VP, _VP, ctypes.c_int, ctypes.c_int, _I64, _VP]),
     "fdbcs_history_digest_arrays_ranges": (ctypes.c_int, [_I64, _VP, _VP, _VP, _I64, _I32, _VP, _VP, ctypes.c_int,
                                                           ctypes.c_int, _VP]),
+    "fdbcs_history_verify": (ctypes.c_int, [_VP, ctypes.c_uint32, ctypes.POINTER(_CVerifyOverride),
+                                            ctypes.POINTER(_CVerifyReport)]),
+    "fdbcs_history_verify_timing": (ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_double),
+                                                   ctypes.POINTER(ctypes.c_double)]),
+    "fdbcs_history_verify_sizes": (ctypes.c_int, [ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     "fdbcs_history_split_keys": (ctypes.c_int, [_VP, _VP, _I32, _VP, _I32, _I32, ctypes.POINTER(_I64),
                                                 ctypes.POINTER(_I64)]),
     "fdbcs_history_split_keys_read": (ctypes.c_int, [_VP, _VP, _I64, _VP, _I64]),
@@ -619,6 +713,27 @@ class ConflictSet:
         """Milliseconds of the last digest's kernels (device) and of the whole call (host)."""
         a, b = ctypes.c_double(), ctypes.c_double()
         _check(load_library().fdbcs_history_digest_timing(self._h, ctypes.byref(a), ctypes.byref(b)), "digestTiming")
+        return a.value, b.value
+
+    def verify(self, checks=None, override: Optional[VerifyOverride] = None) -> VerifyReport:
+        """fdbcs_history_verify: recompute on the device everything a lookup relies on (key order,
+        padding, tails, the range-max levels, the samples, both directories, the delta's dominance
+        over the base) where the set lies, and report per tier and class what is wrong and where.
+        `checks`: an iterable of VERIFY_CLASSES names or a bit mask (default: all).  `override`: one
+        what-if element (debug).  Read-only; raises FdbcsError(FDBCS_E_STATE) with batches in flight."""
+        mask = 0
+        if checks is not None:
+            mask = int(checks) if isinstance(checks, int) else sum(1 << _cls(c) for c in checks)
+        ov = override.c_struct() if override is not None else None
+        out = _CVerifyReport()
+        _check(load_library().fdbcs_history_verify(self._h, mask, ctypes.byref(ov) if ov is not None else None,
+                                                   ctypes.byref(out)), "historyVerify")
+        return VerifyReport._of(out)
+
+    def verify_timing(self) -> Tuple[float, float]:
+        """Milliseconds of the last verify's kernels (device) and of the whole call (host)."""
+        a, b = ctypes.c_double(), ctypes.c_double()
+        _check(load_library().fdbcs_history_verify_timing(self._h, ctypes.byref(a), ctypes.byref(b)), "verifyTiming")
         return a.value, b.value
 
     def digest_ranges(self, bounds, floor: Optional[int] = None, open_lo: bool = False,

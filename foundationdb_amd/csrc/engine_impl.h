@@ -608,6 +608,11 @@ struct fdbcs_conflict_set {
     DBuf i_dstate;
     int32_t i_path = 0;                           // 0: folded into a new base, 1: merged into the delta
     int64_t i_info_base = 0, i_info_before = 0, i_info_after = 0;  // base size; delta size around it
+    // fdbcs_history_verify: its counts, first indices and one true maximum per level-3 entry (allocated
+    // by the first verify; a set that never verifies holds nothing of it)
+    DBuf v_state;
+    Span v_span;                                  // around the verify's kernels
+    double v_ms_kernels = 0, v_ms_host = 0;       // of the last verify (fdbcs_history_verify_timing)
 };
 
 // Host/device staging of one batch.  Batches are short-lived (one per commit batch, as the

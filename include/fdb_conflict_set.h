@@ -271,6 +271,96 @@ int fdbcs_history_digest_arrays_ranges(int64_t n, const uint8_t* key_bytes, cons
                                        const int64_t* versions, int64_t header_version, int32_t n_bounds,
                                        const uint8_t* bound_bytes, const int64_t* bound_offsets, int open_lo,
                                        int open_hi, fdbcs_digest* out /* [K] */);
+/* Verify the stored state: one read-only pass over both tiers, on the device, that recomputes
+ * everything a lookup relies on, independently of the kernels that build it and of the lookups, and
+ * says what is wrong and where.  No reference counterpart.  The digest compares the canonical history
+ * and goes through the lookups; this checks what the lookups stand on.  After a restore or a
+ * hand-over: digest equal and verify clean.
+ * Tier 0 is the base (its size: the device scalar n), tier 1 the current delta buffer (ndb[current]);
+ * the non-current buffers are scratch and are not read.  A tier of n boundaries holds keys (a
+ * zero-padded 16-byte prefix as two big-endian words, a length, and for a key over 16 bytes the 8-byte
+ * unit of its tail in the tail arena) and versions (INT64_MIN in the delta: a hole, the base shows
+ * through).  Check classes, each per tier, each with three counts (examined, violations, least
+ * violating index or -1):
+ *   ORDER      key[i] < key[i+1] in the full order (prefix words, tail bytes, length), i + 1 < n;
+ *              index i.  A pair that needs a tail TAILS flags is examined and not judged.
+ *   PADDING    the prefix bytes at and past len are zero (every key).  The bytes between the end of a
+ *              tail and its 8-byte pad are NOT checked: the merge copies whole words from a batch's
+ *              packed tails, and every comparison masks them off.
+ *   TAILS      for len > 16: 8 * unit + 8 * ceil((len - 16) / 8) <= tail_used (only long keys are
+ *              examined: the unit of a shorter key is never read by anything).
+ *   VERSIONS   no base version is a hole (base only).
+ *   DOMINANCE  (reported under the delta) a delta boundary j with a version v covers [d_j, d_j+1): no
+ *              base version that holds inside that span exceeds v.  Examined pair by pair: (j, the base
+ *              boundary at or below d_j, the set's header version if there is none) and (j, every base
+ *              boundary strictly inside the span); each pair with a greater base version is one
+ *              violation at index j.  This is what makes "the maximum of the two tiers' maxima" the
+ *              version a read is checked against.
+ *   LVL1/LVL2  lvl1[b] (lvl2[c]) equals the maximum of the versions [64 b, 64 b + 64) ([4096 c, ...))
+ *              clipped to n, for every entry that covers a boundary; index b (c).
+ *   LVL3       for entry j < ceil(n / 262144): the maximum of its eight replica words equals the
+ *              span's true maximum (so none exceeds it; a replica below it is allowed); index j.
+ *   SKEY8      skey8[e] == prefix of key[8 e], e < ceil(n / 8); index e.
+ *   SKEY       skey[L][d] == prefix of key[64 * 8^L * d] for every level L < 12 and every d whose
+ *              boundary is below n; index L << 48 | d.
+ *   DIR        (base, when the set has a directory) for every slot v in [0, dir_top + 1]: dir[v] is the
+ *              number of group starts (key[8 e]) whose directory slot is below v: it lies in
+ *              [0, ceil(n / 8)], start dir[v] - 1 has a slot below v and start dir[v] has not; index
+ *              v, examined dir_top + 2.  Beside it, the slots of the group starts never decrease: a
+ *              start whose slot is below its predecessor's is a violation at that slot.
+ *   EDIR       (delta) the same for every entry whose epoch tag is the current one; the others are
+ *              left alone (edir_trusted counts the current ones).  Without a current epoch nothing is
+ *              examined.
+ * An empty tier is clean with nothing examined.  checks: a bit per class (FDBCS_VERIFY_*), 0 = all.
+ * The verifier survives the states it looks for: sizes are clamped to the allocated capacities, and no
+ * stored value (a tail unit, a directory count) is used as an index before it is checked; what
+ * depends on a value out of range is skipped.  Counts are atomic sums and firsts atomic minima, so a
+ * report is deterministic.
+ * Override (ov, or NULL: the set as stored), a debug facility: every kernel reads the one element it
+ * names as its stored words XOR the masks; nothing in device memory changes, so a what-if needs no
+ * restore and no other entry point ever sees a damaged set.  index counts elements of the array
+ * (LVL3: replica word 8 j + r; TAIL_WORD: 8-byte word of the arena, tier ignored; SKEY: entry d of
+ * `level`).  A 16-byte element takes xor_hi on its first word and xor_lo on its second; (len, tail)
+ * takes xor_lo on len and xor_hi on the unit; smaller elements take xor_lo.
+ * Returns FDBCS_OK whether or not violations were found; FDBCS_E_STATE with batches in flight;
+ * FDBCS_E_INVALID for a NULL handle or out, an unknown check bit, or an override that names no
+ * element of the set as it stands.  The set is not modified, a pending export or split-keys result
+ * stays pending, scratch is a few hundred bytes the set owns from the first call on. */
+#define FDBCS_VERIFY_CLASSES 12
+enum {
+    FDBCS_VERIFY_ORDER = 1 << 0, FDBCS_VERIFY_PADDING = 1 << 1, FDBCS_VERIFY_TAILS = 1 << 2,
+    FDBCS_VERIFY_VERSIONS = 1 << 3, FDBCS_VERIFY_DOMINANCE = 1 << 4, FDBCS_VERIFY_LVL1 = 1 << 5,
+    FDBCS_VERIFY_LVL2 = 1 << 6, FDBCS_VERIFY_LVL3 = 1 << 7, FDBCS_VERIFY_SKEY8 = 1 << 8,
+    FDBCS_VERIFY_SKEY = 1 << 9, FDBCS_VERIFY_DIR = 1 << 10, FDBCS_VERIFY_EDIR = 1 << 11
+};
+enum {
+    FDBCS_VERIFY_OV_KEY = 1, FDBCS_VERIFY_OV_LEN_TAIL = 2, FDBCS_VERIFY_OV_VERSION = 3, FDBCS_VERIFY_OV_LVL1 = 4,
+    FDBCS_VERIFY_OV_LVL2 = 5, FDBCS_VERIFY_OV_LVL3 = 6, FDBCS_VERIFY_OV_SKEY8 = 7, FDBCS_VERIFY_OV_SKEY = 8,
+    FDBCS_VERIFY_OV_DIR = 9, FDBCS_VERIFY_OV_EDIR = 10, FDBCS_VERIFY_OV_TAIL_WORD = 11
+};
+typedef struct fdbcs_verify_class {
+    int64_t examined, violations, first; /* first: least violating index, -1 when none */
+} fdbcs_verify_class;
+typedef struct fdbcs_verify_tier {
+    int64_t n; /* the tier's size as the device scalar gives it */
+    fdbcs_verify_class cls[FDBCS_VERIFY_CLASSES];
+} fdbcs_verify_tier;
+typedef struct fdbcs_verify_report {
+    fdbcs_verify_tier tier[2]; /* 0 base, 1 delta */
+    int64_t edir_trusted;      /* delta-directory entries of the current epoch */
+} fdbcs_verify_report;
+typedef struct fdbcs_verify_override {
+    int32_t what, tier, level, reserved; /* FDBCS_VERIFY_OV_*; level: SKEY only */
+    int64_t index;
+    uint64_t xor_lo, xor_hi;
+} fdbcs_verify_override;
+int fdbcs_history_verify(fdbcs_conflict_set* cs, uint32_t checks /* bit per class, 0 = all */,
+                         const fdbcs_verify_override* ov /* NULL: the set as stored */, fdbcs_verify_report* out);
+/* Diagnostics: device time of the last verify's kernels and host time of the whole call (ms). */
+int fdbcs_history_verify_timing(fdbcs_conflict_set* cs, double* ms_kernels, double* ms_host);
+/* sizeof(fdbcs_verify_report) and sizeof(fdbcs_verify_override) as the library was built (600, 40):
+ * what a binding checks its own layout against. */
+int fdbcs_history_verify_sizes(int64_t* report_bytes, int64_t* override_bytes);
 /* Up to `want` boundary keys strictly inside (lo, hi), strictly ascending, in original bytes: bounds
  * to bisect a range on without an export.  They are taken at evenly spaced positions among the
  * boundaries inside the range of whichever tier (base or delta) holds more of them there: fewer than

@@ -8,6 +8,7 @@ conflicting-read reports must match oracle/skiplist_baseline.cpp batch by batch.
 
     python3 scripts/stress_parity.py [seconds] [first_seed] [--state-every K] [--digest-every K]
                                      [--import-every K] [--import-into delta] [--read-versions-every K]
+                                     [--verify-every K]
 
 --state-every K (default off) also feeds the semantic oracle and compares the engine's exported
 history (ConflictSet.dump_history at floor = oldest version) with the canonical form of the oracle's
@@ -35,6 +36,11 @@ the oracle's boundaries, by a generator of its own: the other options' streams a
 tenth range empty) with the plain-Python model (tests/read_versions_model.py) on the oracle's dump,
 at floor = oldest version.
 
+--verify-every K (default off) runs ConflictSet.verify every K batches (and after a merge of
+--import-every): the stored tiers, the range-max levels, the samples and both directories are
+recomputed where they lie, so a wrong index shows in the batch that built it whether or not a later
+read goes through it.  On a violation the report is printed and the round fails.
+
 Exit status 1 and the failing seed on the first mismatch."""
 import os
 import sys
@@ -55,6 +61,7 @@ from tests import read_versions_model  # noqa: E402
 
 DIGESTS = [0]  # digests compared (--digest-every)
 QUERIES = [0]  # ranges compared (--read-versions-every)
+VERIFIES = [0]  # clean verify reports (--verify-every)
 
 KNOBS = {
     "FDBCS_DIR_BITS": ["0", "0", "16", "18"],
@@ -103,7 +110,18 @@ def merge_round(rng, e, o, so, key, hdr, now, pending, into="base"):
     return None, h
 
 
-def one(seed, state_every=0, import_every=0, import_into="base", digest_every=0, read_versions_every=0):
+def verify_state(e, what):
+    """None if ConflictSet.verify reports the stored state clean, else the error (the report is printed)."""
+    rep = e.cs.verify()
+    VERIFIES[0] += 1
+    if rep.ok:
+        return None
+    print(rep.as_dict(), flush=True)
+    return f"verify {what}: {rep!r}"
+
+
+def one(seed, state_every=0, import_every=0, import_into="base", digest_every=0, read_versions_every=0,
+        verify_every=0):
     rng = np.random.default_rng(seed)
     qrng = np.random.default_rng([seed, 15])
     for k, vals in KNOBS.items():
@@ -167,6 +185,10 @@ def one(seed, state_every=0, import_every=0, import_into="base", digest_every=0,
         co = {t: sorted(v) for t, v in co.items() if v}
         if ce != co:
             return f"conflicting reads batch {i}"
+        if verify_every and (i + 1) % verify_every == 0:
+            err = verify_state(e, f"batch {i}")
+            if err:
+                return err
         if so is not None:
             so.detect(pb, now, oldest)
             if digest_every and (i + 1) % digest_every == 0:
@@ -205,6 +227,10 @@ def one(seed, state_every=0, import_every=0, import_into="base", digest_every=0,
                 merges += 1
                 if err:
                     return f"batch {i}: {err}"
+                if verify_every:
+                    err = verify_state(e, f"after the merge behind batch {i}")
+                    if err:
+                        return err
     e.cs.close()
     return None
 
@@ -237,13 +263,18 @@ def main():
         k = args.index("--read-versions-every")
         read_versions_every = int(args[k + 1])
         del args[k:k + 2]
+    verify_every = 0
+    if "--verify-every" in args:
+        k = args.index("--verify-every")
+        verify_every = int(args[k + 1])
+        del args[k:k + 2]
     budget = float(args[0]) if len(args) > 0 else 120.0
     seed = int(args[1]) if len(args) > 1 else 1
     oracle.build()
     t0 = time.time()
     n = 0
     while time.time() - t0 < budget:
-        err = one(seed, state_every, import_every, import_into, digest_every, read_versions_every)
+        err = one(seed, state_every, import_every, import_into, digest_every, read_versions_every, verify_every)
         knobs = {k: os.environ[k] for k in KNOBS}
         if err:
             print(f"MISMATCH seed {seed} knobs {knobs}: {err}", flush=True)
@@ -257,6 +288,8 @@ def main():
         print(f"stress: {DIGESTS[0]} digests equal to the oracle's")
     if read_versions_every:
         print(f"stress: {QUERIES[0]} read versions equal to the model's")
+    if verify_every:
+        print(f"stress: {VERIFIES[0]} verify reports clean")
     if import_every:
         print(f"stress: {PATHS[1]} merges into the delta, {PATHS[0]} folded into a new base")
 
